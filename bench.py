@@ -33,6 +33,7 @@ matrix, b and x already resident in HBM.
               bounded number of iterations; plus its OpenMP variant as `cpu_baseline_omp`.
 
   python bench.py --gpus 1 --steps 5 --warmup 1
+  python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR     # + the last step's x and residuals as .npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
          --master-port 29500 bench.py --gpus 8 --steps 5 --warmup 1
 """
@@ -155,7 +156,37 @@ def parse():
     ap.add_argument("--no-profile", action="store_true",
                     help="do not event-time the in-loop SpMV (roofline then comes from a "
                          "separate back-to-back SpMV loop)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed -- the solution x and the solve's "
+                         "residuals, what the caller of apply gets back -- as DIR/<name>.npy (float64, at most 64 MB "
+                         "in all: a fixed, seeded sample of the rows of a larger x), to compare two builds output for "
+                         "output; the inputs are the same from run to run for the same arguments")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 64 * 1000 ** 2
+
+
+def dump_outputs(directory, s, perf, rank, world):
+    """--dump-outputs: the last timed step's results as float64 .npy files (one set per rank at N > 1, suffix _rank<r>).
+    x           the solution, downloaded in the caller's numbering; when the whole vector exceeds this rank's share of
+                DUMP_BYTES, the rows x_rows (sorted, drawn with a fixed seed -- the same rows on every run) of it
+    residuals   [initial residual, final residual, norm factor, iterations] as the solve reported them"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    share = (DUMP_BYTES - (1 << 20)) // world          # (1 MB left for the residuals)
+    x = s.download_solution()
+    if x.nbytes > share:
+        rows = np.sort(np.random.default_rng(20241016).choice(x.size, share // 16, replace=False))
+        np.save(os.path.join(directory, f"x_rows{tag}.npy"), rows.astype(np.float64))
+        x = x[rows]
+    np.save(os.path.join(directory, f"x{tag}.npy"), x.astype(np.float64))
+    np.save(os.path.join(directory, f"residuals{tag}.npy"),
+            np.array([perf.initial_residual, perf.final_residual, perf.norm_factor, perf.n_iterations], np.float64))
 
 
 def kernels_sha16():
@@ -647,6 +678,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:                    # before anything below touches the solver's resident x
+        dump_outputs(args.dump_outputs, s, perfs[-1], rank, world)
 
     # turns actually done: CG / GMRES report checks (= turns + 1), BiCGStab reports checks / 2
     bicg = args.solver == "GKOBiCGStab"
