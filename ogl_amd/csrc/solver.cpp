@@ -307,7 +307,7 @@ int32_t ogl_solver::xcd_group() const
     return v >= 0 ? v : pat_xcd_group;
 }
 
-DevCsr ogl_solver::csr() const
+DevCsr ogl_solver::csr(bool packed) const
 {
     DevCsr A;
     A.n_rows = pat.n_rows;
@@ -315,334 +315,15 @@ DevCsr ogl_solver::csr() const
     A.row_ptrs = d_row_ptrs.p;
     A.cols = d_cols.p;
     A.vals = d_vals.p;
-    A.stream = 12.0 * (double)pat.local_nnz + 44.0 * (double)pat.n_rows + turn_extra_bytes() > stream_above_bytes();
+    A.stream = streamed(12.0 * (double)pat.local_nnz + 44.0 * (double)pat.n_rows);
     A.xcd_group = xcd_group();
     A.lds_rounds = prop("spmvLdsRounds", 1.0) == 2.0 ? 2 : 1;
     if (d_band_order.n) {
         A.block_order = d_band_order.p;
         A.n_blocks = (int32_t)d_band_order.n;
     }
-    if (s21_use && s21_state == 1) {
-        A.chunks21 = d_s21_chunks.p;
-        A.codes21 = d_s21_codes.p;
-        A.far_idx21 = d_s21_far_idx.p;
-        A.far_col21 = d_s21_far_col.p;
-    }
+    if (packed) s21_dev.view(A);
     return A;
-}
-
-// Packed columns for the CSR-stream kernel, from the device pattern (setup_kernels.hip).  The values stay the
-// CSR array: nothing to refresh per coefficient update.
-int ogl_solver::build_stream21()
-{
-    hipStream_t st = reg->stream;
-    s21_state = -1;
-    s21_use = false;
-    const int32_t N = pat.n_rows;
-    const size_t nc = (size_t)n_chunks(N);
-    if (N == 0) return OGL_OK;
-    DevBuf<int32_t> words, tmp, flags, far;
-    OGL_TRY(d_s21_chunks.alloc(nc, st));
-    OGL_TRY(words.alloc(nc + 1, st));
-    OGL_TRY(far.alloc(nc + 1, st));
-    OGL_TRY(tmp.alloc(scan_tmp_len((int64_t)nc), st));
-    OGL_TRY(flags.alloc(1, st));
-    Stream21Build b;
-    b.n_rows = N;
-    b.row_ptrs = d_row_ptrs.p;
-    b.cols = d_cols.p;
-    b.chunks = d_s21_chunks.p;
-    b.words = words.p;
-    b.scan_tmp = tmp.p;
-    b.flags = flags.p;
-    b.far = far.p;
-    launch_stream21_plan(st, b);
-    int32_t total = 0, total_far = 0;
-    OGL_HIP_CHECK(hipMemcpyAsync(&total, words.p + nc, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    OGL_HIP_CHECK(hipMemcpyAsync(&total_far, far.p + nc, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    OGL_HIP_CHECK(hipStreamSynchronize(st));
-    OGL_HIP_CHECK(hipGetLastError());
-    // (a pattern whose chunks reach far beyond their 2^21-column windows all over the place -- a random numbering of a
-    //  large mesh -- is left to the plain CSR-stream kernel)
-    if (total < 0 || total_far < 0 || (double)total_far > STREAM21_MAX_FAR * (double)pat.local_nnz) {
-        d_s21_chunks.release();
-        return OGL_OK;
-    }
-    OGL_TRY(d_s21_codes.alloc((size_t)total + 1, st));
-    OGL_TRY(d_s21_far_idx.alloc((size_t)total_far + 1, st));
-    OGL_TRY(d_s21_far_col.alloc((size_t)total_far + 1, st));
-    launch_stream21_fill(st, b, d_s21_codes.p, d_s21_far_idx.p, d_s21_far_col.p);
-    OGL_HIP_CHECK(hipStreamSynchronize(st));
-    OGL_HIP_CHECK(hipGetLastError());
-    s21_state = 1;
-    props["csr21FarEntries"] = (double)total_far;
-    // bytes one SpMV reads of this layout: values + code words + row pointers + chunk headers (+ the far lists and the
-    // values and x their entries read a second time)
-    props["csr21MatrixBytes"] = 8.0 * (double)pat.local_nnz + 16.0 * (double)total + 4.0 * ((double)N + 1.0) +
-                                16.0 * (double)nc + 24.0 * (double)total_far;
-    return OGL_OK;
-}
-
-DevEll ogl_solver::ell() const
-{
-    DevEll E;
-    E.n_rows = pat.n_rows;
-    E.width = ell_width;
-    E.stride = ell_stride;
-    E.cols = d_ell_cols.p;
-    E.vals = d_ell_vals.p;
-    E.stream = 12.0 * (double)ell_width * (double)ell_stride + 40.0 * (double)pat.n_rows + turn_extra_bytes() > stream_above_bytes();
-    return E;
-}
-
-// matrixFormat Ell (CsrMatrixWrapper.H:146-149): `width` = longest row; slot i of row r lives at
-// i * stride + r.  ell_map holds the CSR position of each slot (-1 = padding), so the values are
-// refreshed from the freshly permuted CSR values whatever path produced them.
-int ogl_solver::build_ell()
-{
-    hipStream_t st = reg->stream;
-    OGL_TRY(download_local_pattern(pat));
-    const int32_t N = pat.n_rows;
-    int32_t width = 0;
-    for (int32_t r = 0; r < N; ++r) width = std::max(width, pat.row_ptrs[r + 1] - pat.row_ptrs[r]);
-    const int64_t stride = ((int64_t)N + 1) / 2 * 2 + 2;  // even, and the pair load of the last row fits
-    const size_t len = (size_t)width * (size_t)stride;
-    std::vector<int32_t> cols(len, -1), map(len, -1);
-    for (int32_t r = 0; r < N; ++r)
-        for (int32_t k = pat.row_ptrs[r], i = 0; k < pat.row_ptrs[r + 1]; ++k, ++i) {
-            cols[(size_t)i * stride + r] = pat.cols[k];
-            map[(size_t)i * stride + r] = k;
-        }
-    OGL_TRY(d_ell_cols.alloc(len + 2, st));
-    OGL_TRY(d_ell_map.alloc(len + 2, st));
-    OGL_TRY(d_ell_vals.alloc(len + 2, st));
-    OGL_TRY(reg->stager.h2d(d_ell_cols.p, cols.data(), len * sizeof(int32_t), st));
-    OGL_TRY(reg->stager.h2d(d_ell_map.p, map.data(), len * sizeof(int32_t), st));
-    ell_width = width;
-    ell_stride = stride;
-    ell_ready = true;
-    return OGL_OK;
-}
-
-DevSell ogl_solver::sell() const
-{
-    DevSell S;
-    S.n_rows = pat.n_rows;
-    S.chunks = d_sell_chunks.p;
-    S.dict = d_sell_dict.p;
-    S.codes = d_sell_codes.p;
-    S.vals = d_sell_vals.p;
-    S.stream = sell_bytes + 40.0 * (double)pat.n_rows + turn_extra_bytes() > stream_above_bytes();
-    S.xcd_group = xcd_group();
-    if (d_band_order.n) {
-        S.block_order = d_band_order.p;
-        S.n_blocks = (int32_t)d_band_order.n;
-    }
-    if (n_spill) {
-        S.spill_chunk_ptr = d_spill_chunks.p;
-        S.spill_rows = d_spill_rows.p;
-        S.spill_ptrs = d_spill_ptrs.p;
-        S.spill_cols = d_spill_cols.p;
-        S.spill_vals = d_spill_vals.p;
-    }
-    return S;
-}
-
-DevSym ogl_solver::sym() const
-{
-    DevSym S;
-    S.n_rows = pat.n_rows;
-    S.nd = sym_nd;
-    for (int j = 0; j < 4; ++j) S.d[j] = sym_d[j];
-    S.mask = d_sym_mask.p;
-    S.planes = d_sym_planes.p;
-    S.stream = 8.0 * (double)d_sym_planes.n + 41.0 * (double)pat.n_rows + turn_extra_bytes() > stream_above_bytes();
-    if (d_sym_order.n && !band_order_off) {
-        S.block_order = d_sym_order.p;
-        S.n_blocks = (int32_t)d_sym_order.n;
-    }
-    return S;
-}
-
-DevSymx ogl_solver::symx() const
-{
-    DevSymx S;
-    S.n_rows = pat.n_rows;
-    S.chunks = d_symx_chunks.p;
-    S.mask = d_symx_mask.p;
-    S.planes = d_symx_planes.p;
-    S.ex_rowptr = d_symx_ex_rowptr.p;
-    S.ex_cols = d_symx_ex_cols.p;
-    S.ex_vals = d_symx_ex_vals.p;
-    S.stream = symx_bytes + 41.0 * (double)pat.n_rows + turn_extra_bytes() > stream_above_bytes();
-    S.fast = symx_fast;
-    S.n_blocks = (int32_t)d_symx_chunks.n;
-    S.chunks_general = d_symx_chunks_general.p;
-    S.n_blocks_general = (int32_t)d_symx_chunks_general.n;
-    S.ex_lrow = d_symx_ex_lrow.p;
-    S.xcd_group = xcd_group();
-    return S;
-}
-
-// Per-chunk half storage against the compressed full-storage copy, once per pattern (same bits either way): the
-// former moves about a third fewer bytes, but rows with explicit entries cost it a merge; the faster one stays.
-int ogl_solver::tune_symx()
-{
-    hipStream_t st = reg->stream;
-    EventPair ev;
-    OGL_HIP_CHECK(ev_create(&ev[0]));
-    OGL_HIP_CHECK(ev_create(&ev[1]));
-    OGL_HIP_CHECK(hipMemsetAsync(d_p.p, 0, ((size_t)pat.n_rows + 2) * sizeof(double), st));
-    SpmvDots dots;
-    dots.with = d_p.p;
-    dots.part = d_part0.p;
-    constexpr int WARM = 2, TIMED = 5;
-    float best[2] = {1e30f, 1e30f};  // [0] compressed full storage, [1] per-chunk half storage
-    for (int round = 0; round < WARM + TIMED; ++round)
-        for (int which = 0; which < 2; ++which) {
-            OGL_HIP_CHECK(hipEventRecord(ev[0], st));
-            if (which)
-                launch_spmv_symx(st, symx(), SPMV_PLAIN, d_p.p, nullptr, d_q.p, dots, nullptr);
-            else
-                launch_spmv_sell(st, sell(), SPMV_PLAIN, d_p.p, nullptr, d_q.p, dots, nullptr);
-            OGL_HIP_CHECK(hipEventRecord(ev[1], st));
-            OGL_HIP_CHECK(hipEventSynchronize(ev[1]));
-            float ms = 0;
-            OGL_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            if (round >= WARM) best[which] = std::min(best[which], ms);
-        }
-    OGL_HIP_CHECK(hipGetLastError());
-    props["spmvTunedSellUs"] = 1e3 * best[0];
-    props["spmvTunedSymxUs"] = 1e3 * best[1];
-    OGL_HIP_CHECK(hipStreamSynchronize(st));
-    if (best[1] <= best[0]) {  // half storage stays
-        for (auto *b : {&d_sell_dict, &d_sell_map, &d_spill_rows, &d_spill_ptrs, &d_spill_cols, &d_spill_map,
-                        &d_spill_chunks})
-            b->release();
-        d_sell_chunks.release();
-        d_sell_codes.release();
-        d_sell_vals.release();
-        d_spill_vals.release();
-        n_spill = n_spill_rows = 0;
-        sell_state = -1;
-        props["sellMatrixBytes"] = symx_bytes;
-    } else {                   // full storage stays
-        symx_state = -1;
-        for (auto *b : {&d_symx_map, &d_symx_ex_rowptr, &d_symx_ex_cols, &d_symx_ex_map, &d_symx_ex_lrow}) b->release();
-        d_symx_chunks.release();
-        d_symx_chunks_general.release();
-        d_symx_mask.release();
-        d_symx_planes.release();
-        d_symx_ex_vals.release();
-        props["symmetricHalf"] = 0.0;
-        props["symmetricHalfPerChunk"] = 0.0;
-        props["sellMatrixBytes"] = sell_bytes;
-    }
-    return OGL_OK;
-}
-
-// Half storage with per-chunk distances (build_symx_layout, host side: it needs the whole pattern); the planes
-// and the explicit entries are refreshed from the CSR values through their maps.
-int ogl_solver::build_symx()
-{
-    hipStream_t st = reg->stream;
-    symx_state = -1;
-    if (pat.n_rows == 0) return OGL_OK;
-    OGL_TRY(download_local_pattern(pat));
-    SymxLayout L;
-    if (!build_symx_layout(pat.n_rows, pat.row_ptrs.data(), pat.cols.data(), L)) return OGL_OK;
-    const size_t nex = L.ex_cols.size();
-    // headers in dispatch order, each naming its chunk (symx_block_order): the lean kernel's list, the general one's
-    std::vector<SymxChunk> hdr_ord[2];
-    int64_t general_chunks = 0;
-    for (int g = 0; g < 2; ++g) {
-        std::vector<int32_t> order;
-        symx_block_order(L, g == 1, order);
-        hdr_ord[g].resize(order.size());
-        for (size_t b = 0; b < order.size(); ++b) {
-            if (order[b] >= 0) hdr_ord[g][b] = L.chunks[(size_t)order[b]];
-            else hdr_ord[g][b] = SymxChunk{};
-            hdr_ord[g][b].chunk = order[b];
-            if (g == 1 && order[b] >= 0) ++general_chunks;
-        }
-    }
-    OGL_TRY(d_symx_chunks.alloc(hdr_ord[0].size(), st));
-    OGL_TRY(d_symx_chunks_general.alloc(hdr_ord[1].size(), st));
-    OGL_TRY(d_symx_ex_lrow.alloc(nex + NNZ_PAD, st));
-    OGL_TRY(d_symx_mask.alloc(L.mask.size(), st));
-    OGL_TRY(d_symx_map.alloc(L.map.size(), st));
-    OGL_TRY(d_symx_planes.alloc(L.map.size(), st));
-    OGL_TRY(d_symx_ex_rowptr.alloc(std::max<size_t>(1, L.ex_rowptr.size()), st));
-    OGL_TRY(d_symx_ex_cols.alloc(nex + NNZ_PAD, st));
-    OGL_TRY(d_symx_ex_map.alloc(nex + NNZ_PAD, st));
-    OGL_TRY(d_symx_ex_vals.alloc(nex + NNZ_PAD, st));
-    if (!hdr_ord[0].empty())
-        OGL_TRY(reg->stager.h2d(d_symx_chunks.p, hdr_ord[0].data(), hdr_ord[0].size() * sizeof(SymxChunk), st));
-    if (!hdr_ord[1].empty())
-        OGL_TRY(reg->stager.h2d(d_symx_chunks_general.p, hdr_ord[1].data(), hdr_ord[1].size() * sizeof(SymxChunk), st));
-    OGL_TRY(reg->stager.h2d(d_symx_mask.p, L.mask.data(), L.mask.size(), st));
-    OGL_TRY(reg->stager.h2d(d_symx_map.p, L.map.data(), L.map.size() * sizeof(int32_t), st));
-    if (!L.ex_rowptr.empty())
-        OGL_TRY(reg->stager.h2d(d_symx_ex_rowptr.p, L.ex_rowptr.data(), L.ex_rowptr.size() * sizeof(int32_t), st));
-    if (nex) {
-        OGL_TRY(reg->stager.h2d(d_symx_ex_cols.p, L.ex_cols.data(), nex * sizeof(int32_t), st));
-        OGL_TRY(reg->stager.h2d(d_symx_ex_map.p, L.ex_map.data(), nex * sizeof(int32_t), st));
-        OGL_TRY(reg->stager.h2d(d_symx_ex_lrow.p, L.ex_lrow.data(), nex * sizeof(int32_t), st));
-    }
-    props["symxGeneralChunks"] = (double)general_chunks;
-    symx_state = 1;
-    symx_fast = L.all_fast;
-    symx_values_stale = true;
-    // bytes one SpMV reads of this layout: planes, masks, headers, explicit entries (value + column + row) and their
-    // row pointers
-    symx_bytes = 8.0 * (double)(L.map.size() - 2) + (double)(L.mask.size() - 16) + 96.0 * (double)L.chunks.size() +
-                 16.0 * (double)nex + 4.0 * (double)L.ex_rowptr.size();
-    props["sellMatrixBytes"] = symx_bytes;
-    props["sellReadSlots"] = (double)(L.map.size() - 2);
-    props["sellAllocatedSlots"] = (double)(L.map.size() - 2);
-    props["sellChunksDelta16"] = 0.0;
-    props["sellChunksCol32"] = 0.0;
-    props["sellSpilledEntries"] = 0.0;
-    props["symxPlanarEntries"] = (double)L.planar;
-    props["symxExplicitEntries"] = (double)nex;
-    return OGL_OK;
-}
-
-// Once per sparsity pattern; d_sym_map refreshes the planes from the permuted CSR values on the device.
-int ogl_solver::build_sym(const SymLayout &L)
-{
-    hipStream_t st = reg->stream;
-    OGL_TRY(d_sym_mask.alloc(L.mask.size(), st));
-    OGL_TRY(d_sym_map.alloc(L.map.size(), st));
-    OGL_TRY(d_sym_planes.alloc(L.map.size(), st));
-    OGL_TRY(reg->stager.h2d(d_sym_mask.p, L.mask.data(), L.mask.size(), st));
-    OGL_TRY(reg->stager.h2d(d_sym_map.p, L.map.data(), L.map.size() * sizeof(int32_t), st));
-    return finish_sym(L.nd, L.d);
-}
-
-// the part of the half-storage set-up that does not depend on where mask and map were built
-int ogl_solver::finish_sym(int nd, const int32_t *d)
-{
-    hipStream_t st = reg->stream;
-    sym_nd = nd;
-    for (int j = 0; j < 4; ++j) sym_d[j] = j < nd ? d[j] : 0;
-    std::vector<int32_t> order;
-    band_block_order(pat.n_rows, d[nd - 1], order);
-    d_sym_order.release();
-    if (!order.empty()) {
-        OGL_TRY(d_sym_order.alloc(order.size(), st));
-        OGL_TRY(reg->stager.h2d(d_sym_order.p, order.data(), order.size() * sizeof(int32_t), st));
-    }
-    sym_state = 1;
-    sym_values_stale = true;
-    // bytes one SpMV reads of this layout (bench.py's moved-bytes model): planes + masks
-    props["sellMatrixBytes"] = 8.0 * (double)(d_sym_map.n - 2) + (double)(d_sym_mask.n - 16);
-    props["sellReadSlots"] = (double)(d_sym_map.n - 2);
-    props["sellAllocatedSlots"] = (double)(d_sym_map.n - 2);
-    props["sellChunksDelta16"] = 0.0;
-    props["sellChunksCol32"] = 0.0;
-    props["sellSpilledEntries"] = 0.0;
-    return OGL_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -941,23 +622,11 @@ int ogl_solver::build_sym_on_device(const HostPattern &np, SymDistances *sd_out,
     const int64_t nc = n_chunks(N);
     const double upper_entries = (double)N + (double)np.upper_nnz;  // diagonal + one entry per face
     if ((double)nd * (double)nc * CHUNK_ROWS > SYM_MAX_PADDING * upper_entries + 8.0 * CHUNK_ROWS) return OGL_OK;
-    const size_t mask_len = (size_t)nc * CHUNK_ROWS + 16, map_len = (size_t)nc * nd * CHUNK_ROWS + 2;
-    OGL_TRY(d_sym_mask.alloc(mask_len, st));
-    OGL_TRY(d_sym_map.alloc(map_len, st));
-    OGL_TRY(d_sym_planes.alloc(map_len, st));
-    OGL_HIP_CHECK(hipMemsetAsync(d_sym_mask.p, 0, mask_len, st));
-    OGL_HIP_CHECK(hipMemsetAsync(d_sym_map.p, 0xFF, map_len * sizeof(int32_t), st));
     SymDistances sd{};
     sd.nd = nd;
     for (int j = 0; j < nd; ++j) sd.d[j] = dist[j];
-    OGL_HIP_CHECK(hipMemsetAsync(work.p + SYM_TABLE, 0, SYM_FLAGS * sizeof(int32_t), st));
-    launch_sym_fill(st, N, d_row_ptrs.p, d_cols.p, sd, d_sym_mask.p, d_sym_map.p, work.p + SYM_TABLE);
-    OGL_HIP_CHECK(hipMemcpyAsync(got, work.p + SYM_TABLE, SYM_FLAGS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    OGL_HIP_CHECK(hipStreamSynchronize(st));
-    OGL_HIP_CHECK(hipGetLastError());
-    if (got[SYM_FLAG_TOO_MANY]) return OGL_OK;
+    OGL_TRY(sym_dev.fill_on_device(N, d_row_ptrs.p, d_cols.p, sd, work.p + SYM_TABLE, st, done));
     *sd_out = sd;
-    *done = true;
     return OGL_OK;
 }
 
@@ -987,124 +656,23 @@ int ogl_solver::csr_band(int64_t *band)
     return OGL_OK;
 }
 
-int SellDev::build(ogl_label n_rows, const ogl_label *row_ptrs, const ogl_label *cols, Stager &stager,
-                   hipStream_t st, bool sort_windows)
-{
-    ready = false;
-    sorted = false;
-    rmap.release();
-    SellLayout L;
-    if (n_rows == 0) return OGL_OK;
-    if (!sort_windows) {
-        if (!build_sell_layout(n_rows, row_ptrs, cols, L, /*allow_spill*/ false)) return OGL_OK;
-    } else {
-        // The rows of every wavefront's window (SELL_WAVE_ROWS rows) longest first, in a copy of the pattern that only
-        // this layout sees: what choose_numbering does for the system matrix through the numbering itself is done here
-        // with a slot order of the layout's own, undone by the kernel (DevSell::rmap) -- W in the CALLER's triangle on a
-        // renumbered copy has rows of 1 .. 7 entries next to each other and does not qualify otherwise.
-        const int64_t nc = n_chunks(n_rows);
-        std::vector<ogl_label> order((size_t)nc * CHUNK_ROWS);
-        for (size_t i = 0; i < order.size(); ++i) order[i] = (ogl_label)i;
-        auto len = [&](ogl_label r) { return row_ptrs[r + 1] - row_ptrs[r]; };
-        bool moved = false;
-        for (ogl_label k0 = 0; k0 < n_rows; k0 += SELL_WAVE_ROWS) {
-            const auto b = order.begin() + k0, e = order.begin() + std::min<int64_t>(n_rows, (int64_t)k0 + SELL_WAVE_ROWS);
-            std::stable_sort(b, e, [&](ogl_label x, ogl_label y) { return len(x) > len(y); });
-            for (auto it = b; it != e && !moved; ++it) moved = *it != k0 + (ogl_label)(it - b);
-        }
-        if (!moved) return OGL_OK;
-        std::vector<ogl_label> prp((size_t)n_rows + 1, 0), pc((size_t)row_ptrs[n_rows]), at((size_t)row_ptrs[n_rows]);
-        for (ogl_label sr = 0; sr < n_rows; ++sr) prp[(size_t)sr + 1] = prp[(size_t)sr] + len(order[(size_t)sr]);
-        for (ogl_label sr = 0; sr < n_rows; ++sr) {
-            const ogl_label r = order[(size_t)sr];
-            for (ogl_label k = row_ptrs[r], q = prp[(size_t)sr]; k < row_ptrs[r + 1]; ++k, ++q) {
-                pc[(size_t)q] = cols[k];
-                at[(size_t)q] = k;
-            }
-        }
-        if (!build_sell_layout(n_rows, prp.data(), pc.data(), L, /*allow_spill*/ false)) return OGL_OK;
-        for (auto &m : L.map)
-            if (m >= 0) m = at[(size_t)m];  // (values are gathered from the CSR values of the pattern itself)
-        std::vector<uint16_t> rm(order.size());
-        for (size_t i = 0; i < order.size(); ++i) rm[i] = (uint16_t)(order[i] - (ogl_label)(i / CHUNK_ROWS * CHUNK_ROWS));
-        OGL_TRY(rmap.alloc(rm.size(), st));
-        OGL_TRY(stager.h2d(rmap.p, rm.data(), rm.size() * sizeof(uint16_t), st));
-        sorted = true;
-    }
-    OGL_TRY(chunks.alloc(L.chunks.size(), st));
-    OGL_TRY(dict.alloc(L.dict.size(), st));
-    OGL_TRY(codes.alloc(L.codes.size(), st));
-    OGL_TRY(map.alloc(L.map.size(), st));
-    OGL_TRY(vals.alloc(L.map.size(), st));
-    OGL_TRY(stager.h2d(chunks.p, L.chunks.data(), L.chunks.size() * sizeof(SellChunk), st));
-    OGL_TRY(stager.h2d(dict.p, L.dict.data(), L.dict.size() * sizeof(int32_t), st));
-    OGL_TRY(stager.h2d(codes.p, L.codes.data(), L.codes.size(), st));
-    OGL_TRY(stager.h2d(map.p, L.map.data(), L.map.size() * sizeof(int32_t), st));
-    slots = L.n_slots;
-    read_slots = L.read_slots;
-    ready = true;
-    return OGL_OK;
-}
-
-// Once per sparsity pattern: derive the compressed layout on the host; sell_map (like ell_map)
-// refreshes the values from the permuted CSR values on the device.
+// Once per sparsity pattern: the compressed layout of the system matrix, derived on the host (or taken from
+// choose_numbering); sell_dev.map refreshes the values from the permuted CSR values on the device.
 int ogl_solver::build_sell(SellLayout *pre, bool pre_qualifies)
 {
-    hipStream_t st = reg->stream;
     SellLayout own;
-    SellLayout &L = pre ? *pre : own;
-    n_spill = n_spill_rows = 0;
-    if (!pre) OGL_TRY(download_local_pattern(pat));
-    const bool ok = pre ? pre_qualifies
-                        : (pat.n_rows > 0 &&
-                           build_sell_layout(pat.n_rows, pat.row_ptrs.data(), pat.cols.data(), own));
-    if (pat.n_rows == 0 || !ok) {
-        sell_state = -1;
-        return OGL_OK;
+    if (!pre) {
+        OGL_TRY(download_local_pattern(pat));
+        pre_qualifies = pat.n_rows > 0 && build_sell_layout(pat.n_rows, pat.row_ptrs.data(), pat.cols.data(), own);
+        pre = &own;
     }
-    OGL_TRY(d_sell_chunks.alloc(L.chunks.size(), st));
-    OGL_TRY(d_sell_dict.alloc(L.dict.size(), st));
-    OGL_TRY(d_sell_codes.alloc(L.codes.size(), st));
-    OGL_TRY(d_sell_map.alloc(L.map.size(), st));
-    OGL_TRY(d_sell_vals.alloc(L.map.size(), st));
-    OGL_TRY(reg->stager.h2d(d_sell_chunks.p, L.chunks.data(), L.chunks.size() * sizeof(SellChunk), st));
-    OGL_TRY(reg->stager.h2d(d_sell_dict.p, L.dict.data(), L.dict.size() * sizeof(int32_t), st));
-    OGL_TRY(reg->stager.h2d(d_sell_codes.p, L.codes.data(), L.codes.size(), st));
-    OGL_TRY(reg->stager.h2d(d_sell_map.p, L.map.data(), L.map.size() * sizeof(int32_t), st));
-    // spill: tails of the rows longer than their chunk's cap (row-sorted), added by a second pass
-    n_spill_rows = (int32_t)L.spill_rows.size();
-    n_spill = (int32_t)L.spill_cols.size();
-    if (n_spill) {
-        OGL_TRY(d_spill_rows.alloc(L.spill_rows.size(), st));
-        OGL_TRY(d_spill_ptrs.alloc(L.spill_ptrs.size(), st));
-        OGL_TRY(d_spill_cols.alloc(L.spill_cols.size(), st));
-        OGL_TRY(d_spill_map.alloc(L.spill_map.size() + NNZ_PAD, st));
-        OGL_TRY(d_spill_vals.alloc(L.spill_cols.size() + NNZ_PAD, st));
-        OGL_TRY(d_spill_chunks.alloc(L.spill_chunk_ptr.size(), st));
-        OGL_TRY(reg->stager.h2d(d_spill_rows.p, L.spill_rows.data(), L.spill_rows.size() * sizeof(int32_t), st));
-        OGL_TRY(reg->stager.h2d(d_spill_ptrs.p, L.spill_ptrs.data(), L.spill_ptrs.size() * sizeof(int32_t), st));
-        OGL_TRY(reg->stager.h2d(d_spill_cols.p, L.spill_cols.data(), L.spill_cols.size() * sizeof(int32_t), st));
-        OGL_TRY(reg->stager.h2d(d_spill_map.p, L.spill_map.data(), L.spill_map.size() * sizeof(int32_t), st));
-        OGL_TRY(reg->stager.h2d(d_spill_chunks.p, L.spill_chunk_ptr.data(), L.spill_chunk_ptr.size() * sizeof(int32_t), st));
-    }
-    props["sellSpilledEntries"] = (double)n_spill;
-    sell_slots = L.n_slots;
-    sell_state = 1;
-    sell_irregular = L.n_delta16 + L.n_col32 > 0;
-    // a banded pattern (1-byte codes throughout: a structured mesh): the largest offset any chunk's table holds = the
-    // band the workgroup order below is built for
-    sell_band_rows = 0;
-    if (!sell_irregular)
-        for (int32_t d : L.dict)
-            if (d != SELL_PAD_OFFSET) sell_band_rows = std::max<int64_t>(sell_band_rows, std::abs((int64_t)d));
-    sell_tuned = 0;
-    // bytes one SpMV reads of this layout (bench.py's moved-bytes model): the value planes and codes
-    // up to every wavefront's own width (planes beyond it are allocated, not read), headers, tables
-    const double read_frac = L.n_slots ? (double)L.read_slots / (double)L.n_slots : 1.0;
-    props["sellMatrixBytes"] = 8.0 * (double)L.read_slots + read_frac * (double)(L.codes.size() - 16) +
-                               (double)(L.chunks.size() * sizeof(SellChunk)) + 4.0 * (double)L.dict.size() +
-                               16.0 * (double)L.spill_cols.size();  // spilled entries: value + column + their share of row data
-    sell_bytes = props["sellMatrixBytes"];
+    sell_dev.tried = true;
+    sell_dev.ready = false;
+    if (pat.n_rows == 0 || !pre_qualifies) return OGL_OK;
+    const SellLayout &L = *pre;
+    OGL_TRY(sell_dev.upload(L, reg->stager, reg->stream));
+    props["sellSpilledEntries"] = (double)sell_dev.n_spill;
+    props["sellMatrixBytes"] = sell_dev.matrix_bytes;
     props["sellReadSlots"] = (double)L.read_slots;
     props["sellAllocatedSlots"] = (double)L.n_slots;
     props["sellChunksDelta16"] = (double)L.n_delta16;
@@ -1154,11 +722,42 @@ int ogl_solver::download_rows(double *dst, const double *src)
 }
 
 
-// Which kernel runs the in-loop SpMV of a pattern with irregular chunks: measured, once per pattern.  Both
-// read the same matrix and give the same bits (y and the fused dot partials), so this is a speed choice
-// only and ranks are free to differ.  Work vectors p (input, zeroed: the time does not depend on the
-// values) and q (output) are free between solves.
-int ogl_solver::tune_spmv_layout()
+// Values of a layout are gathered from d_vals once per coefficient upload, when the layout is about to be timed or used.
+void ogl_solver::refresh_values(SpmvLayout l)
+{
+    auto fresh = [&](auto &L) {
+        if (L.ready && L.epoch != vals_epoch) {
+            L.refresh(d_vals.p, reg->stream);
+            L.epoch = vals_epoch;
+        }
+    };
+    switch (l) {
+    case SpmvLayout::Ell: fresh(ell_dev); break;
+    case SpmvLayout::Sell: fresh(sell_dev); break;
+    case SpmvLayout::Sym: fresh(sym_dev); break;
+    case SpmvLayout::Symx: fresh(symx_dev); break;
+    default: break;  // (the CSR-stream kernel reads d_vals itself)
+    }
+}
+
+void ogl_solver::release_layout(SpmvLayout l)
+{
+    switch (l) {
+    case SpmvLayout::Csr21: s21_dev.release(); break;
+    case SpmvLayout::Ell: ell_dev.release(); break;
+    case SpmvLayout::Sell: sell_dev.release(); break;
+    case SpmvLayout::Sym: sym_dev.release(); break;
+    case SpmvLayout::Symx: symx_dev.release(); break;
+    default: break;
+    }
+}
+
+// Which kernel runs the in-loop SpMV, measured once per pattern where that is a question: the candidates read the same
+// matrix and give the same bits (y and the fused dot partials), so this is a speed choice only and ranks are free to
+// differ.  Each candidate's best of TIMED launches after WARM ones, the candidates interleaved within each round; ties go
+// to the later candidate, a `pin` among them wins whatever the timing says; the losers are released.  Work vectors p
+// (input, zeroed: the time does not depend on the values) and q (output) are free between solves.
+int ogl_solver::tune_spmv_layouts(const std::vector<SpmvLayout> &cand, const SpmvLayout *pin, SpmvLayout *winner)
 {
     hipStream_t st = reg->stream;
     EventPair ev;
@@ -1168,59 +767,98 @@ int ogl_solver::tune_spmv_layout()
     SpmvDots dots;
     dots.with = d_p.p;
     dots.part = d_part0.p;
+    for (SpmvLayout c : cand) refresh_values(c);
     constexpr int WARM = 2, TIMED = 5;
-    // [0] CSR-stream, [1] compressed chunked ELL, [2] CSR-stream with packed columns
-    const bool have[3] = {true, sell_state == 1 && !sell_values_stale, s21_state == 1};
-    float best[3] = {1e30f, 1e30f, 1e30f};
+    std::vector<float> best(cand.size(), 1e30f);
     for (int round = 0; round < WARM + TIMED; ++round)
-        for (int which = 0; which < 3; ++which) {
-            if (!have[which]) continue;
+        for (size_t i = 0; i < cand.size(); ++i) {
             OGL_HIP_CHECK(hipEventRecord(ev[0], st));
-            if (which == 1) {
-                launch_spmv_sell(st, sell(), SPMV_PLAIN, d_p.p, nullptr, d_q.p, dots, nullptr);
-            } else {
-                s21_use = which == 2;
-                launch_spmv(st, csr(), SPMV_PLAIN, d_p.p, nullptr, d_q.p, dots, nullptr);
-            }
+            spmv_on(cand[i], SPMV_PLAIN, d_p.p, nullptr, d_q.p, dots, nullptr);
             OGL_HIP_CHECK(hipEventRecord(ev[1], st));
             OGL_HIP_CHECK(hipEventSynchronize(ev[1]));
             float ms = 0;
             OGL_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            if (round >= WARM) best[which] = std::min(best[which], ms);
+            if (round >= WARM) best[i] = std::min(best[i], ms);
         }
     OGL_HIP_CHECK(hipGetLastError());
-    int winner = 0;
-    for (int which = 1; which < 3; ++which)
-        if (have[which] && best[which] <= best[winner]) winner = which;
-    // (property spmvForceLayout 0 | 1 | 2: CSR-stream | compressed | packed columns whatever the timing says -- how the
-    //  parity tests reach a layout on a pattern where another one wins)
-    const int forced = (int)prop("spmvForceLayout", -1.0);
-    if (forced >= 0 && forced < 3 && have[forced]) winner = forced;
-    layout_tuned = true;
-    sell_tuned = winner == 1 ? 1 : -1;
-    s21_use = winner == 2;
-    props["spmvTunedCsrUs"] = 1e3 * best[0];
-    if (have[1]) props["spmvTunedSellUs"] = 1e3 * best[1];
-    if (have[2]) props["spmvTunedCsr21Us"] = 1e3 * best[2];
+    size_t w = 0;
+    for (size_t i = 1; i < cand.size(); ++i)
+        if (best[i] <= best[w]) w = i;
+    for (size_t i = 0; i < cand.size(); ++i) {
+        if (pin && cand[i] == *pin) w = i;
+        static const char *const name[] = {"Csr", "Csr21", "Ell", "Sell", "Sym", "Symx"};
+        props[std::string("spmvTuned") + name[(int)cand[i]] + "Us"] = 1e3 * best[i];
+    }
     OGL_HIP_CHECK(hipStreamSynchronize(st));
-    if (have[1] && sell_tuned < 0) {  // the compressed copy is of no use for this pattern: no refreshes, no memory
-        for (auto *b : {&d_sell_dict, &d_sell_map, &d_spill_rows, &d_spill_ptrs, &d_spill_cols, &d_spill_map,
-                        &d_spill_chunks})
-            b->release();
-        d_sell_chunks.release();
-        d_sell_codes.release();
-        d_sell_vals.release();
-        d_spill_vals.release();
-        n_spill = n_spill_rows = 0;
-        sell_state = -1;
+    for (size_t i = 0; i < cand.size(); ++i)
+        if (i != w) release_layout(cand[i]);  // (no refreshes, no memory for a layout of no use to this pattern)
+    *winner = cand[w];
+    return OGL_OK;
+}
+
+// The layout of the in-loop SpMV, once this call's layouts are built and timed: Ell when that is the format; else, with
+// compress_indices, the first that is ready of the half storage, its per-chunk variant, the compressed copy and the packed
+// columns (the timing has released the losers); else the CSR arrays.  Refreshes it, sets the workgroup order, and
+// writes every property that describes it.
+int ogl_solver::select_spmv_layout()
+{
+    using L = SpmvLayout;
+    L l = L::Csr;
+    if (cfg.matrix_format == OGL_FORMAT_ELL) l = L::Ell;
+    else if (!cfg.compress_indices) l = L::Csr;
+    else if (sym_dev.ready) l = L::Sym;
+    else if (symx_dev.ready) l = L::Symx;
+    else if (sell_dev.ready) l = L::Sell;
+    else if (s21_dev.ready) l = L::Csr21;
+    refresh_values(l);
+    spmv_layout = l;
+    {   // Band-aware workgroup order of the compressed / CSR-stream kernels (the half-storage kernels take theirs from
+        // their own distances): the chunks of rows r and r +- band run on one XCD, so a strip of x is fetched into one L2
+        // instead of three.  Full storage of the 216^3 box, STREAM instantiation: 128.2 -> 124.6 us (0.718 -> 0.739 of
+        // peak); the plain CSR-stream kernel takes the same time either way (195.7 / 195.8 us) but fetches 14 % less over the
+        // fabric (1.19 -> 1.02 x the model's bytes, profiles/r06_pmc_nocompress_summary.json), so it gets the order too.
+        // Property spmvBandRows: the band in rows, 0 = off, -1 (default) = the largest offset of a banded pattern (the
+        // compressed layout's tables; for the CSR arrays the distance table of the half-storage set-up, csr_band()).
+        int64_t band = (int64_t)prop("spmvBandRows", -1.0);
+        if (band < 0) {
+            band = 0;
+            if (l == L::Sell) band = sell_dev.band_rows;
+            // (single rank: the order has not been run next to the halo waits of a multi-rank SpMV on the CSR arrays)
+            if ((l == L::Csr || l == L::Csr21) && pat.n_rows >= SPMV_TUNE_MIN_ROWS && !reg->comm->multi())
+                OGL_TRY(csr_band(&band));
+        }
+        if (band != band_order_rows) {
+            d_band_order.release();
+            band_order_rows = band;
+            std::vector<int32_t> order;
+            if (band > 0) band_block_order(pat.n_rows, band, order);
+            if (!order.empty()) {
+                OGL_TRY(d_band_order.alloc(order.size(), reg->stream));
+                OGL_TRY(reg->stager.h2d(d_band_order.p, order.data(), order.size() * sizeof(int32_t), reg->stream));
+            }
+            drop_cg_graph();
+        }
     }
-    if (have[2] && !s21_use) {
-        d_s21_chunks.release();
-        d_s21_codes.release();
-        d_s21_far_idx.release();
-        d_s21_far_col.release();
-        s21_state = -1;
+    // which layout the in-loop SpMV runs on (SpmvLayout) and which instantiation of its kernel (what a profiler lists;
+    // bench.py looks up exactly that one)
+    props["spmvLayout"] = l == L::Csr ? 0.0 : l == L::Ell ? 1.0 : l == L::Csr21 ? 3.0 : 2.0;
+    bool stream = false, fast = false;
+    switch (l) {
+    case L::Ell: stream = ell().stream; break;
+    case L::Sym: {
+        const DevSym S = sym();
+        stream = S.stream;
+        fast = S.nd >= 2 && S.d[1] == 1;
+        for (int j = 2; j < S.nd; ++j) fast = fast && (S.d[j] % 2 == 0);
+        props["spmvSymPlanes"] = (double)S.nd;
+        break;
     }
+    case L::Symx: stream = symx().stream, fast = symx().fast; break;
+    case L::Sell: stream = sell().stream; break;
+    default: stream = csr().stream;
+    }
+    props["spmvStream"] = stream ? 1.0 : 0.0;
+    props["spmvSymFast"] = fast ? 1.0 : 0.0;
     return OGL_OK;
 }
 
@@ -1373,10 +1011,8 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
                                     h_nl_vals.size() * sizeof(double), st));
         }
         matrix_set = true;
-        ell_values_stale = true;
-        sell_values_stale = true;
-        sym_values_stale = true;
-        symx_values_stale = true;
+        ++vals_epoch;  // (every derived layout is stale: the SpMV reads the CSR arrays until select_spmv_layout)
+        spmv_layout = SpmvLayout::Csr;
         return OGL_OK;
     };
     // Has the addressing changed?  Counts first (free); then the hash of every face and interface cell,
@@ -1428,6 +1064,10 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
         have_pattern = false;
         matrix_set = false;
         drop_cg_graph();
+        spmv_layout = SpmvLayout::Csr;
+        ell_dev.ready = sym_dev.ready = symx_dev.ready = sell_dev.ready = sell_dev.tried = false;
+        s21_dev.release();
+        s21_dev.tried = layout_tuned = false;
         HostPattern np;
         // Where the pattern is built: on the device from the face addressing (setup_kernels.hip), unless the
         // environment / property says otherwise or the addressing is not conforming; host_matrix.cpp then
@@ -1520,17 +1160,6 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
         static std::atomic<uint64_t> pattern_counter{0};  // registries may live on different threads
         pat_id = ++pattern_counter;
         matrix_set = false;
-        ell_ready = false;
-        sell_state = 0;
-        sym_state = 0;
-        s21_state = 0;
-        s21_use = false;
-        symx_state = 0;
-        layout_tuned = false;
-        d_s21_chunks.release();
-        d_s21_codes.release();
-        d_s21_far_idx.release();
-        d_s21_far_col.release();
         d_band_order.release();  // (the band-aware workgroup order belongs to the pattern it was built for)
         band_order_rows = 0;
         x_resident = b_resident = false;
@@ -1641,13 +1270,13 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
         props["symmetricHalf"] = 0.0;
         bool sym_ok = false;
         if (sym_on_device) {
-            OGL_TRY(finish_sym(sym_dist.nd, sym_dist.d));
+            OGL_TRY(sym_dev.finish(sym_dist.nd, sym_dist.d, pat.n_rows, reg->stager, st, props));
             sym_ok = true;
         } else if (!sym_tried && prop("symmetricHalfWhole_enable", 1.0) != 0.0 && try_sym && pat.symmetric &&
                    pat.local_iface_nnz == 0 && !pat.renumbered()) {
             SymLayout symL;
             if (build_sym_layout(pat.n_rows, pat.row_ptrs.data(), pat.cols.data(), symL)) {
-                OGL_TRY(build_sym(symL));
+                OGL_TRY(sym_dev.build(symL, pat.n_rows, reg->stager, st, props));
                 sym_ok = true;
             }
         }
@@ -1655,156 +1284,72 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
         if (!sym_ok && try_sym && pat.symmetric && pat.local_iface_nnz == 0 && !pat.renumbered() &&
             prop("symmetricHalfPerChunk_enable", 1.0) != 0.0) {
             // banded only locally (multi-block mesh, refinement shell): per-chunk distances + explicit exceptions
-            OGL_TRY(build_symx());
-            if (symx_state == 1) {
+            OGL_TRY(download_local_pattern(pat));
+            OGL_TRY(symx_dev.build(pat, reg->stager, st, props));
+            if (symx_dev.ready) {
                 sym_ok = true;
                 props["symmetricHalfPerChunk"] = 1.0;
             }
         }
-        if (symx_state != 1) {
-            symx_state = -1;
-            for (auto *b : {&d_symx_map, &d_symx_ex_rowptr, &d_symx_ex_cols, &d_symx_ex_map, &d_symx_ex_lrow}) b->release();
-            d_symx_chunks.release();
-            d_symx_chunks_general.release();
-            d_symx_mask.release();
-            d_symx_planes.release();
-            d_symx_ex_vals.release();
-        }
-        symx_tune_pending = false;
+        if (!symx_dev.ready) symx_dev.release();
         if (sym_ok) {
             props["symmetricHalf"] = 1.0;
             // (per-chunk half storage of a system that is not launch-bound: timed once against the compressed full
             //  storage the numbering policy has laid out on the way, after the first values are in)
-            symx_tune_pending = symx_state == 1 && cfg.compress_indices == 1 && pat.n_rows >= SPMV_TUNE_MIN_ROWS;
-            if (symx_tune_pending) {
-                if (pre_built)
-                    OGL_TRY(build_sell(&pre_sell, rep.sell_used));
-                else
-                    OGL_TRY(build_sell());
-                symx_tune_pending = sell_state == 1;  // (nothing to time against when the compressed copy does not qualify)
-                props["sellMatrixBytes"] = symx_bytes;
+            if (symx_dev.ready && cfg.compress_indices == 1 && pat.n_rows >= SPMV_TUNE_MIN_ROWS) {
+                OGL_TRY(pre_built ? build_sell(&pre_sell, rep.sell_used) : build_sell());
+                props["sellMatrixBytes"] = symx_dev.matrix_bytes;
             }
-            if (!symx_tune_pending) {
-                sell_state = -1;
-                d_sell_chunks.release();
-                d_sell_codes.release();
-                d_sell_vals.release();
-                d_sell_map.release();
-                d_sell_dict.release();
-            }
+            if (!sell_dev.ready) sell_dev.release();  // (nothing to time against when the compressed copy does not qualify)
         }
-        if (sym_state != 1) {
-            sym_state = -1;
-            d_sym_mask.release();
-            d_sym_map.release();
-            d_sym_planes.release();
-        }
-        if (sym_state != 1 && symx_state != 1 && pre_built && try_sell) OGL_TRY(build_sell(&pre_sell, rep.sell_used));
+        if (!sym_dev.ready) sym_dev.release();
+        if (!sym_dev.ready && !symx_dev.ready && pre_built && try_sell) OGL_TRY(build_sell(&pre_sell, rep.sell_used));
         OGL_TRY(setup_peer_halo());  // collective when the peer mesh is up (every rank, every pattern)
     }
 
     if (!coefficients_done && (!matrix_set || cfg.update_sys_matrix || cfg.regenerate)) OGL_TRY(upload_coefficients());
     if (cfg.matrix_format == OGL_FORMAT_ELL) {
-        if (!ell_ready) OGL_TRY(build_ell());
-        if (ell_values_stale) {
-            launch_gather_coeffs_masked(st, (int64_t)ell_width * ell_stride, d_ell_map.p, d_vals.p,
-                                        d_ell_vals.p);
-            ell_values_stale = false;
+        if (!ell_dev.ready) {
+            OGL_TRY(download_local_pattern(pat));
+            OGL_TRY(ell_dev.build(pat, reg->stager, st));
         }
-    } else if (cfg.compress_indices && sym_state == 1) {
-        if (sym_values_stale) {
-            launch_gather_coeffs_masked(st, (int64_t)d_sym_map.n - 2, d_sym_map.p, d_vals.p, d_sym_planes.p);
-            sym_values_stale = false;
-        }
-    } else if (cfg.compress_indices && symx_state == 1) {
-        if (symx_values_stale) {
-            launch_gather_coeffs_masked(st, (int64_t)d_symx_map.n - 2, d_symx_map.p, d_vals.p, d_symx_planes.p);
-            const int32_t nex = (int32_t)(d_symx_ex_cols.n - NNZ_PAD);
-            if (nex > 0) launch_gather_coeffs(st, nex, d_symx_ex_map.p, d_vals.p, d_symx_ex_vals.p);
-            symx_values_stale = false;
-        }
-        if (symx_tune_pending) {
-            symx_tune_pending = false;
-            if (sell_state == 1) {
-                launch_gather_sell(st, (int32_t)d_sell_chunks.n, d_sell_chunks.p, d_sell_map.p, d_vals.p, d_sell_vals.p);
-                if (n_spill) launch_gather_coeffs(st, n_spill, d_spill_map.p, d_vals.p, d_spill_vals.p);
-                sell_values_stale = false;
-                OGL_TRY(tune_symx());
+    } else if (cfg.compress_indices && !sym_dev.ready && symx_dev.ready) {
+        // per-chunk half storage built next to the compressed full storage (above): the faster one stays
+        if (sell_dev.ready) {
+            SpmvLayout win;
+            OGL_TRY(tune_spmv_layouts({SpmvLayout::Sell, SpmvLayout::Symx}, nullptr, &win));
+            if (win == SpmvLayout::Symx) {
+                props["sellMatrixBytes"] = symx_dev.matrix_bytes;
+            } else {
+                props["symmetricHalf"] = 0.0;
+                props["symmetricHalfPerChunk"] = 0.0;
+                props["sellMatrixBytes"] = sell_dev.matrix_bytes;
             }
         }
-    } else if (cfg.compress_indices) {
-        if (sell_state == 0) OGL_TRY(build_sell());
-        if (sell_state == 1 && sell_values_stale) {
-            launch_gather_sell(st, (int32_t)d_sell_chunks.n, d_sell_chunks.p, d_sell_map.p, d_vals.p,
-                               d_sell_vals.p);
-            if (n_spill) launch_gather_coeffs(st, n_spill, d_spill_map.p, d_vals.p, d_spill_vals.p);
-            sell_values_stale = false;
-        }
+    } else if (cfg.compress_indices && !sym_dev.ready) {
+        if (!sell_dev.tried) OGL_TRY(build_sell());
         // irregular patterns (16 / 32-bit codes in the chunked ELL, or one that does not qualify for it at all: a
         // polyhedral mesh) of a size where the SpMV is not launch-bound: the CSR-stream kernel gets its packed
-        // columns, and the candidates are timed once per pattern
+        // columns, and the candidates are timed once per pattern (compress_indices 2: no timing, the first that is
+        // ready of the compressed copy and the packed columns runs)
         const bool big = pat.n_rows >= SPMV_TUNE_MIN_ROWS;
-        const bool irregular_sell = sell_state == 1 && sell_irregular;
-        if (big && s21_state == 0 && (irregular_sell || sell_state == -1)) OGL_TRY(build_stream21());
-        if (big && cfg.compress_indices == 1 && !layout_tuned && (irregular_sell || s21_state == 1))
-            OGL_TRY(tune_spmv_layout());
-        if (cfg.compress_indices == 2) s21_use = s21_state == 1 && sell_state != 1;  // force: no timing
-    }
-    // which layout the in-loop SpMV runs on: 0 CSR-stream, 1 ELL, 2 index-compressed chunked ELL
-    // (2 also for the half storage of a symmetric matrix: property symmetricHalf tells them apart)
-    // 3: CSR-stream with packed columns
-    {   // Band-aware workgroup order of the compressed / CSR-stream kernels (the half-storage kernels take theirs from
-        // their own distances): the chunks of rows r and r +- band run on one XCD, so a strip of x is fetched into one L2
-        // instead of three.  Full storage of the 216^3 box, STREAM instantiation: 128.2 -> 124.6 us (0.718 -> 0.739 of
-        // peak); the plain CSR-stream kernel takes the same time either way (195.7 / 195.8 us) but fetches 14 % less over the
-        // fabric (1.19 -> 1.02 x the model's bytes, profiles/r06_pmc_nocompress_summary.json), so it gets the order too.
-        // Property spmvBandRows: the band in rows, 0 = off, -1 (default) = the largest offset of a banded pattern (the
-        // compressed layout's tables; for the CSR arrays the distance table of the half-storage set-up, csr_band()).
-        int64_t band = (int64_t)prop("spmvBandRows", -1.0);
-        if (band < 0) {
-            const bool by_sell = cfg.matrix_format != OGL_FORMAT_ELL && use_sell() && !use_sym() && !use_symx();
-            const bool by_csr = cfg.matrix_format != OGL_FORMAT_ELL && !use_sell() && !use_sym() && !use_symx();
-            band = 0;
-            if (by_sell) band = sell_band_rows;
-            // (single rank: the order has not been run next to the halo waits of a multi-rank SpMV on the CSR arrays)
-            if (by_csr && pat.n_rows >= SPMV_TUNE_MIN_ROWS && !reg->comm->multi()) OGL_TRY(csr_band(&band));
-        }
-        if (band != band_order_rows) {
-            d_band_order.release();
-            band_order_rows = band;
-            std::vector<int32_t> order;
-            if (band > 0) band_block_order(pat.n_rows, band, order);
-            if (!order.empty()) {
-                OGL_TRY(d_band_order.alloc(order.size(), st));
-                OGL_TRY(reg->stager.h2d(d_band_order.p, order.data(), order.size() * sizeof(int32_t), st));
-            }
-            drop_cg_graph();
+        const bool irregular_sell = sell_dev.ready && sell_dev.irregular;
+        if (big && !s21_dev.tried && (irregular_sell || !sell_dev.ready))
+            OGL_TRY(s21_dev.build(pat.n_rows, pat.local_nnz, d_row_ptrs.p, d_cols.p, st, props));
+        if (big && cfg.compress_indices == 1 && !layout_tuned && (irregular_sell || s21_dev.ready)) {
+            std::vector<SpmvLayout> cand{SpmvLayout::Csr};
+            if (sell_dev.ready) cand.push_back(SpmvLayout::Sell);
+            if (s21_dev.ready) cand.push_back(SpmvLayout::Csr21);
+            // (property spmvForceLayout 0 | 1 | 2: CSR-stream | compressed | packed columns whatever the timing says -- how
+            //  the parity tests reach a layout on a pattern where another one wins)
+            const int forced = (int)prop("spmvForceLayout", -1.0);
+            const SpmvLayout by_force[3] = {SpmvLayout::Csr, SpmvLayout::Sell, SpmvLayout::Csr21};
+            SpmvLayout win;
+            OGL_TRY(tune_spmv_layouts(cand, forced >= 0 && forced < 3 ? &by_force[forced] : nullptr, &win));
+            layout_tuned = true;
         }
     }
-    const bool on_csr = cfg.matrix_format != OGL_FORMAT_ELL && !use_sell() && !use_sym() && !use_symx();
-    if (!cfg.compress_indices) s21_use = false;
-    props["spmvLayout"] = cfg.matrix_format == OGL_FORMAT_ELL ? 1.0 : (!on_csr ? 2.0 : (s21_use && s21_state == 1 ? 3.0 : 0.0));
-    {   // ... and which instantiation of its kernel (what a profiler lists; bench.py looks up exactly that one)
-        bool stream = false, fast = false;
-        if (cfg.matrix_format == OGL_FORMAT_ELL) {
-            stream = ell().stream;
-        } else if (use_sym()) {
-            const DevSym S = sym();
-            stream = S.stream;
-            fast = S.nd >= 2 && S.d[1] == 1;
-            for (int j = 2; j < S.nd; ++j) fast = fast && (S.d[j] % 2 == 0);
-            props["spmvSymPlanes"] = (double)S.nd;
-        } else if (use_symx()) {
-            stream = symx().stream;
-            fast = symx().fast;
-        } else if (use_sell()) {
-            stream = sell().stream;
-        } else {
-            stream = csr().stream;
-        }
-        props["spmvStream"] = stream ? 1.0 : 0.0;
-        props["spmvSymFast"] = fast ? 1.0 : 0.0;
-    }
+    OGL_TRY(select_spmv_layout());
     OGL_HIP_CHECK(hipStreamSynchronize(st));
     OGL_HIP_CHECK(hipGetLastError());
     // what this call's addressing arrays were (ogl_solver_set_matrix_like: a sibling built on the same arrays right after

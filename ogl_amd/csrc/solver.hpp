@@ -15,124 +15,9 @@
 #include "host_matrix.hpp"
 #include "kernels.hpp"
 #include "setup_kernels.hpp"
+#include "spmv_layouts.hpp"
 
 namespace ogl {
-
-#define OGL_HIP_CHECK(expr)                                                                \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return ::ogl::fail(OGL_ERR_HIP, "%s failed: %s (%s:%d)", #expr,                \
-                               hipGetErrorString(e_), __FILE__, __LINE__);                 \
-    } while (0)
-#define OGL_TRY(expr)                 \
-    do {                              \
-        int rc_ = (expr);             \
-        if (rc_ != OGL_OK) return rc_; \
-    } while (0)
-
-// PersistentArray<T> (DevicePersistent/Array/Array.H:91-229): a named device array that lives as
-// long as its registry.
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;    // elements in use
-    size_t cap = 0;  // elements allocated (>= n)
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    void release()
-    {
-        ledger::dev_free(p);
-        p = nullptr;
-        n = cap = 0;
-    }
-    void swap(DevBuf &o)
-    {
-        std::swap(p, o.p);
-        std::swap(n, o.n);
-        std::swap(cap, o.cap);
-    }
-    // `count` elements, zero-filled when the size changes.  A block that is large enough (and not more than four times
-    // too large) is kept: sizes that go back and forth from solve to solve -- the registry-wide preconditioner store
-    // taking scalar Jacobi, blocks, W in turn (Preconditioner.H:357: one key for all fields), a residual history whose
-    // length follows the adaptive evaluation frequency -- then cost no hipFree / hipMalloc pair per time step, and the
-    // same pointers come back (a captured hipGraph stays valid).
-    int alloc(size_t count, hipStream_t st)
-    {
-        if (count == n && p) return OGL_OK;
-        if (p && count > 0 && count <= cap && count >= cap / 4) {
-            OGL_HIP_CHECK(hipMemsetAsync(p, 0, count * sizeof(T), st));
-            n = count;
-            return OGL_OK;
-        }
-        release();
-        if (count == 0) return OGL_OK;
-        OGL_HIP_CHECK(ledger::dev_malloc(reinterpret_cast<void **>(&p), count * sizeof(T)));
-        OGL_HIP_CHECK(hipMemsetAsync(p, 0, count * sizeof(T), st));
-        n = cap = count;
-        return OGL_OK;
-    }
-};
-
-// Pinned double-buffered staging for pageable host arrays (K10/K12: "pinned async copies").
-// Pageable host arrays <-> device through a ring of pinned buffers.  The copy between the caller's array and a
-// pinned buffer is what limits a coefficient refresh (one core moves 10-25 GB/s, the PCIe 5 x16 link takes 55): it
-// is split over a small pool of persistent helper threads (OGL_STAGE_THREADS, default 8) that store past the
-// caches (non-temporal: the DMA engine -- or, coming down, the caller -- reads the data from DRAM anyway, and a
-// plain store would first read the destination line), while the DMA of the previous buffers is in flight.
-class CopyPool;
-class Stager {
-public:
-    static constexpr int NBUF = 4;
-    ~Stager();
-    int init(size_t chunk_bytes);
-    int h2d(void *dst, const void *src, size_t bytes, hipStream_t st);
-    int d2h(void *dst, const void *src, size_t bytes, hipStream_t st);  // returns after completion
-
-private:
-    void *pin_[NBUF] = {};
-    hipEvent_t ev_[NBUF] = {};
-    bool busy_[NBUF] = {};
-    size_t chunk_ = 0;
-    int next_ = 0;
-    CopyPool *pool_ = nullptr;
-};
-
-class Stager;
-
-// Device copy of an index-compressed chunked ELL (SellChunk, common.hpp) of some CSR matrix whose
-// values live elsewhere: pattern once (`build`), values by `refresh` from the CSR value array.
-struct SellDev {
-    DevBuf<SellChunk> chunks;
-    DevBuf<int32_t> dict, map;
-    DevBuf<uint8_t> codes;
-    DevBuf<double> vals;
-    int64_t slots = 0, read_slots = 0;
-    bool ready = false;  // false: the pattern does not qualify (or build was never called)
-    // rows of each wavefront's window stored longest first (sort_windows; the kernel undoes it: DevSell::rmap)
-    DevBuf<uint16_t> rmap;
-    bool sorted = false;
-    int build(ogl_label n_rows, const ogl_label *row_ptrs, const ogl_label *cols, Stager &stager,
-              hipStream_t st, bool sort_windows = false);
-    void refresh(const double *csr_vals, hipStream_t st)
-    {
-        if (ready) launch_gather_sell(st, (int32_t)chunks.n, chunks.p, map.p, csr_vals, vals.p);
-    }
-    DevSell view(int32_t n_rows, bool stream) const
-    {
-        DevSell S;
-        S.n_rows = n_rows;
-        S.chunks = chunks.p;
-        S.dict = dict.p;
-        S.codes = codes.p;
-        S.vals = vals.p;
-        S.rmap = sorted ? rmap.p : nullptr;
-        S.stream = stream;
-        return S;
-    }
-};
 
 // A generated preconditioner ("Cached_preconditinoner" holds one of these, Preconditioner.H:357)
 struct PrecondData {
@@ -252,26 +137,41 @@ struct ogl_solver {
     ogl::DevBuf<double> d_vals;                              // "<field>_matrix" values
     ogl::DevBuf<double> d_source;                            // unsorted [upper|lower|diag|iface]
     ogl::DevBuf<int32_t> d_diag_pos;  // position of each row's first diagonal entry (scalar Jacobi)
-    // matrixFormat Ell: slot-major copy of the local matrix (built on demand, refreshed from vals)
-    ogl::DevBuf<int32_t> d_ell_cols, d_ell_map;
-    ogl::DevBuf<double> d_ell_vals;
-    int32_t ell_width = 0;
-    int64_t ell_stride = 0;
-    bool ell_ready = false, ell_values_stale = true;
-    int build_ell();
-    // half storage of a symmetric matrix on a banded pattern (SymLayout, host_matrix.hpp): what the Coo/Csr
-    // formats run on when cfg.compress_indices and cfg.symmetric_half are set, the lduMatrix has no `lower`
-    // and no same-rank (cyclic) interface, the device copy keeps the caller's numbering and the pattern
-    // qualifies.  Takes the place of the compressed copy below (sym_state as sell_state).
-    ogl::DevBuf<uint8_t> d_sym_mask;
-    ogl::DevBuf<int32_t> d_sym_map, d_sym_order;  // (order: band_block_order, may be empty)
+    // ---- derived device layouts the SpMV may run on instead of the CSR arrays (spmv_layouts.hpp) ----
+    // matrixFormat Ell; the half storage of a symmetric matrix (compress_indices + symmetric_half), else its per-chunk
+    // variant; the index-compressed chunked ELL (compress_indices); the packed columns of the CSR-stream kernel.  Each is
+    // built once per pattern and refreshed from d_vals when it is about to be timed or used (refresh_values).
+    ogl::EllDev ell_dev;
+    ogl::SymDev sym_dev;
+    ogl::SymxDev symx_dev;
+    ogl::SellDev sell_dev;
+    ogl::Stream21Dev s21_dev;
+    uint64_t vals_epoch = 0;  // bumped by every coefficient upload into d_vals
+    void refresh_values(ogl::SpmvLayout l);
+    void release_layout(ogl::SpmvLayout l);
+    // The layout the in-loop SpMV runs on: chosen by select_spmv_layout at the end of every set_matrix (after any
+    // timing), Csr from a coefficient or pattern change until then.  The views below are those the kernels get.
+    ogl::SpmvLayout spmv_layout = ogl::SpmvLayout::Csr;
+    int select_spmv_layout();
+    // Patterns with irregular chunks (16-bit delta / 32-bit column codes: unstructured meshes) are timed on the
+    // candidate kernels once per pattern (tune_spmv_layouts): the compressed layout moves fewer bytes, but its slot-major
+    // gather -- one entry of 64 different rows per instruction -- only pays where neighbouring rows have neighbouring
+    // columns; on a polyhedral mesh the CSR-stream kernel's row-major gather wins.  The results are bit-identical.
+    bool layout_tuned = false;  // ... done for this pattern
+    int tune_spmv_layouts(const std::vector<ogl::SpmvLayout> &cand, const ogl::SpmvLayout *pin, ogl::SpmvLayout *winner);
+    // `pre` != nullptr: the layout choose_numbering already derived for this pattern (`pre_qualifies`: usable)
+    int build_sell(ogl::SellLayout *pre = nullptr, bool pre_qualifies = false);
     bool band_order_off = std::getenv("OGL_NO_BAND_ORDER") != nullptr;  // (A/B switch for measurements)
-    ogl::DevBuf<double> d_sym_planes;
-    int32_t sym_nd = 0, sym_d[4] = {0, 0, 0, 0};
-    int sym_state = 0;
-    bool sym_values_stale = true;
-    int build_sym(const ogl::SymLayout &L);
-    int finish_sym(int nd, const int32_t *d);
+    bool streamed(double bytes) const { return bytes + turn_extra_bytes() > stream_above_bytes(); }
+    ogl::DevEll ell() const { return ell_dev.view(pat.n_rows, streamed(ell_dev.bytes(pat.n_rows))); }
+    ogl::DevSym sym() const { return sym_dev.view(pat.n_rows, streamed(sym_dev.bytes(pat.n_rows)), !band_order_off); }
+    ogl::DevSymx symx() const { return symx_dev.view(pat.n_rows, streamed(symx_dev.bytes(pat.n_rows)), xcd_group()); }
+    ogl::DevSell sell() const
+    {
+        return sell_dev.view(pat.n_rows, streamed(sell_dev.bytes(pat.n_rows)), xcd_group(), &d_band_order);
+    }
+    ogl::DevCsr csr(bool packed) const;  // packed: with the packed columns (SpmvLayout::Csr21)
+    ogl::DevCsr csr() const { return csr(spmv_layout == ogl::SpmvLayout::Csr21); }
     // device set-up (setup_kernels.hip)
     int build_pattern_on_device(const ogl_ldu_view &ldu, ogl::HostPattern &np, bool *built);
     int build_sym_on_device(const ogl::HostPattern &np, ogl::SymDistances *sd_out, bool *done);
@@ -285,70 +185,6 @@ struct ogl_solver {
     int curve_on_device(ogl_label n, const double *centres, std::vector<ogl_label> &new_id);
     int curve_far_on_device(const ogl::HostPattern &hp, const std::vector<ogl_label> &new_id,
                             const std::vector<ogl_label> &old_of, int64_t &far);
-    ogl::DevSym sym() const;
-    bool use_sym() const
-    {
-        return cfg.matrix_format != OGL_FORMAT_ELL && cfg.compress_indices && sym_state == 1 && !sym_values_stale;
-    }
-    // half storage with per-chunk distances and explicit exceptions (SymxLayout, host_matrix.hpp): symmetric
-    // matrices that are banded only locally (multi-block meshes, refinement shells) -- tried when the global
-    // half storage above does not qualify, before the compressed full-storage copy below
-    ogl::DevBuf<ogl::SymxChunk> d_symx_chunks, d_symx_chunks_general;  // (dispatch order: lean kernel's list, general one's)
-    ogl::DevBuf<uint8_t> d_symx_mask;
-    ogl::DevBuf<int32_t> d_symx_map, d_symx_ex_rowptr, d_symx_ex_cols, d_symx_ex_map, d_symx_ex_lrow;
-    ogl::DevBuf<double> d_symx_planes, d_symx_ex_vals;
-    int symx_state = 0;  // 0 not tried, 1 built, -1 not worth it
-    bool symx_fast = false;
-    // built next to the compressed full-storage copy and still to be timed against it (once per pattern, systems
-    // of >= SPMV_TUNE_MIN_ROWS rows with compress_indices 1): the faster one stays
-    bool symx_tune_pending = false;
-    int tune_symx();
-    bool symx_values_stale = true;
-    double symx_bytes = 0.0;
-    int build_symx();
-    ogl::DevSymx symx() const;
-    bool use_symx() const
-    {
-        return cfg.matrix_format != OGL_FORMAT_ELL && cfg.compress_indices && symx_state == 1 && !symx_values_stale;
-    }
-    // index-compressed chunked ELL copy (SellChunk, common.hpp): what the Coo/Csr formats run on when
-    // cfg.compress_indices is set and the pattern qualifies.  sell_state: 0 = not tried for this
-    // pattern, 1 = built, -1 = pattern does not qualify (CSR-stream kernel runs)
-    ogl::DevBuf<ogl::SellChunk> d_sell_chunks;
-    ogl::DevBuf<int32_t> d_sell_dict, d_sell_map;
-    ogl::DevBuf<uint8_t> d_sell_codes;
-    ogl::DevBuf<double> d_sell_vals;
-    int64_t sell_slots = 0;
-    double sell_bytes = 0.0;  // bytes one SpMV reads of the compressed copy (decides the cache policy of its loads)
-    int sell_state = 0;
-    // spill of the compressed copy: tails of the rows longer than their chunk's cap (SellLayout)
-    ogl::DevBuf<int32_t> d_spill_rows, d_spill_ptrs, d_spill_cols, d_spill_map, d_spill_chunks;
-    ogl::DevBuf<double> d_spill_vals;
-    int32_t n_spill_rows = 0, n_spill = 0;   // (d_spill_chunks holds the per-chunk ranges of d_spill_rows)
-    bool sell_values_stale = true;
-    // Patterns with irregular chunks (16-bit delta / 32-bit column codes: unstructured meshes) are timed on
-    // both kernels once per pattern (tune_spmv_layout): the compressed layout moves fewer bytes, but its
-    // slot-major gather -- one entry of 64 different rows per instruction -- only pays where neighbouring
-    // rows have neighbouring columns; on a polyhedral mesh the CSR-stream kernel's row-major gather wins.
-    // sell_tuned: 0 = not measured, 1 = compressed layout is faster (or cfg.compress_indices == 2: forced),
-    // -1 = the CSR-stream kernel is.  The results are bit-identical either way.
-    bool sell_irregular = false;
-    int sell_tuned = 0;
-    bool layout_tuned = false;  // tune_spmv_layout has run for this pattern
-    int tune_spmv_layout();
-    // packed columns for the CSR-stream kernel (Stream21Chunk, common.hpp): built for irregular patterns of
-    // >= SPMV_TUNE_MIN_ROWS rows when compress_indices is set; s21_use: the in-loop CSR-stream SpMV reads them
-    // (it won the one-off timing, or compress_indices = force and the chunked ELL does not qualify)
-    ogl::DevBuf<ogl::Stream21Chunk> d_s21_chunks;
-    ogl::DevBuf<uint4> d_s21_codes;
-    ogl::DevBuf<int32_t> d_s21_far_idx, d_s21_far_col;  // the chunks' entries outside their 2^21-column windows
-    int s21_state = 0;  // 0 not tried for this pattern, 1 built, -1 a chunk's columns span 2^21 or more
-    bool s21_use = false;
-    int build_stream21();
-    // `pre` != nullptr: the layout choose_numbering already derived for this pattern
-    // (`pre_qualifies` tells whether it is usable)
-    int build_sell(ogl::SellLayout *pre = nullptr, bool pre_qualifies = false);
-    ogl::DevSell sell() const;
     // renumbering (config `renumber`): pat.new_id on the device + a staging vector, so that host
     // vectors cross the boundary in the caller's cell order
     ogl::DevBuf<int32_t> d_new_id, d_old_of;
@@ -385,12 +221,6 @@ struct ogl_solver {
     int setup_peer_halo();
     ogl::PeerHalo peer_halo_args(uint32_t seq) const;
     double *peer_recv(uint32_t seq) const;
-    bool use_sell() const
-    {
-        return cfg.matrix_format != OGL_FORMAT_ELL && cfg.compress_indices && sell_state == 1 &&
-               !sell_values_stale && sell_tuned >= 0;
-    }
-    ogl::DevEll ell() const;
     // halo part
     std::vector<int32_t> boundary_rows, boundary_ptrs;
     ogl::DevBuf<int32_t> d_boundary_rows, d_boundary_ptrs, d_nl_cols, d_send_idxs;
@@ -410,7 +240,7 @@ struct ogl_solver {
     ogl::DevBuf<double> d_V, d_gm;                      // GMRES: Krylov bases, dense state
     ogl::DevBuf<double> d_isai_tmp;                     // ISAI(spd): W r before W^T
     ogl::DevBuf<double> d_part0, d_part1, d_part2;  // (part2: beta partials of the fused-finaliser turn)
-    int64_t band_order_rows = 0, sell_band_rows = 0;
+    int64_t band_order_rows = 0;
     bool source_diag_valid = false;  // d_source's diagonal segment is the diagonal of d_vals (set by the coefficient update)
     int64_t csr_band_rows = 0;   // band of the device CSR arrays (csr_band), valid for pattern csr_band_pat
     uint64_t csr_band_pat = 0;
@@ -453,6 +283,9 @@ struct ogl_solver {
     // prepacked: the kernel that produced x has put the halo values already (begin_halo_put)
     int dist_spmv(int mode, const double *x, const double *b, double *y, const ogl::SpmvDots &dots,
                   const ogl::DevScalars *gate, bool prepacked = false);
+    // the local SpMV on layout l (the in-loop one: spmv_layout)
+    void spmv_on(ogl::SpmvLayout l, int mode, const double *x, const double *b, double *y, const ogl::SpmvDots &dots,
+                 const ogl::DevScalars *gate, const ogl::HaloFused &hf = ogl::HaloFused{});
     int finalize(int phase, ogl::FinArgs &a);
     int run_cg(ogl_perf *perf);
     int run_bicgstab(ogl_perf *perf);
@@ -476,7 +309,6 @@ struct ogl_solver {
     int turn_bicg_folded(KrylovRun &k, int enq, int pe);
     int turn_bicg(KrylovRun &k, int enq, int pe);
     int time_spmv(int repeats, double *avg_ms);
-    ogl::DevCsr csr() const;
     ogl::DevHalo halo() const;
     double prop(const std::string &key, double dflt) const;
     // ogl_solver_set_matrix_like: the solver whose device copy of upper / lower this set_matrix may take (only during

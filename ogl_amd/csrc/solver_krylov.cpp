@@ -49,6 +49,20 @@ HaloFused ogl_solver::halo_fused_args(const PeerHalo &ph) const
     return hf;
 }
 
+void ogl_solver::spmv_on(SpmvLayout l, int mode, const double *x, const double *b, double *y, const SpmvDots &dots,
+                         const DevScalars *gate, const HaloFused &hf)
+{
+    hipStream_t st = reg->stream;
+    switch (l) {
+    case SpmvLayout::Ell: launch_spmv_ell(st, ell(), mode, x, b, y, dots, gate, hf); break;
+    case SpmvLayout::Sym: launch_spmv_sym(st, sym(), mode, x, b, y, dots, gate, hf); break;
+    case SpmvLayout::Symx: launch_spmv_symx(st, symx(), mode, x, b, y, dots, gate, hf); break;
+    case SpmvLayout::Sell: launch_spmv_sell(st, sell(), mode, x, b, y, dots, gate, hf); break;
+    case SpmvLayout::Csr:
+    case SpmvLayout::Csr21: launch_spmv(st, csr(l == SpmvLayout::Csr21), mode, x, b, y, dots, gate, hf); break;
+    }
+}
+
 int ogl_solver::dist_spmv(int mode, const double *x, const double *b, double *y,
                           const SpmvDots &dots, const DevScalars *gate, bool prepacked)
 {
@@ -95,16 +109,7 @@ int ogl_solver::dist_spmv(int mode, const double *x, const double *b, double *y,
     // The fused dot partials of the local kernel are final for every chunk without boundary rows;
     // the few chunks that hold boundary rows are redone after "y += A_non_local recv" (same
     // per-chunk tree, so the sums are bit-identical to a dot over the finished y).
-    if (cfg.matrix_format == OGL_FORMAT_ELL && ell_ready && !ell_values_stale)
-        launch_spmv_ell(st, ell(), mode, x, b, y, dots, gate, hf);
-    else if (use_sym())
-        launch_spmv_sym(st, sym(), mode, x, b, y, dots, gate, hf);
-    else if (use_symx())
-        launch_spmv_symx(st, symx(), mode, x, b, y, dots, gate, hf);
-    else if (use_sell())
-        launch_spmv_sell(st, sell(), mode, x, b, y, dots, gate, hf);
-    else
-        launch_spmv(st, csr(), mode, x, b, y, dots, gate, hf);
+    spmv_on(spmv_layout, mode, x, b, y, dots, gate, hf);
     if (safe) {
         launch_halo_wait(st, ph, gate, d_scal.p);
         launch_spmv_non_local(st, halo(), mode, recv, y, gate);
@@ -294,7 +299,7 @@ int ogl_solver::krylov_plan(KrylovRun &k)
     // columns and forms p_new there itself (kernels_spmv_sym.hip, k_cg_turn_sym_big<.., HALO>), so the merged kernel has
     // nothing to put and only waits for a put of the PREVIOUS launch.  Every rank must run the same turn (what the
     // neighbours put differs): agreed below together with the global row count.
-    bool merged = !bicg && !gmres && !generic && nc >= 1 && use_sym() && cfg.matrix_format != OGL_FORMAT_ELL &&
+    bool merged = !bicg && !gmres && !generic && nc >= 1 && spmv_layout == SpmvLayout::Sym &&
                   ((fused && small) ? prop("fusedTurn", 1.0) != 0.0 : prop("fusedTurnBig", sym().stream ? 0.0 : 1.0) != 0.0);
     if (multi)
         merged = merged && peer_halo && prop("haloFused", 1.0) != 0.0 && prop("fusedTurnMulti", 1.0) != 0.0 &&
@@ -865,18 +870,21 @@ int ogl_solver::krylov_loop(KrylovRun &k)
         // slots the turn kernels take, the turn's shape, and the pattern the layouts belong to (a rebuild with the same
         // sizes usually gets the same pointers back: 32x64x32 -> 64x32x32)
         KeyHasher kh;
-        kh(k.n), kh(batch), kh(cfg.matrix_format), kh(use_sell()), kh(use_sym()), kh(use_symx()), kh(symx_fast), kh(s21_use);
+        kh(k.n), kh(batch), kh(cfg.matrix_format), kh(spmv_layout);
         kh(k.fused), kh(k.fused2), kh(k.merged), kh(k.ring.k), kh(k.p0), kh(k.p1), kh(k.z_kept), kh(k.s), kh(k.s2), kh(pat_id);
         for (const void *v : {(const void *)d_p.p, (const void *)d_x.p, (const void *)d_r.p, (const void *)d_q.p,
                               (const void *)precond, (const void *)d_part0.p, (const void *)d_part1.p,
                               (const void *)d_part2.p, (const void *)d_history.p, (const void *)d_z.p, (const void *)d_p2.p})
             kh(v);
         for (int i = 0; i < k.ring.k; ++i) kh((const void *)k.ring.b[i]);
-        visit(kh, csr());
-        visit(kh, ell());
-        if (sell_state == 1) visit(kh, sell());
-        if (use_sym()) visit(kh, sym());
-        if (use_symx()) visit(kh, symx());
+        visit(kh, csr());  // (also what the generation kernels read)
+        switch (spmv_layout) {  // (a captured turn reads the selected layout only)
+        case SpmvLayout::Ell: visit(kh, ell()); break;
+        case SpmvLayout::Sell: visit(kh, sell()); break;
+        case SpmvLayout::Sym: visit(kh, sym()); break;
+        case SpmvLayout::Symx: visit(kh, symx()); break;
+        default: break;  // (Csr, Csr21: csr() above)
+        }
         visit(kh, k.lead);
         const uint64_t key = kh.h;
         if (!cg_graph || key != cg_graph_key) {
