@@ -58,7 +58,10 @@ typedef enum {
     OGL_PRECOND_NONE = 0, /* Preconditioner.H:342 */
     OGL_PRECOND_BJ = 1,   /* Preconditioner.H:91-105 (Schwarz-wrapped Jacobi on the local matrix) */
     OGL_PRECOND_ISAI = 2, /* Preconditioner.H:225-241  isai_type::spd     (M^-1 = W^T W)           */
-    OGL_PRECOND_GISAI = 3 /* Preconditioner.H:242-258  isai_type::general (M^-1 = W)               */
+    OGL_PRECOND_GISAI = 3, /* Preconditioner.H:242-258  isai_type::general (M^-1 = W)              */
+    OGL_PRECOND_IC = 4,    /* Preconditioner.H:106-126  factorization::Ic, A ~ L L^T, exact solves   */
+    OGL_PRECOND_ILU = 5,   /* Preconditioner.H:106-126  factorization::Ilu, A ~ L U, exact solves    */
+    OGL_PRECOND_IRILU = 6  /* Preconditioner.H:147-178  the ILU factors, 5 Richardson sweeps each    */
 } ogl_precond_kind;
 
 typedef enum { OGL_FORMAT_COO = 0, OGL_FORMAT_CSR = 1, OGL_FORMAT_ELL = 2 } ogl_matrix_format;
@@ -332,6 +335,9 @@ int ogl_solver_download_solution(ogl_solver *s, ogl_scalar *psi);
 
 /* y = A x through the in-loop SpMV kernel (dist_mtx::apply, StoppingCriterion.C:29). */
 int ogl_solver_spmv(ogl_solver *s, const ogl_scalar *x, ogl_scalar *y);
+/* z = M^-1 r with the preconditioner of the last solve (r, z: host vectors of n_rows in the caller's cell order; the
+ * local operator only).  OGL_ERR_STATE before the first solve. */
+int ogl_solver_apply_preconditioner(ogl_solver *s, const ogl_scalar *r, ogl_scalar *z);
 /* `repeats` back-to-back in-loop SpMVs (fused with the p.q dot, as in the CG loop) on resident
  * vectors, timed with HIP events on the solver's stream; avg_ms = per launch. */
 int ogl_solver_time_spmv(ogl_solver *s, int32_t repeats, double *avg_ms);

@@ -17,6 +17,7 @@ OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_COMM, ERR_STATE, ERR_UNSUPPORTED, ERR_COMM_SELFTEST = -1, -2, -3, -4, -5, -6, -7
 SOLVER_CG, SOLVER_BICGSTAB, SOLVER_GMRES = 0, 1, 2
 PRECOND_NONE, PRECOND_BJ, PRECOND_ISAI, PRECOND_GISAI = 0, 1, 2, 3
+PRECOND_IC, PRECOND_ILU, PRECOND_IRILU = 4, 5, 6
 FORMAT_COO, FORMAT_CSR, FORMAT_ELL = 0, 1, 2
 RENUMBER_OFF, RENUMBER_ON, RENUMBER_AUTO = 0, 1, 2
 IFACE_PROCESSOR, IFACE_CYCLIC = 0, 1
@@ -86,7 +87,7 @@ EXPORTED_SYMBOLS = [
     "ogl_solver_solve", "ogl_solver_history", "ogl_solver_export_system",
     "ogl_solver_get_property",
     "ogl_solver_set_property", "ogl_solver_apply_resident", "ogl_solver_upload_solution",
-    "ogl_solver_upload_rhs", "ogl_solver_download_solution", "ogl_solver_spmv",
+    "ogl_solver_upload_rhs", "ogl_solver_download_solution", "ogl_solver_spmv", "ogl_solver_apply_preconditioner",
     "ogl_solver_time_spmv", "ogl_solver_reduce", "ogl_reduction_chunk_rows",
     "ogl_solver_matrix_dims", "ogl_solver_get_local_matrix", "ogl_solver_get_non_local_matrix",
     "ogl_solver_get_comm_pattern", "ogl_host_init_local_sparsity", "ogl_host_symmetric_update",
@@ -354,6 +355,13 @@ class Solver:
         y = np.zeros_like(x)
         _check(lib().ogl_solver_spmv(self._h, _ps(x), _ps(y)))
         return y
+
+    def apply_preconditioner(self, r):
+        """z = M^-1 r with the preconditioner of the last solve (caller's cell order, local operator)."""
+        r = _s(r)
+        z = np.zeros_like(r)
+        _check(lib().ogl_solver_apply_preconditioner(self._h, _ps(r), _ps(z)))
+        return z
 
     def time_spmv(self, repeats):
         ms = C.c_double()

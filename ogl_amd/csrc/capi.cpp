@@ -406,6 +406,30 @@ extern "C" int ogl_solver_spmv(ogl_solver *s, const ogl_scalar *x, ogl_scalar *y
     OGL_GUARD_END
 }
 
+extern "C" int ogl_solver_apply_preconditioner(ogl_solver *s, const ogl_scalar *r, ogl_scalar *z)
+{
+    OGL_GUARD_BEGIN
+    if (!s || !r || !z) return fail(OGL_ERR_INVALID, "NULL argument");
+    if (!s->matrix_set || !s->precond_ready) return fail(OGL_ERR_STATE, "apply_preconditioner before the first solve");
+    // the registry-wide store may have been regenerated by another field, or this solver's pattern changed, since
+    if (!s->precond_current())
+        return fail(OGL_ERR_STATE, "apply_preconditioner: the preconditioner of the last solve is gone (another field "
+                                   "regenerated the shared one, or the pattern changed): solve again first");
+    OGL_HIP_CHECK(hipSetDevice(s->reg->device));
+    OGL_TRY(s->upload_rows(s->d_w.p, r));
+    if (!s->precond_data)  // (preconditioner none: the identity)
+        OGL_HIP_CHECK(hipMemcpyAsync(s->d_q.p, s->d_w.p, (size_t)s->pat.n_rows * sizeof(double), hipMemcpyDeviceToDevice,
+                                     s->reg->stream));
+    else if (s->precond_data->kind == 1)
+        launch_mul(s->reg->stream, s->pat.n_rows, s->d_q.p, s->d_w.p, s->precond_data->values.p, nullptr);
+    else
+        s->apply_preconditioner(s->d_w.p, s->d_q.p, nullptr);
+    OGL_TRY(s->download_rows(z, s->d_q.p));
+    OGL_HIP_CHECK(hipGetLastError());
+    return OGL_OK;
+    OGL_GUARD_END
+}
+
 extern "C" int ogl_solver_time_spmv(ogl_solver *s, int32_t repeats, double *avg_ms)
 {
     OGL_GUARD_BEGIN

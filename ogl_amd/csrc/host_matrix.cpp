@@ -1578,6 +1578,143 @@ bool build_symx_layout(ogl_label n_rows, const ogl_label *row_ptrs, const ogl_la
     return true;
 }
 
+// ---------------------------------------------------------------------------------------
+// Incomplete factorisations: structure in the caller's numbering
+// ---------------------------------------------------------------------------------------
+namespace {
+// rows sorted by level (stable: ascending row within a level)
+void level_schedule(const std::vector<int32_t> &level, std::vector<int32_t> &ptr, std::vector<int32_t> &rows)
+{
+    int32_t n_levels = 0;
+    for (int32_t l : level) n_levels = std::max(n_levels, l + 1);
+    ptr.assign((size_t)n_levels + 1, 0);
+    for (int32_t l : level) ++ptr[(size_t)l + 1];
+    for (int32_t l = 0; l < n_levels; ++l) ptr[(size_t)l + 1] += ptr[(size_t)l];
+    std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
+    rows.resize(level.size());
+    for (size_t i = 0; i < level.size(); ++i) rows[(size_t)fill[(size_t)level[i]]++] = (int32_t)i;
+}
+}  // namespace
+
+bool build_factor_structure(const HostPattern &p, bool ic, FactorStructure &F, ogl_label &bad_row)
+{
+    const ogl_label N = p.n_rows;
+    const bool rn = p.renumbered();
+    F = FactorStructure{};
+    F.ic = ic;
+    F.row_ptrs.assign((size_t)N + 1, 0);
+    F.diag.assign((size_t)N, -1);
+    F.map_ptr.assign(1, 0);
+    std::vector<std::pair<int32_t, int32_t>> ent;  // (caller column, device CSR position)
+    for (ogl_label i = 0; i < N; ++i) {
+        const ogl_label r = rn ? p.new_id[(size_t)i] : i;
+        ent.clear();
+        for (ogl_label k = p.row_ptrs[(size_t)r]; k < p.row_ptrs[(size_t)r + 1]; ++k) {
+            const ogl_label c = rn ? p.old_of[(size_t)p.cols[(size_t)k]] : p.cols[(size_t)k];
+            if (!ic || c <= i) ent.emplace_back(c, k);
+        }
+        std::stable_sort(ent.begin(), ent.end(),
+                         [](const std::pair<int32_t, int32_t> &a, const std::pair<int32_t, int32_t> &b) { return a.first < b.first; });
+        for (size_t t = 0; t < ent.size(); ++t) {
+            if (t == 0 || ent[t].first != ent[t - 1].first) {
+                if (t > 0) F.map_ptr.push_back((int32_t)F.map.size());
+                if (ent[t].first == i) F.diag[(size_t)i] = (int32_t)F.cols.size();
+                F.cols.push_back(ent[t].first);
+            }
+            F.map.push_back(ent[t].second);
+        }
+        if (!ent.empty()) F.map_ptr.push_back((int32_t)F.map.size());
+        F.row_ptrs[(size_t)i + 1] = (int32_t)F.cols.size();
+        if (F.diag[(size_t)i] < 0) {  // (no diagonal entry: nothing to divide by)
+            bad_row = i;
+            return false;
+        }
+    }
+    const int32_t nf = (int32_t)F.cols.size();
+    // update lists (no searching on the device)
+    F.upd_ptr.assign((size_t)nf + 1, 0);
+    std::vector<int32_t> where((size_t)N, -1), stamp((size_t)N, -1);
+    for (ogl_label i = 0; i < N; ++i) {
+        for (int32_t e = F.row_ptrs[(size_t)i]; e < F.row_ptrs[(size_t)i + 1]; ++e) {
+            where[(size_t)F.cols[(size_t)e]] = e;
+            stamp[(size_t)F.cols[(size_t)e]] = i;
+        }
+        for (int32_t e = F.row_ptrs[(size_t)i]; e < F.row_ptrs[(size_t)i + 1]; ++e) {
+            const int32_t k = F.cols[(size_t)e];
+            if (k < i) {
+                if (ic) {  // common m < k of rows i and k
+                    for (int32_t q = F.row_ptrs[(size_t)k]; q < F.diag[(size_t)k]; ++q) {
+                        const int32_t m = F.cols[(size_t)q];
+                        if (stamp[(size_t)m] == i) {
+                            F.upd_a.push_back(where[(size_t)m]);
+                            F.upd_b.push_back(q);
+                        }
+                    }
+                } else {  // j > k of row k that row i has too
+                    for (int32_t q = F.diag[(size_t)k] + 1; q < F.row_ptrs[(size_t)k + 1]; ++q) {
+                        const int32_t j = F.cols[(size_t)q];
+                        if (stamp[(size_t)j] == i) {
+                            F.upd_a.push_back(where[(size_t)j]);
+                            F.upd_b.push_back(q);
+                        }
+                    }
+                }
+            }
+            F.upd_ptr[(size_t)e + 1] = (int32_t)F.upd_a.size();
+        }
+    }
+    // forward levels over the strictly lower part
+    std::vector<int32_t> level((size_t)N, 0);
+    for (ogl_label i = 0; i < N; ++i) {
+        int32_t l = 0;
+        for (int32_t e = F.row_ptrs[(size_t)i]; e < F.row_ptrs[(size_t)i + 1]; ++e)
+            if (F.cols[(size_t)e] < i) l = std::max(l, level[(size_t)F.cols[(size_t)e]] + 1);
+        level[(size_t)i] = l;
+    }
+    level_schedule(level, F.fwd_ptr, F.fwd_rows);
+    if (ic) {  // L^T: counting transpose, rows sorted by column (the diagonal comes first)
+        F.t_row_ptrs.assign((size_t)N + 1, 0);
+        F.t_cols.resize((size_t)nf);
+        F.t_map.resize((size_t)nf);
+        for (int32_t e = 0; e < nf; ++e) ++F.t_row_ptrs[(size_t)F.cols[(size_t)e] + 1];
+        for (ogl_label r = 0; r < N; ++r) F.t_row_ptrs[(size_t)r + 1] += F.t_row_ptrs[(size_t)r];
+        std::vector<int32_t> fill(F.t_row_ptrs.begin(), F.t_row_ptrs.end() - 1);
+        for (ogl_label r = 0; r < N; ++r)
+            for (int32_t e = F.row_ptrs[(size_t)r]; e < F.row_ptrs[(size_t)r + 1]; ++e) {
+                const int32_t t = fill[(size_t)F.cols[(size_t)e]]++;
+                F.t_cols[(size_t)t] = r;
+                F.t_map[(size_t)t] = e;
+            }
+    }
+    // backward levels over the strictly upper part (U, or L^T for IC), rows descending
+    const std::vector<int32_t> &urp = ic ? F.t_row_ptrs : F.row_ptrs;
+    const std::vector<int32_t> &uc = ic ? F.t_cols : F.cols;
+    for (ogl_label i = N - 1; i >= 0; --i) {
+        int32_t l = 0;
+        for (int32_t e = urp[(size_t)i]; e < urp[(size_t)i + 1]; ++e)
+            if (uc[(size_t)e] > i) l = std::max(l, level[(size_t)uc[(size_t)e]] + 1);
+        level[(size_t)i] = l;
+    }
+    level_schedule(level, F.bwd_ptr, F.bwd_rows);
+    return true;
+}
+
+void factor_segments(const std::vector<int32_t> &level_ptr, int32_t thin_rows, std::vector<int32_t> &seg)
+{
+    seg.clear();
+    const int32_t L = (int32_t)level_ptr.size() - 1;
+    for (int32_t l = 0; l < L;) {
+        const bool thin = level_ptr[(size_t)l + 1] - level_ptr[(size_t)l] <= thin_rows;
+        int32_t e = l + 1;
+        if (thin)
+            while (e < L && level_ptr[(size_t)e + 1] - level_ptr[(size_t)e] <= thin_rows) ++e;
+        seg.push_back(l);
+        seg.push_back(e);
+        seg.push_back(thin ? 1 : 0);
+        l = e;
+    }
+}
+
 }  // namespace ogl
 
 // ---------------------------------------------------------------------------------------

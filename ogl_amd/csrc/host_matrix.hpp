@@ -235,4 +235,30 @@ bool isai_pattern(const HostPattern &p, bool spd, int power, int max_row, std::v
 // HostMatrix.C:180-207: concatenated bouCoeffs of the (non-)processor interfaces, times -1.
 void collect_interface_coeffs(const ogl_ldu_view &ldu, bool local, ogl_scalar *out);
 
+// ---- incomplete factorisations (IC(0) / ILU(0) on the local pattern, preconditioner kinds IC, ILU, IRILU) ----
+// Everything that depends on the pattern only, in the CALLER's numbering (row i = device row p.new_id[i] on a
+// renumbered pattern), built once per pattern; the device fills the values and factors them.
+struct FactorStructure {
+    bool ic = false;
+    // factor CSR: ILU = the pattern of A (strict L, the diagonal, U in one array); IC = tril(A).  Columns ascending,
+    // a column repeated in A (cyclic patches) is one entry.  diag[i] = position of (i, i).
+    std::vector<int32_t> row_ptrs, cols, diag;
+    // value map: factor entry e = sum of the device CSR values map[map_ptr[e] .. map_ptr[e + 1]), in that order
+    std::vector<int32_t> map_ptr, map;
+    // update list of every strictly lower entry e = (i, k), in factorisation order (upd_ptr[e] .. upd_ptr[e + 1]):
+    //   ILU: after l_ik = a_ik / u_kk, a[upd_a] -= l_ik * a[upd_b]   (upd_a = pos(i, j), upd_b = pos(k, j), j > k ascending)
+    //   IC:  s = a_ik; s -= a[upd_a] * a[upd_b] (upd_a = pos(i, m), upd_b = pos(k, m), m < k ascending); l_ik = s / l_kk
+    std::vector<int32_t> upd_ptr, upd_a, upd_b;
+    // IC: L^T by a counting transpose (rows ascending by column, diagonal first); t_map = position in L
+    std::vector<int32_t> t_row_ptrs, t_cols, t_map;
+    // level schedules: forward level(i) = 1 + max level(j), j < i in row i; backward the same over the upper part,
+    // rows descending.  Rows of level l: rows[level_ptr[l] .. level_ptr[l + 1]), ascending.
+    std::vector<int32_t> fwd_ptr, fwd_rows, bwd_ptr, bwd_rows;
+};
+// false: row `bad_row` has no diagonal entry
+bool build_factor_structure(const HostPattern &p, bool ic, FactorStructure &F, ogl_label &bad_row);
+// Runs of consecutive levels of at most `thin_rows` rows each become one single-workgroup segment; every other level is
+// a segment of its own.  seg = (first level, end level, thin) triples.
+void factor_segments(const std::vector<int32_t> &level_ptr, int32_t thin_rows, std::vector<int32_t> &seg);
+
 }  // namespace ogl

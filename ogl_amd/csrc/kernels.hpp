@@ -45,6 +45,10 @@ struct DevScalars {
     unsigned long long halo_wait_ticks, reduce_wait_ticks;
     uint32_t reduce_waits;
     uint32_t launch_seq;  // leader finalisation (LeadBox): tag of the next leader launch's mailbox words
+    // IC / ILU / IRILU: the factor's breakdown word (PrecondData::f_breakdown), copied here after the last kernel of the
+    // solve so that it comes back with the final scalars
+    int32_t factor_breakdown;
+    int32_t pad_;
 };
 
 // GKOCG, three-launch leader turn: K search-direction buffers used in turn (the head of turn j reads b[j % K] and writes
@@ -289,6 +293,50 @@ void launch_isai_generate(hipStream_t st, const DevCsr &A, int spd, const int32_
 void launch_isai_generate_huge(hipStream_t st, const DevCsr &A, int spd, const int32_t *w_row_ptrs,
                                const int32_t *w_cols, double *w_vals, const int32_t *huge_rows,
                                const int64_t *scratch_off, int32_t first, int32_t count, double *scratch);
+
+// Incomplete factorisations (kernels_factor.hip; preconditioners IC, ILU, IRILU).  The factor lives in the caller's
+// numbering (FactorStructure, host_matrix.hpp): one CSR `f` (ILU: strict L, the diagonal, U; IC: L with the diagonal
+// last), diag[i] = position of (i, i).  Level-scheduled kernels take one thread per row of a level; a run of thin levels
+// goes to one workgroup that walks them with a barrier between levels (no waits between workgroups).
+struct DevFactor {
+    int32_t n_rows = 0;
+    int32_t ic = 0;
+    const int32_t *row_ptrs = nullptr, *cols = nullptr, *diag = nullptr;
+    double *vals = nullptr;
+    // update lists per strictly lower entry (FactorStructure::upd_*)
+    const int32_t *upd_ptr = nullptr, *upd_a = nullptr, *upd_b = nullptr;
+    int32_t *breakdown = nullptr;  // atomicMin of the rows with a zero (ILU) / non-positive (IC) pivot
+};
+// one triangle of the factor, row by row: lower: off-diagonal entries [beg[i], end[i]), the diagonal at end[i] (unit:
+// none); upper: the diagonal at beg[i], off-diagonal entries (beg[i], end[i])
+struct DevTri {
+    const int32_t *beg = nullptr, *end = nullptr, *cols = nullptr;
+    const double *vals = nullptr;
+    int32_t upper = 0, unit = 0;
+};
+// f[e] = sum of src[map[map_ptr[e] .. map_ptr[e + 1])] in that order
+void launch_factor_gather(hipStream_t st, int32_t nf, const int32_t *map_ptr, const int32_t *map, const double *src,
+                          double *f);
+// IC(0) / ILU(0) of the rows of levels [l0, l1) (seg: thin = one workgroup walks them)
+// (level_ptr: the same array on the host and on the device)
+void launch_factor_levels(hipStream_t st, const DevFactor &F, const int32_t *level_ptr_host, const int32_t *level_ptr,
+                          const int32_t *level_rows, int32_t l0, int32_t l1, bool thin);
+// x = T^-1 b on the rows of levels [l0, l1); b_perm != nullptr: b_i = b[b_perm[i]].  x may be b (in place).
+void launch_tri_levels(hipStream_t st, const DevTri &T, const int32_t *level_ptr_host, const int32_t *level_ptr,
+                       const int32_t *level_rows, int32_t l0, int32_t l1, bool thin, const double *b, const int32_t *b_perm, double *x,
+                       const DevScalars *gate);
+// IRILU: sweeps per triangle ([UPSTREAM] Ir with BJ(1), 5 iterations, Preconditioner.H:147-178)
+constexpr int IRILU_SWEEPS = 5;
+// one Richardson sweep x_out = x + D^-1 (b - T x) over all rows (inv_d == nullptr: D = I)
+void launch_tri_sweep(hipStream_t st, int32_t n, const DevTri &T, const double *inv_d, const double *b,
+                      const double *x, double *x_out, const DevScalars *gate);
+// inv_d[i] = 1 / f[diag[i]]
+void launch_factor_inv_diag(hipStream_t st, int32_t n, const int32_t *diag, const double *f, double *inv_d);
+// gated permutations (as launch_permute_gather / _scatter)
+void launch_factor_gather_perm(hipStream_t st, int32_t n, const int32_t *new_id, const double *in, double *out,
+                               const DevScalars *gate);
+void launch_factor_scatter_perm(hipStream_t st, int32_t n, const int32_t *new_id, const double *in, double *out,
+                                const DevScalars *gate);
 
 // renumbering (keyword `renumber`): host vectors arrive in the caller's cell order
 //   scatter: out[new_id[i]] = in[i]   (b, x on upload)      gather: out[i] = in[new_id[i]]   (x on copy-back)

@@ -288,6 +288,12 @@ double ogl_solver::turn_extra_bytes() const
     if (cfg.preconditioner == OGL_PRECOND_ISAI) extra += 10.0 * (nnz + N);      // tril(A) twice, ~10 bytes per entry
     if (cfg.preconditioner == OGL_PRECOND_GISAI) extra += 10.0 * nnz;
     if (cfg.preconditioner == OGL_PRECOND_BJ && cfg.max_block_size > 1) extra += 8.0 * cfg.max_block_size * N;
+    if (cfg.preconditioner == OGL_PRECOND_IC) extra += 24.0 * (nnz + N) / 2.0;  // L and L^T, 12 bytes per entry
+    if (cfg.preconditioner == OGL_PRECOND_ILU || cfg.preconditioner == OGL_PRECOND_IRILU) extra += 12.0 * nnz;
+    if (cfg.preconditioner == OGL_PRECOND_IRILU) extra += 16.0 * N;  // the sweeps' two iterates
+    if ((cfg.preconditioner == OGL_PRECOND_IC || cfg.preconditioner == OGL_PRECOND_ILU ||
+         cfg.preconditioner == OGL_PRECOND_IRILU) && pat.renumbered())
+        extra += 8.0 * N;  // the vector in the caller's order
     if (cfg.preconditioner != OGL_PRECOND_NONE && !(cfg.preconditioner == OGL_PRECOND_BJ && cfg.max_block_size == 1))
         extra += 16.0 * N;                                                      // materialised z (and the ISAI temporary)
     if (cfg.solver == OGL_SOLVER_BICGSTAB) extra += 32.0 * N;

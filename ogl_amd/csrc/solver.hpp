@@ -21,7 +21,7 @@ namespace ogl {
 
 // A generated preconditioner ("Cached_preconditinoner" holds one of these, Preconditioner.H:357)
 struct PrecondData {
-    int kind = 0;  // 0 none, 1 scalar Jacobi (inverse diagonal), 2 block Jacobi
+    int kind = 0;  // 0 none, 1 scalar Jacobi (inverse diagonal), 2 block Jacobi, 3 ISAI, 4 GISAI, 5 IC, 6 ILU, 7 IRILU
     size_t n_rows = 0;
     int stride = 0;  // block Jacobi: maxBlockSize
     int32_t n_blocks = 0;
@@ -49,6 +49,16 @@ struct PrecondData {
     std::vector<int32_t> huge_batches;
     int32_t n_huge_rows = 0;
     SellDev w_sell, wt_sell;  // compressed copies the apply runs on when compress_indices is set
+    // incomplete factorisations (kinds 5 IC, 6 ILU, 7 IRILU; FactorStructure, host_matrix.hpp): the factor in the CALLER's
+    // numbering -- self-contained, applied through the applying solver's permutation -- with its value map, update
+    // lists, L^T (IC) and the level schedules
+    DevBuf<int32_t> f_row_ptrs, f_cols, f_diag, f_map_ptr, f_map, f_upd_ptr, f_upd_a, f_upd_b;
+    DevBuf<int32_t> ft_row_ptrs, ft_cols, ft_map, f_fwd_ptr, f_fwd_rows, f_bwd_ptr, f_bwd_rows;
+    DevBuf<double> f_vals, ft_vals, f_inv_d;
+    DevBuf<int32_t> f_breakdown;  // first row with a zero / non-positive pivot (0x7f7f7f7f: none)
+    std::vector<int32_t> f_fwd_ptr_h, f_bwd_ptr_h;
+    int32_t f_nnz = 0;
+    uint64_t serial = 0;  // new value with every generation (an applier checks it still holds what it adopted)
     // the pattern-only part (block pointers / W and W^T patterns) is kept for as long as it was
     // derived from the same sparsity pattern: only the values are regenerated per solve
     uint64_t struct_pat_id = 0;
@@ -67,10 +77,11 @@ struct PrecondData {
     uint64_t gen_pat_id = 0;
     bool gen_device_numbering = false;
     bool caller_order_blocks() const { return kind == 2 && !by_device_row && !gen_device_numbering; }
+    bool factor() const { return kind >= 5; }
     bool foreign_to(uint64_t id, bool renumbered) const
     {
         if (gen_pat_id == id) return false;
-        return gen_device_numbering || (renumbered && !caller_order_blocks());
+        return gen_device_numbering || (renumbered && !caller_order_blocks() && !factor());
     }
 };
 
@@ -239,6 +250,13 @@ struct ogl_solver {
     ogl::DevBuf<double> d_v, d_s, d_t, d_y, d_z, d_rr;  // BiCGStab
     ogl::DevBuf<double> d_V, d_gm;                      // GMRES: Krylov bases, dense state
     ogl::DevBuf<double> d_isai_tmp;                     // ISAI(spd): W r before W^T
+    ogl::DevBuf<double> d_fac_tmp[3];  // IC / ILU / IRILU: vectors in the caller's order, IRILU's iterates
+    bool precond_ready = false;        // a solve has set up precond_data (ogl_solver_apply_preconditioner)
+    uint64_t precond_serial = 0, precond_pat = 0;  // ... the object's serial and this solver's pattern at that time
+    bool precond_current() const;      // precond_data is still what the last solve set up, for this pattern
+    // this solver's launch segments of the factor's level schedules ((first level, end level, thin) triples, property
+    // iluThinRows), formed when the preconditioner is set up for a solve
+    std::vector<int32_t> fac_seg_fwd, fac_seg_bwd;
     ogl::DevBuf<double> d_part0, d_part1, d_part2;  // (part2: beta partials of the fused-finaliser turn)
     int64_t band_order_rows = 0;
     bool source_diag_valid = false;  // d_source's diagonal segment is the diagonal of d_vals (set by the coefficient update)
@@ -276,7 +294,9 @@ struct ogl_solver {
     int ensure_vectors();
     int init_preconditioner();
     int generate_preconditioner(ogl::PrecondData &P);
-    // out = M^-1 in for the block-Jacobi / ISAI / GISAI kinds; dot_part != nullptr: also the per-chunk
+    void apply_factor(const double *in, double *out, const ogl::DevScalars *gate, double *dot_part);
+    int check_factor_breakdown(int32_t word);
+    // out = M^-1 in for the block-Jacobi / ISAI / GISAI / IC / ILU / IRILU kinds; dot_part != nullptr: also the per-chunk
     // partials of sum_i in_i * out_i (CG's rho), out of the same kernel
     void apply_preconditioner(const double *in, double *out, const ogl::DevScalars *gate,
                               double *dot_part = nullptr);

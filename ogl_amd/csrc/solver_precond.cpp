@@ -27,7 +27,79 @@ int ogl_solver::generate_preconditioner(PrecondData &P)
     const bool through_perm = pat.renumbered() && caller_numbering;
     if (P.struct_caller_numbering != caller_numbering) P.struct_pat_id = 0;  // (the switch was flipped: rebuild)
     P.struct_caller_numbering = caller_numbering;
-    if (cfg.preconditioner == OGL_PRECOND_ISAI || cfg.preconditioner == OGL_PRECOND_GISAI) {
+    if (cfg.preconditioner == OGL_PRECOND_IC || cfg.preconditioner == OGL_PRECOND_ILU ||
+        cfg.preconditioner == OGL_PRECOND_IRILU) {
+        // factorization::Ic / Ilu (Preconditioner.H:106-126,147-178) on the local matrix in the caller's numbering.
+        // Pattern-only part on the host (FactorStructure), values gathered and factored on the device level by level.
+        const bool ic = cfg.preconditioner == OGL_PRECOND_IC;
+        const int skind = ic ? 5 : 6;  // (ILU and IRILU share the factor)
+        const char *name = ic ? "IC" : (cfg.preconditioner == OGL_PRECOND_ILU ? "ILU" : "IRILU");
+        if (!P.has_structure(pat_id, skind, 0)) {
+            P.struct_pat_id = 0;
+            OGL_TRY(download_local_pattern(pat));
+            FactorStructure F;
+            ogl_label bad = -1;
+            if (!build_factor_structure(pat, ic, F, bad))
+                return fail(OGL_ERR_INVALID, "preconditioner %s: row %d has no diagonal entry", name, bad);
+            auto up = [&](DevBuf<int32_t> &d, const std::vector<int32_t> &h) -> int {
+                OGL_TRY(d.alloc(std::max<size_t>(1, h.size()), st));
+                if (!h.empty()) OGL_TRY(reg->stager.h2d(d.p, h.data(), h.size() * sizeof(int32_t), st));
+                return OGL_OK;
+            };
+            OGL_TRY(up(P.f_row_ptrs, F.row_ptrs));
+            OGL_TRY(up(P.f_cols, F.cols));
+            OGL_TRY(up(P.f_diag, F.diag));
+            OGL_TRY(up(P.f_map_ptr, F.map_ptr));
+            OGL_TRY(up(P.f_map, F.map));
+            OGL_TRY(up(P.f_upd_ptr, F.upd_ptr));
+            OGL_TRY(up(P.f_upd_a, F.upd_a));
+            OGL_TRY(up(P.f_upd_b, F.upd_b));
+            OGL_TRY(up(P.ft_row_ptrs, F.t_row_ptrs));
+            OGL_TRY(up(P.ft_cols, F.t_cols));
+            OGL_TRY(up(P.ft_map, F.t_map));
+            OGL_TRY(up(P.f_fwd_ptr, F.fwd_ptr));
+            OGL_TRY(up(P.f_fwd_rows, F.fwd_rows));
+            OGL_TRY(up(P.f_bwd_ptr, F.bwd_ptr));
+            OGL_TRY(up(P.f_bwd_rows, F.bwd_rows));
+            P.f_nnz = (int32_t)F.cols.size();
+            OGL_TRY(P.f_vals.alloc(std::max<size_t>(1, F.cols.size()), st));
+            if (ic) OGL_TRY(P.ft_vals.alloc(std::max<size_t>(1, F.cols.size()), st));
+            else P.ft_vals.release();
+            OGL_TRY(P.f_breakdown.alloc(1, st));
+            P.f_fwd_ptr_h = F.fwd_ptr;
+            P.f_bwd_ptr_h = F.bwd_ptr;
+            props["iluUpdates"] = (double)F.upd_a.size();
+            P.struct_pat_id = pat_id;
+            P.struct_kind = skind;
+            P.struct_stride = 0;
+        }
+        // runs of levels of at most iluThinRows rows each: one single-workgroup launch per run
+        std::vector<int32_t> seg;
+        factor_segments(P.f_fwd_ptr_h, (int32_t)prop("iluThinRows", 256.0), seg);
+        OGL_HIP_CHECK(hipMemsetAsync(P.f_breakdown.p, 0x7f, sizeof(int32_t), st));
+        launch_factor_gather(st, P.f_nnz, P.f_map_ptr.p, P.f_map.p, csr().vals, P.f_vals.p);
+        DevFactor F;
+        F.n_rows = pat.n_rows;
+        F.ic = ic ? 1 : 0;
+        F.row_ptrs = P.f_row_ptrs.p;
+        F.cols = P.f_cols.p;
+        F.diag = P.f_diag.p;
+        F.vals = P.f_vals.p;
+        F.upd_ptr = P.f_upd_ptr.p;
+        F.upd_a = P.f_upd_a.p;
+        F.upd_b = P.f_upd_b.p;
+        F.breakdown = P.f_breakdown.p;
+        for (size_t g = 0; g + 2 < seg.size(); g += 3)
+            launch_factor_levels(st, F, P.f_fwd_ptr_h.data(), P.f_fwd_ptr.p, P.f_fwd_rows.p, seg[g], seg[g + 1],
+                                 seg[g + 2] != 0);
+        if (ic) launch_gather_coeffs(st, P.f_nnz, P.ft_map.p, P.f_vals.p, P.ft_vals.p);
+        if (cfg.preconditioner == OGL_PRECOND_IRILU) {
+            OGL_TRY(P.f_inv_d.alloc(n + 2, st));
+            launch_factor_inv_diag(st, (int32_t)n, P.f_diag.p, P.f_vals.p, P.f_inv_d.p);
+        }
+        P.kind = ic ? 5 : (cfg.preconditioner == OGL_PRECOND_ILU ? 6 : 7);
+        P.stride = 0;
+    } else if (cfg.preconditioner == OGL_PRECOND_ISAI || cfg.preconditioner == OGL_PRECOND_GISAI) {
         // Isai<spd|general> with sparsity_power 1 and skip_sorting (Preconditioner.H:225-258).
         // Pattern of W on the host (tril(A) for spd, A for general), its transpose + map for spd,
         // values on the device (one dense solve per row).
@@ -214,16 +286,117 @@ int ogl_solver::generate_preconditioner(PrecondData &P)
         P.stride = cfg.max_block_size;
     }
     P.n_rows = n;
+    static uint64_t serials = 0;
+    P.serial = ++serials;
     P.gen_pat_id = pat_id;
-    P.gen_device_numbering =
-        pat.renumbered() && !(P.kind == 2 && P.through_perm && !P.by_device_row);  // (see PrecondData::foreign_to)
+    P.gen_device_numbering = pat.renumbered() && !(P.kind == 2 && P.through_perm && !P.by_device_row) &&
+                             !P.factor();  // (see PrecondData::foreign_to)
     return OGL_OK;
+}
+
+// IC / ILU: exact solves y = L^-1 r, z = U^-1 y (U = L^T for IC) level by level; IRILU: 5 Richardson sweeps per
+// triangle, x0 = the right-hand side ([UPSTREAM] Ilu<Ir, Ir> with BJ(1) inner solvers, Preconditioner.H:147-178).
+// On a renumbered device copy the vectors are carried into the caller's order and back.
+void ogl_solver::apply_factor(const double *in, double *out, const DevScalars *gate, double *dot_part)
+{
+    hipStream_t st = reg->stream;
+    const PrecondData &P = *precond_data;
+    const int32_t n = pat.n_rows;
+    const bool rn = pat.renumbered();
+    const int32_t *perm = rn ? d_new_id.p : nullptr;
+    DevTri L, U;
+    L.beg = P.f_row_ptrs.p;
+    L.end = P.f_diag.p;
+    L.cols = P.f_cols.p;
+    L.vals = P.f_vals.p;
+    L.unit = P.kind == 5 ? 0 : 1;
+    U.upper = 1;
+    if (P.kind == 5) {
+        U.beg = P.ft_row_ptrs.p;
+        U.end = P.ft_row_ptrs.p + 1;
+        U.cols = P.ft_cols.p;
+        U.vals = P.ft_vals.p;
+    } else {
+        U.beg = P.f_diag.p;
+        U.end = P.f_row_ptrs.p + 1;
+        U.cols = P.f_cols.p;
+        U.vals = P.f_vals.p;
+    }
+    if (P.kind == 7) {
+        constexpr int sweeps = IRILU_SWEEPS;
+        const double *b = in;
+        if (rn) {
+            launch_factor_gather_perm(st, n, perm, in, d_fac_tmp[2].p, gate);
+            b = d_fac_tmp[2].p;
+        }
+        // L (unit diagonal): from x0 = b, the last sweep lands in tmp0
+        const double *x = b;
+        for (int k = 0; k < sweeps; ++k) {
+            double *dst = (sweeps - 1 - k) % 2 == 0 ? d_fac_tmp[0].p : d_fac_tmp[1].p;
+            launch_tri_sweep(st, n, L, nullptr, b, x, dst, gate);
+            x = dst;
+        }
+        // U: from x0 = y (tmp0), the last sweep lands in the result (caller's order)
+        double *fin = rn ? d_fac_tmp[2].p : out;
+        const double *y = d_fac_tmp[0].p;
+        x = y;
+        for (int k = 0; k < sweeps; ++k) {
+            double *dst = (sweeps - 1 - k) % 2 == 0 ? fin : d_fac_tmp[1].p;
+            launch_tri_sweep(st, n, U, P.f_inv_d.p, y, x, dst, gate);
+            x = dst;
+        }
+        if (rn) launch_factor_scatter_perm(st, n, perm, fin, out, gate);
+    } else {
+        double *x = rn ? d_fac_tmp[2].p : out;
+        const std::vector<int32_t> &sf = fac_seg_fwd, &sb = fac_seg_bwd;
+        for (size_t g = 0; g + 2 < sf.size(); g += 3)
+            launch_tri_levels(st, L, P.f_fwd_ptr_h.data(), P.f_fwd_ptr.p, P.f_fwd_rows.p, sf[g], sf[g + 1], sf[g + 2] != 0,
+                              in, perm, x, gate);
+        for (size_t g = 0; g + 2 < sb.size(); g += 3)  // (in place: row i reads its own y_i first)
+            launch_tri_levels(st, U, P.f_bwd_ptr_h.data(), P.f_bwd_ptr.p, P.f_bwd_rows.p, sb[g], sb[g + 1], sb[g + 2] != 0,
+                              x, nullptr, x, gate);
+        if (rn) launch_factor_scatter_perm(st, n, perm, x, out, gate);
+    }
+    if (dot_part) launch_partials_dot(st, n, in, out, dot_part, gate);
+}
+
+// a zero (ILU) / non-positive (IC) pivot of the factor in use: the solve fails instead of handing out NaN.  `word` = the
+// factor's breakdown word as it came back with the final scalars.  Several ranks: a breakdown on any rank fails every rank
+// (its NaN reaches the others through the all-reduced dots).
+int ogl_solver::check_factor_breakdown(int32_t word)
+{
+    if (!precond_data || !precond_data->factor()) return OGL_OK;
+    const int32_t row = word == 0x7f7f7f7f ? -1 : word;
+    props["iluBreakdownRow"] = (double)row;
+    const int kind = precond_data->kind;
+    const char *name = kind == 5 ? "IC" : (kind == 6 ? "ILU" : "IRILU");
+    bool elsewhere = false;
+    if (reg->comm->multi()) {
+        hipStream_t st = reg->stream;
+        OGL_TRY(d_flag.alloc(2, st));
+        const double mine = row >= 0 ? 1.0 : 0.0;
+        double any = 0.0;
+        OGL_HIP_CHECK(hipMemcpyAsync(d_flag.p, &mine, sizeof(double), hipMemcpyHostToDevice, st));
+        OGL_TRY(reg->allreduce(d_flag.p, 1));
+        OGL_HIP_CHECK(hipMemcpyAsync(&any, d_flag.p, sizeof(double), hipMemcpyDeviceToHost, st));
+        OGL_HIP_CHECK(hipStreamSynchronize(st));
+        elsewhere = any != 0.0 && row < 0;
+    }
+    if (elsewhere)
+        return fail(OGL_ERR_INVALID, "preconditioner %s: the factor of another rank's local matrix broke down", name);
+    if (row < 0) return OGL_OK;
+    return fail(OGL_ERR_INVALID, "preconditioner %s: %s pivot in row %d of the local matrix (caller's numbering)%s",
+                name, kind == 5 ? "non-positive" : "zero", row, kind == 5 ? " (IC needs a positive diagonal)" : "");
 }
 
 void ogl_solver::apply_preconditioner(const double *in, double *out, const DevScalars *gate,
                                       double *dot_part)
 {
     hipStream_t st = reg->stream;
+    if (precond_data->factor()) {
+        apply_factor(in, out, gate, dot_part);
+        return;
+    }
     // the last kernel of the apply also leaves the partials of in . out
     SpmvDots last{};
     if (dot_part) {
@@ -290,19 +463,27 @@ int ogl_solver::init_preconditioner()
 {
     precond = nullptr;
     precond_data = nullptr;
-    if (cfg.preconditioner == OGL_PRECOND_NONE) return OGL_OK;  // :342
+    precond_ready = false;
+    if (cfg.preconditioner == OGL_PRECOND_NONE) {  // :342
+        precond_ready = true;
+        precond_pat = pat_id;
+        return OGL_OK;
+    }
     const bool isai = cfg.preconditioner == OGL_PRECOND_ISAI || cfg.preconditioner == OGL_PRECOND_GISAI;
-    if (cfg.preconditioner != OGL_PRECOND_BJ && !isai)
+    const bool factor = cfg.preconditioner == OGL_PRECOND_IC || cfg.preconditioner == OGL_PRECOND_ILU ||
+                        cfg.preconditioner == OGL_PRECOND_IRILU;
+    if (cfg.preconditioner != OGL_PRECOND_BJ && !isai && !factor)
         return fail(OGL_ERR_UNSUPPORTED, "preconditioner kind %d is not built", cfg.preconditioner);
     if (isai && (cfg.sparsity_power < 1 || cfg.sparsity_power > 8))
         return fail(OGL_ERR_INVALID, "ISAI sparsityPower %d outside [1, 8]", cfg.sparsity_power);
-    if (!isai && (cfg.max_block_size < 1 || cfg.max_block_size > MAX_JACOBI_BLOCK))
+    if (cfg.preconditioner == OGL_PRECOND_BJ && (cfg.max_block_size < 1 || cfg.max_block_size > MAX_JACOBI_BLOCK))
         return fail(OGL_ERR_INVALID, "BJ maxBlockSize %d outside [1, %d]", cfg.max_block_size,
                     MAX_JACOBI_BLOCK);
     if (cfg.preconditioner == OGL_PRECOND_ISAI)
         OGL_TRY(d_isai_tmp.alloc((size_t)pat.n_rows + 2, reg->stream));
-    const int kind = isai ? (cfg.preconditioner == OGL_PRECOND_ISAI ? 3 : 4)
-                          : (cfg.max_block_size == 1 ? 1 : 2);
+    const int kind = factor ? (cfg.preconditioner == OGL_PRECOND_IC ? 5 : (cfg.preconditioner == OGL_PRECOND_ILU ? 6 : 7))
+                     : isai ? (cfg.preconditioner == OGL_PRECOND_ISAI ? 3 : 4)
+                            : (cfg.max_block_size == 1 ? 1 : 2);
     const int stride = kind == 2 ? cfg.max_block_size : (isai ? cfg.sparsity_power : 0);
     const int cache = (int)prop("preconditionerCaching", 0);
     const bool stored =
@@ -312,13 +493,28 @@ int ogl_solver::init_preconditioner()
     //  a silently permuted operator here: generate for this solve instead.  Blocks kept block-major in the caller's
     //  order are applied through this solver's permutation.)
     const bool foreign = stored && reg->cached_precond.foreign_to(pat_id, pat.renumbered());
+    // (property precondTimedApplies > 0, measurements only: the generation and that many applies timed with HIP events)
+    const int timed = (int)prop("precondTimedApplies", 0.0);
+    EventPair tev;
+    if (timed > 0) {
+        OGL_HIP_CHECK(ev_create(&tev[0]));
+        OGL_HIP_CHECK(ev_create(&tev[1]));
+    }
     if (stored && cache > 0 && !foreign) {
         props["preconditionerCaching"] = cache - 1;
         precond_data = &reg->cached_precond;
     } else {
         props["preconditionerCaching"] = cfg.caching;
         PrecondData &P = stored ? own_precond : reg->cached_precond;
+        if (timed > 0) OGL_HIP_CHECK(hipEventRecord(tev[0], reg->stream));
         OGL_TRY(generate_preconditioner(P));
+        if (timed > 0) {
+            OGL_HIP_CHECK(hipEventRecord(tev[1], reg->stream));
+            OGL_HIP_CHECK(hipEventSynchronize(tev[1]));
+            float ms = 0.f;
+            OGL_HIP_CHECK(hipEventElapsedTime(&ms, tev[0], tev[1]));
+            props["precondGenerateMs"] = ms;
+        }
         if (!stored) reg->has_cached_precond = true;
         precond_data = &P;
     }
@@ -329,5 +525,53 @@ int ogl_solver::init_preconditioner()
         OGL_TRY(d_bj_tmp0.alloc((size_t)pat.n_rows + 2, reg->stream));
         OGL_TRY(d_bj_tmp1.alloc((size_t)pat.n_rows + 2, reg->stream));
     }
+    if (precond_data->factor()) {
+        // vectors in the caller's order (renumbered) and IRILU's iterates, for this solver's own applies
+        const PrecondData &P = *precond_data;
+        const size_t n = (size_t)pat.n_rows + 2;
+        if (P.kind == 7) {
+            OGL_TRY(d_fac_tmp[0].alloc(n, reg->stream));
+            OGL_TRY(d_fac_tmp[1].alloc(n, reg->stream));
+        }
+        if (pat.renumbered()) OGL_TRY(d_fac_tmp[2].alloc(n, reg->stream));
+        // (this solver's own iluThinRows, also on an object another solver generated)
+        const int32_t thin = (int32_t)prop("iluThinRows", 256.0);
+        factor_segments(P.f_fwd_ptr_h, thin, fac_seg_fwd);
+        factor_segments(P.f_bwd_ptr_h, thin, fac_seg_bwd);
+        int launches = 0;
+        if (P.kind == 7) {
+            launches = 2 * IRILU_SWEEPS + (pat.renumbered() ? 2 : 0);
+        } else {
+            for (const std::vector<int32_t> *seg : {&fac_seg_fwd, &fac_seg_bwd})
+                for (size_t g = 0; g + 2 < seg->size(); g += 3) launches += (*seg)[g + 2] ? 1 : (*seg)[g + 1] - (*seg)[g];
+            launches += pat.renumbered() ? 1 : 0;
+        }
+        props["iluLevels"] = (double)(P.f_fwd_ptr_h.size() - 1);
+        props["iluLaunchesPerApply"] = (double)launches;  // (without the fused dot of a Krylov turn)
+    }
+    if (timed > 0 && d_w.p && d_q.p) {
+        OGL_HIP_CHECK(hipEventRecord(tev[0], reg->stream));
+        for (int i = 0; i < timed; ++i) {
+            if (precond_data->kind == 1)
+                launch_mul(reg->stream, pat.n_rows, d_q.p, d_w.p, precond_data->values.p, nullptr);
+            else
+                apply_preconditioner(d_w.p, d_q.p, nullptr);
+        }
+        OGL_HIP_CHECK(hipEventRecord(tev[1], reg->stream));
+        OGL_HIP_CHECK(hipEventSynchronize(tev[1]));
+        float ms = 0.f;
+        OGL_HIP_CHECK(hipEventElapsedTime(&ms, tev[0], tev[1]));
+        props["precondApplyMs"] = ms / timed;
+    }
+    precond_ready = true;
+    precond_serial = precond_data->serial;
+    precond_pat = pat_id;
     return OGL_OK;
+}
+
+bool ogl_solver::precond_current() const
+{
+    if (!precond_ready || !matrix_set || precond_pat != pat_id) return false;
+    if (!precond_data) return cfg.preconditioner == OGL_PRECOND_NONE;
+    return precond_data->serial == precond_serial && precond_data->n_rows == (size_t)pat.n_rows;
 }
