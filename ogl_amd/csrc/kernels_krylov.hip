@@ -480,7 +480,10 @@ __global__ __launch_bounds__(BLOCK) void k_cg_step1x_fin(int n, double *p, doubl
     st2(p_out, rp, vp);
 }
 
-template <bool LEAD>
+// CPW chunks per workgroup (the leader turn: 2).  A workgroup asks for the rows of all its chunks before it waits for the
+// leaders, so the first wave of workgroups keeps twice the bytes in flight while the mailbox is awaited (the chip idles
+// after one chunk's worth otherwise).  Each chunk keeps its own partials, in the same tree: same bits.
+template <bool LEAD, int CPW>
 __global__ __launch_bounds__(BLOCK) void k_cg_step2r_fin(int n, double *__restrict__ r,
                                                          const double *__restrict__ q,
                                                          const double *__restrict__ inv_diag,
@@ -503,16 +506,23 @@ __global__ __launch_bounds__(BLOCK) void k_cg_step2r_fin(int n, double *__restri
     if (blockIdx.x == 0 && threadIdx.x < sizeof(DevScalars) / 8)
         reinterpret_cast<unsigned long long *>(sout)[threadIdx.x] =
             reinterpret_cast<const unsigned long long *>(sin)[threadIdx.x];
-    const int chunk = blockIdx.x;
-    const RowPair rp = my_rows(chunk, n);
-    double2 vr, vq, vi;
-    vi.x = vi.y = 1.0;
-    const bool early = !LEAD || lead.early_loads != 0;
-    if (early) {
-        vr = ld2(r, rp);
-        vq = ld2_stream(q, rp);  // q: last use of this turn
-        if (inv_diag) vi = ld2(inv_diag, rp);
+    RowPair rp[CPW];
+    double2 vr[CPW], vq[CPW], vi[CPW];
+#pragma unroll
+    for (int h = 0; h < CPW; ++h) {
+        rp[h] = my_rows(blockIdx.x * CPW + h, n);  // (past the last chunk: no rows)
+        vi[h].x = vi[h].y = 1.0;
     }
+    auto load_rows = [&]() {
+#pragma unroll
+        for (int h = 0; h < CPW; ++h) {
+            vr[h] = ld2(r, rp[h]);
+            vq[h] = ld2_stream(q, rp[h]);  // q: last use of this turn
+            if (inv_diag) vi[h] = ld2(inv_diag, rp[h]);
+        }
+    };
+    const bool early = !LEAD || lead.early_loads != 0;
+    if (early) load_rows();
     double pv[2][FIN_VT];
     if (!LEAD) load_partials_as_finaliser<1>(part_beta, nullptr, n_part, pv);
     if (stopped) return;
@@ -522,11 +532,7 @@ __global__ __launch_bounds__(BLOCK) void k_cg_step2r_fin(int n, double *__restri
             if (threadIdx.x == 0) sout->comm_error = sout->stop = 1;
             return;
         }
-        if (!early) {
-            vr = ld2(r, rp);
-            vq = ld2_stream(q, rp);
-            if (inv_diag) vi = ld2(inv_diag, rp);
-        }
+        if (!early) load_rows();
         if (threadIdx.x == 0) v[0] = lead_total(lead_words, 0);
     } else {
         reduce_partials_as_finaliser<1>(pv, n_part, red, v);
@@ -541,31 +547,39 @@ __global__ __launch_bounds__(BLOCK) void k_cg_step2r_fin(int n, double *__restri
     }
     __syncthreads();
     const double rho = sh[0], beta = sh[1];
-    if (beta != 0.0) {
-        const double t = rho / beta;
-        vr.x -= t * vq.x;
-        vr.y -= t * vq.y;
-        st2(r, rp, vr);
-    }
-    double2 vz = vr;
-    if (inv_diag) {
-        vz.x = vr.x * vi.x;
-        vz.y = vr.y * vi.y;
-    }
-    if (z_out) st2(z_out, rp, vz);  // (the 2-launch turn gathers z at the columns of its rows)
-    double d = 0.0, a = 0.0;
-    if (rp.n > 0) {
-        d += vr.x * vz.x;
-        a += fabs(vr.x);
-    }
-    if (rp.n > 1) {
-        d += vr.y * vz.y;
-        a += fabs(vr.y);
-    }
-    block_sum2(d, a, slot);
-    if (threadIdx.x == 0) {
-        part_rho[chunk] = d;
-        part_norm[chunk] = a;
+    const int n_chunks_all = (n + CHUNK_ROWS - 1) / CHUNK_ROWS;
+#pragma unroll
+    for (int h = 0; h < CPW; ++h) {
+        const int chunk = blockIdx.x * CPW + h;
+        if (chunk >= n_chunks_all) break;  // (workgroup-uniform)
+        const RowPair &rh = rp[h];
+        double2 vrh = vr[h];
+        if (beta != 0.0) {
+            const double t = rho / beta;
+            vrh.x -= t * vq[h].x;
+            vrh.y -= t * vq[h].y;
+            st2(r, rh, vrh);
+        }
+        double2 vz = vrh;
+        if (inv_diag) {
+            vz.x = vrh.x * vi[h].x;
+            vz.y = vrh.y * vi[h].y;
+        }
+        if (z_out) st2(z_out, rh, vz);  // (the 2-launch turn gathers z at the columns of its rows)
+        double d = 0.0, a = 0.0;
+        if (rh.n > 0) {
+            d += vrh.x * vz.x;
+            a += fabs(vrh.x);
+        }
+        if (rh.n > 1) {
+            d += vrh.y * vz.y;
+            a += fabs(vrh.y);
+        }
+        block_sum2(d, a, slot);
+        if (threadIdx.x == 0) {
+            part_rho[chunk] = d;
+            part_norm[chunk] = a;
+        }
     }
 }
 
@@ -1502,18 +1516,19 @@ void launch_cg_step1x_fin(hipStream_t st, int32_t n, double *p, double *x, const
 #undef OGL_STEP1X
 }
 
+constexpr int STEP2R_LEAD_CPW = 2;  // chunks per workgroup of the leader turn's step_2r (4 measured the same)
 void launch_cg_step2r_fin(hipStream_t st, int32_t n, double *r, const double *q, const double *inv_diag,
                           double *part_rho, double *part_norm, const DevScalars *sin, DevScalars *sout,
                           const double *part_beta, double *z_out, const LeadBox &lead)
 {
     const int nc = (int)n_chunks(n);
     if (nc == 0) return;
-    if (lead.box && nc >= 3 * FIN_WAVES)
-        hipLaunchKernelGGL(k_cg_step2r_fin<true>, dim3(nc), dim3(BLOCK), 0, st, n, r, q, inv_diag, part_rho, part_norm, sin,
-                           sout, part_beta, nc, z_out, lead);
+    if (lead.box && nc >= 3 * FIN_WAVES)  // (two chunks per workgroup: nc >= 48 leaves at least 24 workgroups, 16 of them leaders)
+        hipLaunchKernelGGL((k_cg_step2r_fin<true, STEP2R_LEAD_CPW>), dim3((nc + STEP2R_LEAD_CPW - 1) / STEP2R_LEAD_CPW),
+                           dim3(BLOCK), 0, st, n, r, q, inv_diag, part_rho, part_norm, sin, sout, part_beta, nc, z_out, lead);
     else
-        hipLaunchKernelGGL(k_cg_step2r_fin<false>, dim3(nc), dim3(BLOCK), 0, st, n, r, q, inv_diag, part_rho, part_norm, sin,
-                           sout, part_beta, nc, z_out, LeadBox{});
+        hipLaunchKernelGGL((k_cg_step2r_fin<false, 1>), dim3(nc), dim3(BLOCK), 0, st, n, r, q, inv_diag, part_rho, part_norm,
+                           sin, sout, part_beta, nc, z_out, LeadBox{});
 }
 
 void launch_cg_step2(hipStream_t st, int32_t n, double *x, double *r, const double *p,
