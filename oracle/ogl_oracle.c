@@ -1020,7 +1020,7 @@ void orc_csr_transpose(orc_label n, const orc_label *rowptr, const orc_label *co
     free(fill);
 }
 
-static void precond_apply(orc_label n, const orc_precond *P, const orc_scalar *r, orc_scalar *z) {
+void orc_precond_apply(orc_label n, const orc_precond *P, const orc_scalar *r, orc_scalar *z) {
     if (P && P->kind == ORC_PRECOND_ISAI_GENERAL) {
         orc_spmv(n, P->w_rowptr, P->w_cols, P->w_vals, r, z);
         return;
@@ -1073,7 +1073,7 @@ orc_label orc_cg_p(const orc_dist_matrix *A, const orc_scalar *b, orc_scalar *x,
     criterion_reset(st);
     dist_residual(A, b, x, r);
     for (;;) {
-        precond_apply(n, inv_diag, r, z);
+        orc_precond_apply(n, inv_diag, r, z);
         rho = dist_dot(A, r, z);
         if (criterion_check(A, crit, st, r, x, b)) break;
         { /* step_1: p = z + (rho / prev_rho) p */
@@ -1140,7 +1140,7 @@ orc_label orc_bicgstab_p(const orc_dist_matrix *A, const orc_scalar *b, orc_scal
                 memcpy(p, r, sizeof(orc_scalar) * (size_t)n);
             }
         }
-        precond_apply(n, inv_diag, p, y);
+        orc_precond_apply(n, inv_diag, p, y);
         orc_dist_spmv(A, y, v);
         beta = dist_dot(A, rr, v);
         { /* step_2: alpha = rho / beta ; s = r - alpha v */
@@ -1152,7 +1152,7 @@ orc_label orc_bicgstab_p(const orc_dist_matrix *A, const orc_scalar *b, orc_scal
             for (orc_label i = 0; i < n; ++i) x[i] += alpha * y[i]; /* finalize */
             break;
         }
-        precond_apply(n, inv_diag, s, z);
+        orc_precond_apply(n, inv_diag, s, z);
         orc_dist_spmv(A, z, t);
         gamma = dist_dot(A, s, t);
         beta = dist_dot(A, t, t);
@@ -1224,7 +1224,7 @@ orc_label orc_gmres_p(const orc_dist_matrix *A, const orc_scalar *b, orc_scalar 
                 for (orc_label j = 0; j < m; ++j) sum += VV(j)[i] * y[j];
                 w[i] = sum;
             }
-            precond_apply(n, P, w, u);
+            orc_precond_apply(n, P, w, u);
             for (orc_label i = 0; i < n; ++i) x[i] += u[i];
             dist_residual(A, b, x, r);
             const orc_scalar rn = dist_norm2(A, r);
@@ -1233,7 +1233,7 @@ orc_label orc_gmres_p(const orc_dist_matrix *A, const orc_scalar *b, orc_scalar 
             it = 0;
         }
         /* Arnoldi step */
-        precond_apply(n, P, VV(it), w);
+        orc_precond_apply(n, P, VV(it), w);
         orc_dist_spmv(A, w, VV(it + 1));
         orc_scalar *nx = VV(it + 1);
         for (orc_label k = 0; k <= it; ++k) { /* finish_arnoldi: modified Gram-Schmidt */
@@ -1276,7 +1276,7 @@ orc_label orc_gmres_p(const orc_dist_matrix *A, const orc_scalar *b, orc_scalar 
             for (orc_label j = 0; j < it; ++j) sum += VV(j)[i] * y[j];
             w[i] = sum;
         }
-        precond_apply(n, P, w, u);
+        orc_precond_apply(n, P, w, u);
         for (orc_label i = 0; i < n; ++i) x[i] += u[i];
     }
 #undef HH

@@ -282,6 +282,9 @@ void orc_csr_transpose(orc_label n, const orc_label *rowptr, const orc_label *co
                        const orc_scalar *vals, orc_label *t_rowptr, orc_label *t_cols,
                        orc_scalar *t_vals);
 
+/* z = M^-1 r, the apply every solver below uses (P == NULL or kind NONE: a copy of r) */
+void orc_precond_apply(orc_label n, const orc_precond *P, const orc_scalar *r, orc_scalar *z);
+
 /* ------------------------------------------------------------------ */
 /* Solvers ([UPSTREAM] gko::solver::Cg / Bicgstab, lduLduBase.H:272-276) */
 /* ------------------------------------------------------------------ */

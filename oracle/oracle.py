@@ -445,6 +445,13 @@ class Precond:
             self.c = _CPrecond(2, None, nb, self.block_ptrs.ctypes.data_as(_LP),
                                self.blocks.ctypes.data_as(_SP), k, None, None, None, None, None, None, None)
 
+    def apply(self, r):
+        """z = M^-1 r (orc_precond_apply: the apply inside every oracle solve); r has one entry per row."""
+        r, pr = _s(r)
+        z = np.zeros_like(r)
+        lib().orc_precond_apply(C.c_int32(r.size), C.byref(self.c), pr, z.ctypes.data_as(_SP))
+        return z
+
 
 class DistMatrix:
     """local CSR (+ optional non-local CSR, halo exchange and all-reduce callbacks)."""

@@ -102,8 +102,9 @@ def test_a_second_solve_and_a_converged_guess(reg, oracle, system, merged):
 @pytest.mark.parametrize("merged", [0.0, 1.0])
 @pytest.mark.parametrize("precond", [capi.PRECOND_BJ, capi.PRECOND_NONE])
 def test_many_tiles_of_partials(reg, precond, merged):
-    """4.5 M rows = 8,789 chunks: a leader stages nine partials per virtual thread.  The five-launch turn is the witness
-    (itself bit-equal to the oracle at 216^3, tests/test_gpu_fullsize_oracle.py)."""
+    """165^3 = 4,492,125 rows = 8,774 chunks: a leader stages nine partials per virtual thread, all of them in its first
+    tile of 32 (the second tile is reached above 32,768 chunks: tests/test_gpu_kernel_variants.py at 260^3).  The
+    five-launch turn is the witness (itself bit-equal to the oracle at 216^3, tests/test_gpu_fullsize_oracle.py)."""
     case = synthetic.poisson_case(165)
     b = synthetic.rhs_for_x_star(case)[0]
     got = {}
