@@ -19,20 +19,28 @@ matrix, b and x already resident in HBM.
               time is reported apart as `csr_equivalent_achieved` / `csr_equivalent_frac` (may exceed 1: it
               is a unit-of-work rate, not a bandwidth).
               `traffic` = HBM-side bytes per launch from the PMC counters (2*FETCH_SIZE + WRITE_SIZE, KiB; the
-              gfx950 correction of MI355X_MICROARCH.md), collected in THIS run at N = 1: after the timed region
-              two short child runs of this command under `rocprofv3 --kernel-trace --pmc <counter>` (separate
-              passes, children of this process, nothing exec'ed in place); when that is not possible (no
-              rocprofv3, this process itself profiled, a pass fails) the committed summary of exactly these
-              kernels (profiles/r*_pmc*_summary.json, refused when the kernel sources have changed) is quoted instead
-              and `traffic_measured_in_this_run` says so.
-  roofline_general = the same measurement for the general layouts on the same system, after the headline
-              and outside its timed region: --full-storage (k_spmv_sell, pattern codes), --no-compress
+              gfx950 correction of MI355X_MICROARCH.md), with --full collected in THIS run at N = 1: after the
+              timed region two short child runs of this command under `rocprofv3 --kernel-trace --pmc <counter>`
+              (separate passes, children of this process, nothing exec'ed in place); without --full, or when that
+              is not possible (no rocprofv3, this process itself profiled, a pass fails) the committed summary of
+              exactly these kernels (profiles/r*_pmc*_summary.json, refused when the kernel sources have changed) is
+              quoted instead and `traffic_measured_in_this_run` says so.
+  roofline_general = (--full) the same measurement for the general layouts on the same system, after the
+              headline and outside its timed region: --full-storage (k_spmv_sell, pattern codes), --no-compress
               (k_spmv_stream, the kernel north_star describes), --shuffle 65536 (irregular numbering: the
               library renumbers itself, k_spmv_sell with 16-bit delta codes or k_spmv_stream).
-  cpu_baseline = the oracle (sequential restatement, 1 core, "port") on the same matrix for a
+  boundary  = the first and the values-only set_matrix of the headline system; with --full also one
+              PCIe-inclusive plug-in call (solve() with H2D / D2H) and the momentum components' refreshes.
+  cpu_baseline = (--full) the oracle (sequential restatement, 1 core, "port") on the same matrix for a
               bounded number of iterations; plus its OpenMP variant as `cpu_baseline_omp`.
 
+A plain run does what `value` needs and no more: set-up, warm-up, the timed steps, --dump-outputs, the result line
+(the roofline above comes from the event pairs of the timed steps and the committed PMC summary).  --full adds
+everything else: the live PMC passes, the general legs, the PCIe-inclusive call, the CPU baselines and, at N > 1,
+the probes of the transport rungs the timed run did not use.  The timed steps are the same either way.
+
   python bench.py --gpus 1 --steps 5 --warmup 1
+  python bench.py --gpus 1 --steps 5 --warmup 1 --full                 # + every figure besides the headline
   python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR     # + the last step's x and residuals as .npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
          --master-port 29500 bench.py --gpus 8 --steps 5 --warmup 1
@@ -57,6 +65,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures and checks: the live PMC "
+                         "passes, the roofline_general legs, the PCIe-inclusive plug-in call and the momentum "
+                         "components (boundary), the CPU baselines, the transport rung probes at N > 1 and, with "
+                         "--no-profile, the separate SpMV loop.  Without it a run sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the result line")
     # (--edge, not --n: torch.distributed.run abbreviates its own options and would swallow --n)
     ap.add_argument("--edge", "--n", dest="n", type=int, default=216,
                     help="box edge per GPU (216 = configs[1])")
@@ -120,7 +134,7 @@ def parse():
                          "turn of systems of <= 1024 chunks, where it takes 2 us off a turn; off above, "
                          "where it measured no faster than stream launches")
     ap.add_argument("--cpu-iters", type=int, default=-1,
-                    help="oracle iterations for cpu_baseline (-1: sized for ~15 s, 0: skip)")
+                    help="with --full: oracle iterations for cpu_baseline (-1: sized for ~15 s, 0: skip)")
     ap.add_argument("--profile-stride", type=int, default=4,
                     help="event-time the in-loop SpMV of every k-th turn (an event pair costs ~2 us of "
                          "the stream's time)")
@@ -131,15 +145,16 @@ def parse():
                     help="set a solver property before set_matrix (development switches: xcdGroup, streamAboveBytes, "
                          "deviceSetup, ...); repeatable")
     ap.add_argument("--no-general-legs", dest="general_legs", action="store_false",
-                    help="skip the roofline_general legs (full storage, CSR-stream, shuffled cells) that follow the "
-                         "headline measurement of the default run")
-    ap.add_argument("--general-steps", type=int, default=5, help="timed steps of each roofline_general leg")
+                    help="with --full: skip the roofline_general legs (full storage, CSR-stream, shuffled cells) that "
+                         "follow the headline measurement")
+    ap.add_argument("--general-steps", type=int, default=5,
+                    help="with --full: timed steps of each roofline_general leg")
     ap.add_argument("--live-pmc", default="auto", choices=["auto", "on", "off"],
-                    help="roofline.traffic measured in THIS run: after the timed region two short child runs of this "
-                         "command under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate passes, ~25 s each). "
-                         "auto: the default headline run at N = 1 when rocprofv3 is there and this process is not "
-                         "itself profiled; otherwise (and whenever a pass fails) the committed summary of the same "
-                         "kernels is quoted")
+                    help="with --full: roofline.traffic measured in THIS run: after the timed region two short child "
+                         "runs of this command under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate "
+                         "passes, ~25 s each).  auto: the headline workload at N = 1 when rocprofv3 is there and this "
+                         "process is not itself profiled; otherwise (and whenever a pass fails, and without --full) the "
+                         "committed summary of the same kernels is quoted")
     ap.add_argument("--config", type=int, default=0, choices=[0, 3, 4],
                     help="the 8-way configurations as BASELINE.json states them, STRONG scaling (the global system is "
                          "fixed, `value` = global solver turns per second): 3 = channel-flow proxy of 20 M cells "
@@ -147,15 +162,15 @@ def parse():
                          "(368^3 box, every rank's cells shuffled in windows of 65536) cut the same way, "
                          "GKOGMRES(30) + BJ, --format Csr | Ell.  0 = the headline workload (216^3 per GPU, weak scaling)")
     ap.add_argument("--no-rung-probes", dest="rung_probes", action="store_false",
-                    help="N > 1: do not collect evidence for the transport rungs the timed run did not use (by default "
-                         "every rung of the ladder -- peer mesh over RCCL, peer mesh over the host bootstrap, RCCL alone, "
-                         "host buffers alone -- is brought up once in child processes after the timed region, self-checked "
-                         "and timed for a few steps: config.transport.rungs)")
+                    help="N > 1 with --full: do not collect evidence for the transport rungs the timed run did not "
+                         "use (by default every rung of the ladder -- peer mesh over RCCL, peer mesh over the host "
+                         "bootstrap, RCCL alone, host buffers alone -- is brought up once in child processes after the "
+                         "timed region, self-checked and timed for a few steps: config.transport.rungs)")
     ap.add_argument("--rung-timeout", type=float, default=120.0,
                     help="seconds a rung probe may take before its child processes are ended")
     ap.add_argument("--no-profile", action="store_true",
                     help="do not event-time the in-loop SpMV (roofline then comes from a "
-                         "separate back-to-back SpMV loop)")
+                         "separate back-to-back SpMV loop, run with --full)")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="after the timed steps, write what the last one computed -- the solution x and the solve's "
                          "residuals, what the caller of apply gets back -- as DIR/<name>.npy (float64, at most 64 MB "
@@ -251,9 +266,11 @@ def live_pmc_traffic(kernel, argv_tail):
     try:
         for cnt in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, cnt)
+            # (--full with every extra but the PCIe-inclusive call switched off: the launches counted are the timed
+            #  step's and that call's)
             cmd = [exe, "--kernel-trace", "--pmc", cnt, "--output-format", "csv", "-d", out, "--", "python3",
-                   os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--iters", "20", "--cpu-iters", "0",
-                   "--no-general-legs", "--live-pmc", "off"] + argv_tail
+                   os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--iters", "20", "--full",
+                   "--cpu-iters", "0", "--no-general-legs", "--live-pmc", "off"] + argv_tail
             p = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=120)
             if p.returncode != 0:
                 _LIVE_PMC_STATE["broken"] = f"rocprofv3 --pmc {cnt} pass failed (rc {p.returncode}): {p.stderr[-300:]}"
@@ -698,7 +715,8 @@ def main():
 
     def spmv_roofline(sv, n_rows, n_nnz, spmv_ms, timing, pmc_variant, in_loop=True):
         """roofline object of the in-loop SpMV of solver `sv`: `achieved` / `frac` on the bytes the layout in
-        use has to move (matrix data + x read once + y written), the CSR-equivalent rate apart."""
+        use has to move (matrix data + x read once + y written), the CSR-equivalent rate apart.  spmv_ms None (not
+        timed): the rates are None."""
         b_csr = 12 * n_nnz + 20 * n_rows + 4            # SURVEY.md §8d: values + columns + row pointers + x + y
         if args.format == "Ell":                        # SURVEY.md §8d: 7 slots/row -> 84 N + 16 N
             b_csr = (12 * 7 + 16) * n_rows
@@ -732,12 +750,14 @@ def main():
             b_moved += 32 * n_rows
             b_csr += 32 * n_rows
         traffic, traffic_src = pmc_traffic(kernel, pmc_variant) if pmc_variant is not None else (None, None)
-        moved = b_moved / (spmv_ms * 1e-3) / 1e9
+        moved, csr_rate = ((None, None) if spmv_ms is None else
+                           (b_moved / (spmv_ms * 1e-3) / 1e9, b_csr / (spmv_ms * 1e-3) / 1e9))
+        of = lambda r, peak: None if r is None else r / peak
         return layout, b_moved, b_csr, {
             "kernel": kernel, "layout": layout, "merged": merged, "bound": "hbm",
-            "achieved": moved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": moved / HBM_PEAK_GBPS,
+            "achieved": moved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": of(moved, HBM_PEAK_GBPS),
             "bytes_per_launch": b_moved,
-            "frac_of_measured_copy_peak": moved / HBM_COPY_GBPS,
+            "frac_of_measured_copy_peak": of(moved, HBM_COPY_GBPS),
             # (the committed summary of exactly this kernel instantiation; replaced in main() by counters collected
             #  in this run when the live PMC passes are on)
             "traffic": traffic, "traffic_source": traffic_src,
@@ -746,14 +766,15 @@ def main():
             # the same time priced in SURVEY.md 8(d)'s CSR bytes (the unit of work `matrixFormat Csr` names):
             # a rate of work, not a bandwidth -- above 1 when the layout moves fewer bytes than a CSR
             "csr_equivalent_bytes_per_launch": b_csr,
-            "csr_equivalent_achieved": b_csr / (spmv_ms * 1e-3) / 1e9,
-            "csr_equivalent_frac": b_csr / (spmv_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+            "csr_equivalent_achieved": csr_rate,
+            "csr_equivalent_frac": of(csr_rate, HBM_PEAK_GBPS),
             "avg_kernel_ms": spmv_ms, "timing": timing,
         }
 
     if args.no_profile:
-        spmv_ms = s.time_spmv(100)
-        spmv_src = "100 back-to-back launches, HIP events"
+        # (a loop of its own: --full only)
+        spmv_ms = s.time_spmv(100) if args.full else None
+        spmv_src = "100 back-to-back launches, HIP events" if args.full else "not timed (--no-profile without --full)"
     else:
         launches = sum(p.spmv_launches for p in perfs)
         spmv_ms = sum(p.spmv_avg_ms * p.spmv_launches for p in perfs) / max(1, launches)
@@ -770,8 +791,8 @@ def main():
     profiled = any(k in os.environ.get("LD_PRELOAD", "") for k in ("rocprof", "roctracer")) or \
         any(k.startswith("ROCPROF") for k in os.environ)
     live_tail = ["--edge", str(n), "--precond", args.precond, "--solver", args.solver]
-    want_live = args.live_pmc == "on" or (args.live_pmc == "auto" and pmc_variant == "" and not args.no_profile
-                                          and not args.prop and not profiled)
+    want_live = args.full and (args.live_pmc == "on" or (args.live_pmc == "auto" and pmc_variant == ""
+                                                         and not args.no_profile and not args.prop and not profiled))
     if want_live and world == 1 and rank == 0 and not os.environ.get("OGL_BENCH_CHILD"):
         live, how = live_pmc_traffic(roofline["kernel"], live_tail)
         roofline["traffic_committed_summary"] = {"bytes": roofline["traffic"], "source": roofline["traffic_source"]}
@@ -829,20 +850,34 @@ def main():
     merged_extra = roofline["merged"]["extra_bytes_per_launch"] if roofline["merged"] else 0
     b_turn, b_turn_what = turn_model(b_moved - merged_extra)   # (the model prices the SpMV alone)
     b_turn_csr, _ = turn_model(b_spmv - merged_extra)
-    # end-to-end plug-in call incl. PCIe (reported, never `value`): one solve() with H2D/D2H
-    # (host arrays prepared outside the timed region: the C ABI borrows the caller's arrays, it allocates nothing)
-    ldu_arrays = capi.LduArrays(case)
-    psi_io = np.zeros_like(b)
-    t0 = time.perf_counter()
-    s.set_matrix(ldu_arrays)
-    _, p_e2e = s.solve(b, psi_io, inplace=True)
-    t_e2e = time.perf_counter() - t0
+    # the headline system's set_matrix calls (load(), before the timed steps)
+    boundary = {"first_set_matrix_s": t_first_matrix, "refresh_set_matrix_s": t_refresh_matrix,
+                "h2d_GBps": 8.0 * (case.n_faces * (1 if case.lower is None else 2) + N) / 1e9 /
+                            max(1e-9, t_refresh_matrix)}
+    if args.full:
+        # end-to-end plug-in call incl. PCIe (reported, never `value`): one solve() with H2D/D2H
+        # (host arrays prepared outside the timed region: the C ABI borrows the caller's arrays, it allocates nothing)
+        ldu_arrays = capi.LduArrays(case)
+        psi_io = np.zeros_like(b)
+        t0 = time.perf_counter()
+        s.set_matrix(ldu_arrays)
+        _, p_e2e = s.solve(b, psi_io, inplace=True)
+        t_e2e = time.perf_counter() - t0
+        boundary.update({
+            "solve_incl_pcie_s": t_e2e,
+            "iters_per_sec_incl_pcie": (p_e2e.n_iterations - 1) / t_e2e,
+            # the legs of that one plug-in call as the library timed them (ogl_perf, lduLduBase.H:296-305's block):
+            # coefficients up (upper [+ lower] + diag through the pinned ring, then the gathers), b [+ x] up,
+            # the Krylov loop, x down
+            "update_matrix_ms": p_e2e.t_update_matrix_ms, "upload_ms": p_e2e.t_upload_ms,
+            "solve_ms": p_e2e.t_solve_ms, "copy_back_ms": p_e2e.t_copy_back_ms,
+            "d2h_GBps": 8.0 * N / 1e6 / max(1e-9, p_e2e.t_copy_back_ms)})
 
     # Momentum components (ogl_solver_set_matrix_like): three solvers on ONE set of host arrays, as solveSegregated
     # builds them for Ux, Uy, Uz -- the second and third take the first one's device copy of upper / lower
     components = None
     if world == 1 and not args.config and not os.environ.get("OGL_BENCH_CHILD") and plain_box and not args.shuffle \
-            and cg_headline:
+            and cg_headline and args.full:
         cs = [reg.solver("U" + c, cfg) for c in "xyz"]
         for k, c in enumerate(cs):                       # (patterns: not timed)
             c.set_matrix(ldu_arrays, like=cs[k - 1] if k else None)
@@ -864,7 +899,7 @@ def main():
     general = None
     if world == 1 and args.general_legs and plain_box and not args.shuffle and args.format == "Csr" and not args.config \
             and not (args.full_storage or args.no_compress or args.force_compress) and cg_headline \
-            and not args.no_profile:
+            and not args.no_profile and args.full:
         general = []
         legs = [("full_storage", dict(symmetric_half=0), None, "_fullstorage"),
                 ("no_compress", dict(compress_indices=0), None, "_nocompress"),
@@ -931,7 +966,7 @@ def main():
                 "shares_its_device": prop_or(s, "peerSharedDevice", 0.0) == 1.0}
         waits = [None] * world
         dist.all_gather_object(waits, mine)
-        if args.rung_probes and not os.environ.get("OGL_BENCH_RUNG"):
+        if args.full and args.rung_probes and not os.environ.get("OGL_BENCH_RUNG"):
             rungs = probe_rungs(chosen_rung, 1e3 * elapsed / max(1, iters) * 1e3)
 
     if general:
@@ -1004,8 +1039,8 @@ def main():
                           "rccl_ranks_seen": comm_info.ranks_seen if comm_info.transport == 2 else None,
                           "peer_mesh": bool(comm_info.peer_mesh), "stepped_down_from": tried,
                           "timed_rung": chosen_rung,
-                          # every rung of the ladder brought up once (the ones the timed run did not use: in child
-                          # processes after the timed region), self-checked and timed on this workload
+                          # with --full: every rung of the ladder brought up once (the ones the timed run did not use:
+                          # in child processes after the timed region), self-checked and timed on this workload
                           "rungs": rungs,
                           "wait_us": waits},
             "selfcheck": selfcheck_report,
@@ -1043,26 +1078,14 @@ def main():
             "csr_equivalent_bytes": b_turn_csr,
             "csr_equivalent_frac_of_peak": b_turn_csr * iters / elapsed / 1e9 / HBM_PEAK_GBPS,
         },
-        "boundary": {
-            "first_set_matrix_s": t_first_matrix, "refresh_set_matrix_s": t_refresh_matrix,
-            "solve_incl_pcie_s": t_e2e,
-            "iters_per_sec_incl_pcie": (p_e2e.n_iterations - 1) / t_e2e,
-            # the legs of that one plug-in call as the library timed them (ogl_perf, lduLduBase.H:296-305's block):
-            # coefficients up (upper [+ lower] + diag through the pinned ring, then the gathers), b [+ x] up,
-            # the Krylov loop, x down
-            "update_matrix_ms": p_e2e.t_update_matrix_ms, "upload_ms": p_e2e.t_upload_ms,
-            "solve_ms": p_e2e.t_solve_ms, "copy_back_ms": p_e2e.t_copy_back_ms,
-            "h2d_GBps": 8.0 * (case.n_faces * (1 if case.lower is None else 2) + N) / 1e9 /
-                        max(1e-9, t_refresh_matrix),
-            "d2h_GBps": 8.0 * N / 1e6 / max(1e-9, p_e2e.t_copy_back_ms),
-            "momentum_components": components,
-        },
+        "boundary": dict(boundary, momentum_components=components),
     }
 
     # ---- CPU baseline (rank 0, N=1 only): the oracle on the same matrix ----------------------
     headline = (args.solver == "GKOCG" and args.precond in ("BJ", "none") and args.block_size == 1
                 and not args.asym)
-    if rank == 0 and world == 1 and args.cpu_iters != 0 and headline and not args.shuffle and not args.config:
+    if rank == 0 and world == 1 and args.cpu_iters != 0 and headline and not args.shuffle and not args.config \
+            and args.full:
         # a child process: thread placement must be fixed before an OpenMP runtime loads (this process
         # already carries torch's), and the oracle shares nothing with the GPU run
         env = {k: v for k, v in os.environ.items() if not k.startswith("OMP_")}

@@ -58,13 +58,13 @@ for STAGE in "$@"; do
     smoke)
       python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2;;
     bench)
-      EXTRA="--cpu-iters 0"; [ "$A1" = default ] && EXTRA=""
+      EXTRA="--full --cpu-iters 0"; [ "$A1" = default ] && EXTRA="--full"
       python bench.py --steps 5 --warmup 1 $EXTRA $(variant $A1) > gpurun_out/${TAG}_bench_$A1.json 2> gpurun_out/${TAG}_bench_$A1.err \
         || { echo "bench $A1 FAILED"; tail -5 gpurun_out/${TAG}_bench_$A1.err; };;
     prof)
       ( cd /tmp && export TMPDIR=/tmp && cd "$OLDPWD"
         OUT=$PWD/gpurun_out/prof_${TAG}_$A1; rm -rf $OUT; mkdir -p $OUT
-        rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --steps 3 --warmup 1 --cpu-iters 0 --no-general-legs $(variant $A1) > $OUT/bench.json 2> $OUT/bench.err
+        rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --steps 3 --warmup 1 --full --cpu-iters 0 --no-general-legs $(variant $A1) > $OUT/bench.json 2> $OUT/bench.err
         echo "prof $A1 rc=$?"
         F=$(find $OUT -name '*kernel_stats.csv' | head -1); [ -n "$F" ] && cp $F $OUT/kernel_stats.csv && head -8 $F | cut -c1-220
         find $OUT -name '*kernel_trace.csv' -size +20M -delete );;
@@ -73,7 +73,7 @@ for STAGE in "$@"; do
         DIRS=""
         for CNT in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
           NAME=$(echo $CNT | tr ' ' '+'); OUT=$PWD/gpurun_out/pmc_${TAG}_${A1}_$NAME; rm -rf $OUT; mkdir -p $OUT
-          rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d $OUT -- python3 bench.py --steps 1 --warmup 0 --iters 20 --cpu-iters 0 --no-general-legs $(variant $A1) > $OUT/bench.json 2> $OUT/bench.err
+          rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d $OUT -- python3 bench.py --steps 1 --warmup 0 --iters 20 --full --cpu-iters 0 --no-general-legs $(variant $A1) > $OUT/bench.json 2> $OUT/bench.err
           echo "pmc $A1 $NAME rc=$?"; DIRS="$DIRS $OUT"
         done
         python3 tools/pmc_summary.py gpurun_out/pmc_${TAG}_${A1}_summary.json $DIRS | grep k_spmv
@@ -86,7 +86,7 @@ for STAGE in "$@"; do
     ranks)
       for PEER in 1 0; do
         OGL_BENCH_PEER=$PEER timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node=$A1 --master-addr 127.0.0.1 \
-          --master-port $((29520 + PEER)) bench.py --gpus $A1 --steps 3 --warmup 1 --edge ${A2:-128} --iters 100 --cpu-iters 0 \
+          --master-port $((29520 + PEER)) bench.py --gpus $A1 --steps 3 --warmup 1 --edge ${A2:-128} --iters 100 --full --cpu-iters 0 \
           > gpurun_out/${TAG}_ranks${A1}_e${A2:-128}_peer$PEER.json 2> gpurun_out/${TAG}_ranks${A1}_e${A2:-128}_peer$PEER.err
         echo "ranks $A1 edge ${A2:-128} peer=$PEER rc=$?"
       done;;
@@ -96,7 +96,7 @@ for STAGE in "$@"; do
       ( cd /tmp && export TMPDIR=/tmp && cd "$OLDPWD"
         OUT=$PWD/gpurun_out/ranktrace_${TAG}_${A1}_e${A2:-128}; rm -rf $OUT; mkdir -p $OUT
         timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node=$A1 --master-addr 127.0.0.1 --master-port 29533 \
-          --no-python rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --gpus $A1 --steps 2 --warmup 1 \
+          --no-python rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --gpus $A1 --steps 2 --warmup 1 --full \
           --edge ${A2:-128} --iters 40 --cpu-iters 0 --no-selfcheck > $OUT/bench.json 2> $OUT/bench.err
         echo "ranktrace $A1 rc=$?"
         python3 tools/ranks_trace.py $OUT > gpurun_out/${TAG}_ranktrace_${A1}_e${A2:-128}.txt 2>&1
