@@ -398,6 +398,19 @@ void launch_cg_step2r_fin(hipStream_t st, int32_t n, double *r, const double *q,
                           double *part_rho, double *part_norm, const DevScalars *sin, DevScalars *sout,
                           const double *part_beta, double *z_out = nullptr,  // z_out: z = r / d kept for k_cg_turn_sym
                           const LeadBox &lead = LeadBox{});
+// The held-z turn (kernels_krylov.hip, k_cg_step2r1x): step_2r_fin of a turn and step_1x_fin of the next in one resident
+// kernel that keeps z = r / d on chip.  `s` is read and rewritten in place; launch_seq advances by two.
+struct HeldZ {
+    unsigned long long *tagged = nullptr;  // 4 words per chunk, fine-grained: the chunk's two partials as tagged half-words
+    int32_t grid = 0;                      // workgroups, all resident at once; each owns chunks w, w + grid, ...
+    int32_t x_early = 1;                   // 1: a head that updates x does so while the sums are awaited
+};
+int held_z_grid(int *chunks_per_workgroup);  // the largest resident grid of the kernel on this device (0: none)
+// every workgroup of `grid` waits, bounded, for all the others: *out = 1 afterwards when they were not all on the chip at once
+int launch_resident_census(hipStream_t st, int grid, unsigned *arrived, int *out, long long timeout_ticks);
+void launch_cg_step2r1x(hipStream_t st, int32_t n, double *r, const double *q, const double *inv_diag, double *p,
+                        double *p_out, double *x, DevScalars *s, const double *part_beta, double *history,
+                        const LeadBox &lead, const PRing &ring, const HeldZ &hz);
 constexpr int FUSED_FIN_MAX_CHUNKS = 1024;  // up to 524,288 rows: one partial per virtual finaliser thread
 // step_1x_fin and the SpMV on half storage in one launch (p_new = z + (rho/rho') p recomputed at the gathered
 // columns; it goes to p_out != p_in for the own rows): a turn is this + step_2r_fin.  z: what step_2r_fin's z_out

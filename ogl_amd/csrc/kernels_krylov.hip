@@ -584,6 +584,289 @@ __global__ __launch_bounds__(BLOCK) void k_cg_step2r_fin(int n, double *__restri
 }
 
 // ------------------------------------------------------------------------------------------
+// The held-z turn (streamed single-rank GKOCG, scalar Jacobi or none): step_2r of turn j and the head (check + pending x
+// update + step_1) of turn j + 1 in ONE resident kernel, so that z = r' / d -- which step_2r has in registers and the head
+// would form again from a second read of r' and 1/d, 16 N bytes per turn -- stays on chip across the grid-wide sums
+// (rho = sum r'.z, sum |r'|) that stand between the two.
+//   grid: G = CUs x B workgroups, all resident at once (the host asks the occupancy and runs a census launch first);
+//   workgroup w owns chunks w, w + G, w + 2 G, ... (one streaming front, as the chunk = block kernels have), at most
+//   R + L of them: z of the first R in registers (compile-time indexed), of the next L in LDS.
+//   phase 1 (step_2r): beta from the leaders as in k_cg_step2r_fin; r' = r - t q stored; the chunk's two partials -- same
+//     tree as everywhere -- go out as tagged half-words [tag : 32 | payload : 32] in fine-grained memory, no fence;
+//   sums: the first 2 x 16 workgroups are the finaliser's wavefronts once more: they POLL the tagged partials of their
+//     virtual threads, add them in lead_wave_sums' order and publish to the LeadBox; everybody polls the box.  No vector
+//     data crosses workgroups, so nobody needs a release;
+//   phase 2 (head): the check on every workgroup's own copy of the scalars (workgroup 0 stores them), x += ... on a head
+//     that does not defer (before the wait when x_early: it needs the incoming rho and phase 1's beta only), and
+//     p_new = z + (rho / rho') p with the z kept.
+// The scalars stay in ONE slot: every workgroup has read every field it needs before it publishes its first partial (the
+// barriers of block_sum2 stand between), and workgroup 0 writes only after it has seen the sums of ALL partials.
+// Every spin is bounded by lead.timeout_ticks and ends the solve with comm_error.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void put_tagged(unsigned long long *w, uint32_t tag, double v)
+{
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
+    __hip_atomic_store(w, ((unsigned long long)tag << 32) | (uint32_t)bits, __ATOMIC_RELAXED, LEAD_SCOPE);
+    __hip_atomic_store(w + 1, ((unsigned long long)tag << 32) | (uint32_t)(bits >> 32), __ATOMIC_RELAXED, LEAD_SCOPE);
+}
+
+// lead_wave_sums over partials that arrive while it runs: partial i of array a is words 4 i + 2 a, + 1 of `tagged`
+// (put_tagged); a word counts once it carries `tag`.  One wavefront, no staging: lane l is virtual thread 64 w + l and
+// adds its partials v, v + 1024, ... in that order -- with a grid of FIN_BLOCK workgroups the order in which workgroup v
+// produces them -- four at a time, so that only the last four are awaited after the chip's last chunk.  A partial that
+// never arrives: nothing is published, and every workgroup's wait for the box runs into its bound.
+__device__ __forceinline__ void lead_wave_sums_tagged(const LeadBox &L, uint32_t tag, const unsigned long long *tagged,
+                                                      int m, int w, int array)
+{
+    constexpr int Q = 4;
+    if (threadIdx.x >= WAVE) return;
+    const int lane = threadIdx.x;
+    const long long t0 = wall_clock64();
+    double s = 0.0;
+    bool arrived = true;
+    for (long i0 = w * WAVE + lane; arrived && i0 < m; i0 += (long)FIN_BLOCK * Q) {
+        unsigned long long lo[Q], hi[Q];
+        for (;;) {
+            bool all = true;
+#pragma unroll
+            for (int e = 0; e < Q; ++e) {
+                const long i = i0 + (long)FIN_BLOCK * e;
+                lo[e] = hi[e] = (unsigned long long)tag << 32;
+                if (i < m) {
+                    lo[e] = __hip_atomic_load(tagged + 4 * i + 2 * array, __ATOMIC_RELAXED, LEAD_SCOPE);
+                    hi[e] = __hip_atomic_load(tagged + 4 * i + 2 * array + 1, __ATOMIC_RELAXED, LEAD_SCOPE);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < Q; ++e) all = all && (uint32_t)(lo[e] >> 32) == tag && (uint32_t)(hi[e] >> 32) == tag;
+            if (all) break;
+            if (wall_clock64() - t0 > L.timeout_ticks) {
+                arrived = false;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(1);
+        }
+#pragma unroll
+        for (int e = 0; e < Q; ++e)
+            if (i0 + (long)FIN_BLOCK * e < m) s += __longlong_as_double((long long)((hi[e] << 32) | (uint32_t)lo[e]));
+    }
+    if (!__all(arrived)) return;  // (the whole wavefront: a sum that lacks one lane's partials must not go out)
+    s = wave_sum(s);
+    if (lane < LEAD_REPLICAS) put_tagged(L.box + (size_t)lane * LEAD_REPLICA_STRIDE + array * 2 * FIN_WAVES + 2 * w, tag, s);
+}
+
+template <int R, int L, int B, int K>
+__global__ __launch_bounds__(BLOCK, B) void k_cg_step2r1x(int n, double *__restrict__ r, const double *__restrict__ q,
+                                                          const double *__restrict__ inv_diag, double *p, double *p_out,
+                                                          double *__restrict__ x, DevScalars *s,
+                                                          const double *__restrict__ part_beta,
+                                                          unsigned long long *tagged, int n_part, double *history,
+                                                          LeadBox lead, const double *p_pend, int ring_phase,
+                                                          int x_early)
+{
+    // (p_pend, ring_phase: PRing::b[1] and PRing::phase of the head in here -- the whole ring would cost 16 SGPRs)
+    static_assert(K == 0 || K == 2, "p in place or two p buffers");
+    constexpr int D = 2;  // chunks whose rows are in flight ahead of the one at work
+    __shared__ double zl[L > 0 ? L * CHUNK_ROWS : 1];
+    __shared__ double sh[4];
+    __shared__ int sh_stop;
+    __shared__ double slot[2 * N_WAVES];
+    __shared__ double lead_words[LEAD_BOX_WORDS / 2];
+    __shared__ int lead_timed_out;
+    static_assert(L * CHUNK_ROWS >= LEAD_STAGE, "the leaders of beta stage through zl, which is idle until phase 1");
+    const uint32_t seq = s->launch_seq;
+    lead_leaders<1>(lead, seq, part_beta, nullptr, nullptr, n_part, zl);  // (as step_2r_fin)
+    const int stopped = s->stop;
+    const double s_rho = s->rho, s_nf = s->norm_factor, s_init = s->init_res;
+    const int phase = K > 0 ? ring_phase : 0;
+    const bool defers = K > 0 && phase != 0;
+    const unsigned s_pending = K > 0 ? (unsigned)s->defer_valid : 0u;
+    const double s_t1 = K > 0 ? s->t_ring[1] : 0.0;
+    const int s_iter = s->iter, s_evals = s->n_evals;
+    const double c_tol = s->crit.tolerance, c_rel = s->crit.rel_tol;
+    const int c_min = s->crit.min_iter, c_max = s->crit.max_iter, c_freq = s->crit.frequency, c_exp = s->crit.export_res;
+    const int G = gridDim.x, w = blockIdx.x, tx = threadIdx.x;
+    const int mine = w < n_part ? (n_part - w + G - 1) / G : 0;  // chunks of this workgroup (<= R + L: the launcher's cap)
+    double2 fr[D], fq[D], fi[D];
+    auto ask = [&](int i, int d) {  // (past the last chunk: no rows, no loads)
+        const RowPair rp = my_rows(w + i * G, n);
+        fr[d] = ld2(r, rp);
+        fq[d] = ld2_stream(q, rp);
+        fi[d].x = fi[d].y = 1.0;
+        if (inv_diag) fi[d] = ld2_stream(inv_diag, rp);  // its only use in the turn
+    };
+#pragma unroll
+    for (int d = 0; d < D; ++d) ask(d, d);
+    if (stopped) return;  // (every workgroup sees the same flag: nobody polls, nobody writes)
+    if (!lead_wait(lead, 2 * FIN_WAVES, seq, lead_words, &lead_timed_out)) {
+        if (tx == 0) s->comm_error = s->stop = 1;
+        return;
+    }
+    if (tx == 0) sh[0] = lead_total(lead_words, 0);
+    __syncthreads();
+    const double beta = sh[0];  // FIN_BETA
+    const uint32_t tag = seq + 1;
+    double2 zr[R];
+#pragma unroll
+    for (int i = 0; i < R + L; ++i) {
+        if (i >= mine) continue;  // (workgroup-uniform; no break: the loop must unroll, zr[] is indexed at compile time)
+        const int chunk = w + i * G;
+        const RowPair rp = my_rows(chunk, n);
+        double2 vr = fr[i % D];
+        const double2 vq = fq[i % D], vi = fi[i % D];
+        if (i + D < R + L) ask(i + D, i % D);
+        if (beta != 0.0) {
+            const double t = s_rho / beta;
+            vr.x -= t * vq.x;
+            vr.y -= t * vq.y;
+            st2(r, rp, vr);
+        }
+        double2 vz = vr;
+        if (inv_diag) {
+            vz.x = vr.x * vi.x;
+            vz.y = vr.y * vi.y;
+        }
+        if (i < R) {
+            zr[i < R ? i : 0] = vz;
+        } else {
+            zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx] = vz.x;
+            zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx + 1] = vz.y;
+        }
+        double d = 0.0, a = 0.0;
+        if (rp.n > 0) {
+            d += vr.x * vz.x;
+            a += fabs(vr.x);
+        }
+        if (rp.n > 1) {
+            d += vr.y * vz.y;
+            a += fabs(vr.y);
+        }
+        block_sum2(d, a, slot);
+        if (tx == 0) {
+            put_tagged(tagged + 4 * (size_t)chunk, tag, d);
+            put_tagged(tagged + 4 * (size_t)chunk + 2, tag, a);
+        }
+    }
+    // the sums of all partials: workgroup b < 32 is wavefront b % 16 of the finaliser for array b / 16
+    if (w < 2 * FIN_WAVES) lead_wave_sums_tagged(lead, tag, tagged, n_part, w % FIN_WAVES, w / FIN_WAVES);
+    // this head's term of x and the terms pending before it: ((x + t_1 p_1) + t p), the bits of single updates
+    const bool own_term = beta != 0.0;
+    const double t_own = own_term ? s_rho / beta : 0.0;
+    auto update_x = [&](const RowPair &rp, const double2 &vp, int upto) {
+        const bool pend = K > 1 && 1 < upto && ((s_pending >> 1) & 1u);
+        if (!pend && !own_term) return;
+        double2 vx = ld2_stream(x, rp);
+        if (pend) {
+            const double2 v1 = ld2(p_pend, rp);
+            vx.x += s_t1 * v1.x;
+            vx.y += s_t1 * v1.y;
+        }
+        if (own_term) {
+            vx.x += t_own * vp.x;
+            vx.y += t_own * vp.y;
+        }
+        st2_stream(x, rp, vx);
+    };
+    const bool early = x_early != 0 && !defers;
+    if (early) {
+#pragma unroll 2
+        for (int i = 0; i < mine; ++i) {
+            const RowPair rp = my_rows(w + i * G, n);
+            update_x(rp, ld2(p, rp), K);
+        }
+    }
+    if (!lead_wait(lead, 4 * FIN_WAVES, tag, lead_words, &lead_timed_out)) {
+        if (tx == 0) s->comm_error = s->stop = 1;
+        return;
+    }
+    if (tx == 0) {
+        // FIN_CG_CHECK, as in k_cg_step1x_fin
+        const double prev_rho = s_rho, rho = lead_total(lead_words, 0), norm = lead_total(lead_words, 1);
+        int iter = s_iter, n_evals = s_evals, stop = 0;
+        double init_res = s_init, res = 0.0;
+        bool evaluated = false;
+        if (iter > 0 && iter < c_min) {
+            iter += 1;
+        } else if (iter % c_freq != 0) {
+            iter += 1;
+        } else {
+            evaluated = true;
+            n_evals += 1;
+            res = norm;
+            if (iter == 0) init_res = res / s_nf;
+            res /= s_nf;
+            if (c_exp && history && w == 0) history[iter] = res;
+            if (iter >= c_max) stop = 1;
+            if (res < c_tol) stop = 1;
+            if (c_rel > 0 && res < c_rel * init_res) stop = 1;
+            iter += 1;
+        }
+        sh[1] = prev_rho;
+        sh[2] = rho;
+        sh_stop = stop;
+        if (w == 0) {
+            s->beta = beta;
+            s->prev_rho = prev_rho;
+            s->rho = rho;
+            s->iter = iter;
+            s->x_pending = 0;
+            if (evaluated) {
+                s->n_evals = n_evals;
+                s->init_res = init_res;
+                s->res = res;
+            }
+            if (stop) s->stop = 1;
+            s->launch_seq = seq + 2;
+            s->defer_valid = (defers && !stop) ? (int)(s_pending | (own_term ? 1u << phase : 0u)) : 0;
+            if (defers && own_term) s->t_ring[phase] = t_own;
+        }
+    }
+    __syncthreads();
+    const double prev = sh[1], rho = sh[2];
+    const int stop = sh_stop;
+    const double tmp = (prev == 0.0) ? 0.0 : rho / prev;
+#pragma unroll
+    for (int i = 0; i < R + L; ++i) {
+        if (i >= mine) continue;
+        const RowPair rp = my_rows(w + i * G, n);
+        double2 vp = ld2(p, rp);
+        if (!defers && !early) update_x(rp, vp, K);
+        if (defers && stop) update_x(rp, vp, phase);  // a deferring head that ends the solve: what is pending goes in now
+        if (stop) continue;
+        double2 vz;
+        if (i < R) {
+            vz = zr[i < R ? i : 0];
+        } else {
+            vz.x = zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx];
+            vz.y = zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx + 1];
+        }
+        vp.x = vz.x + tmp * vp.x;
+        vp.y = vz.y + tmp * vp.y;
+        st2(p_out, rp, vp);
+    }
+}
+
+// Census of a resident grid: every workgroup arrives and waits, bounded, until all have.  *out = 1 when some workgroup
+// gave up (the grid does not fit the chip at once: the held-z turn must not run).  Launched with the turn kernel's LDS size.
+template <int B>
+__global__ __launch_bounds__(BLOCK, B) void k_resident_census(unsigned *arrived, int *out, long long timeout_ticks)
+{
+    extern __shared__ double census_lds[];
+    if (threadIdx.x == 0) {
+        census_lds[0] = 0.0;
+        atomicAdd(arrived, 1u);
+        const long long t0 = wall_clock64();
+        while (__hip_atomic_load(arrived, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gridDim.x) {
+            if (wall_clock64() - t0 > timeout_ticks) {
+                *out = 1;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(8);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // BiCGStab steps ([UPSTREAM] bicgstab::step_1 / step_2 / step_3 / finalize)
 // ------------------------------------------------------------------------------------------
 // step_1: p = r + (rho/prev_rho * alpha/omega) (p - omega v)   [p = r when prev_rho*omega == 0];
@@ -1530,6 +1813,51 @@ void launch_cg_step2r_fin(hipStream_t st, int32_t n, double *r, const double *q,
         hipLaunchKernelGGL((k_cg_step2r_fin<false, 1>), dim3(nc), dim3(BLOCK), 0, st, n, r, q, inv_diag, part_rho, part_norm,
                            sin, sout, part_beta, nc, z_out, LeadBox{});
 }
+
+// The held-z turn's geometry: B workgroups per CU, z of R chunks in registers and of L in LDS per workgroup (116 / 118 of
+// 128 VGPRs, 36.5 of 40 KB of LDS, no scratch: DESIGN.md section 4.2 has the compiler's figures; a tenth chunk of LDS does
+// not fit, and 15 chunks in registers -- 5 in LDS next to a stage for the leaders -- spilled two registers)
+constexpr int HZ_B = 4, HZ_R = 11, HZ_L = 9;
+#define OGL_HELD_Z(K) k_cg_step2r1x<HZ_R, HZ_L, HZ_B, K>
+
+int held_z_grid(int *chunks_per_workgroup)
+{
+    *chunks_per_workgroup = HZ_R + HZ_L;
+    int dev = 0, per_cu[2] = {0, 0};
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[0], OGL_HELD_Z(0), BLOCK, 0) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[1], OGL_HELD_Z(2), BLOCK, 0) != hipSuccess)
+        return 0;
+    // (never more than B per CU, whatever the runtime would admit: the capacity is the committed geometry's)
+    return prop.multiProcessorCount * std::min(HZ_B, std::min(per_cu[0], per_cu[1]));
+}
+
+int launch_resident_census(hipStream_t st, int grid, unsigned *arrived, int *out, long long timeout_ticks)
+{
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(OGL_HELD_Z(2))) != hipSuccess) return 1;
+    if (hipMemsetAsync(arrived, 0, sizeof(unsigned), st) != hipSuccess || hipMemsetAsync(out, 0, sizeof(int), st) != hipSuccess)
+        return 1;
+    hipLaunchKernelGGL((k_resident_census<HZ_B>), dim3(grid), dim3(BLOCK), fa.sharedSizeBytes, st, arrived, out,
+                       timeout_ticks);
+    return 0;
+}
+
+void launch_cg_step2r1x(hipStream_t st, int32_t n, double *r, const double *q, const double *inv_diag, double *p,
+                        double *p_out, double *x, DevScalars *s, const double *part_beta, double *history,
+                        const LeadBox &lead, const PRing &ring, const HeldZ &hz)
+{
+    const int nc = (int)n_chunks(n);
+    if (nc == 0) return;
+    if (ring.k == 2)
+        hipLaunchKernelGGL((OGL_HELD_Z(2)), dim3(hz.grid), dim3(BLOCK), 0, st, n, r, q, inv_diag, p, p_out, x, s, part_beta,
+                           hz.tagged, nc, history, lead, ring.b[1], ring.phase, hz.x_early);
+    else
+        hipLaunchKernelGGL((OGL_HELD_Z(0)), dim3(hz.grid), dim3(BLOCK), 0, st, n, r, q, inv_diag, p, p, x, s, part_beta,
+                           hz.tagged, nc, history, lead, nullptr, 0, hz.x_early);
+}
+#undef OGL_HELD_Z
 
 void launch_cg_step2(hipStream_t st, int32_t n, double *x, double *r, const double *p,
                      const double *q, const double *inv_diag, double *part_rho, double *part_norm,

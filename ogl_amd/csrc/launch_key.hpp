@@ -63,6 +63,8 @@ inline void visit(KeyHasher &h, const DevSymx &a)
 }
 OGL_VIEW_FIELDS(LeadBox, 24);
 inline void visit(KeyHasher &h, const LeadBox &a) { h(a.box), h(a.timeout_ticks), h(a.early_loads); }
+OGL_VIEW_FIELDS(HeldZ, 16);
+inline void visit(KeyHasher &h, const HeldZ &a) { h(a.tagged), h(a.grid), h(a.x_early); }
 
 #undef OGL_VIEW_FIELDS
 

@@ -249,6 +249,7 @@ ogl_solver::~ogl_solver()
     drop_cg_graph();
     ledger::pinned_free(h_scal);
     ledger::dev_free(lead_box);
+    ledger::dev_free(held_z_box);
     for (auto &e : poll_ev)
         if (e) ev_destroy(e);
     for (auto &e : prof_ev)

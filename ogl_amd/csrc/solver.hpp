@@ -270,6 +270,11 @@ struct ogl_solver {
     ogl::DevScalars *h_scal = nullptr;  // pinned, 2 slots
     hipEvent_t poll_ev[2] = {nullptr, nullptr};
     unsigned long long *lead_box = nullptr;  // LeadBox of the leader finalisation (fine-grained, LEAD_BOX_WORDS words)
+    // the held-z turn (k_cg_step2r1x): the chunks' tagged partials (fine-grained, 4 words per chunk) and what the census of
+    // its resident grid said (0: not run yet, 1: all workgroups on the chip at once, -1: not -- the three-launch turn runs)
+    unsigned long long *held_z_box = nullptr;
+    size_t held_z_words = 0;
+    int held_z_census = 0, held_z_census_grid = 0;
     hipEvent_t chk_ev[2] = {nullptr, nullptr};  // brackets one evaluated criterion check per solve (time_for_res_norm_eval)
     bool x_resident = false, b_resident = false;
     ogl::PrecondData own_precond;              // regenerated-for-this-solve preconditioner
@@ -324,6 +329,8 @@ struct ogl_solver {
     int turn_cg_generic_led(KrylovRun &k, int enq, int pe);
     int turn_cg_two_launch(KrylovRun &k, int enq, int pe);
     int turn_cg_three_launch(KrylovRun &k, int enq, int pe);
+    int turn_cg_held_z(KrylovRun &k, int enq, int pe);
+    int plan_held_z(KrylovRun &k);
     int turn_cg_merged(KrylovRun &k, int enq, int pe);
     int turn_cg_five_launch(KrylovRun &k, int enq, int pe);
     int turn_bicg_folded(KrylovRun &k, int enq, int pe);

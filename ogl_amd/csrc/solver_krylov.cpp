@@ -212,6 +212,8 @@ struct ogl_solver::KrylovRun {
     double *y = nullptr, *z = nullptr;  // BiCGStab: identity preconditioner -> y aliases p, z aliases s
     int enq = 0;                        // turns enqueued so far
     double *gm_h(int i, int j) const { return gm + (size_t)j * (m + 1) + i; }
+    HeldZ hz{};  // the held-z turn: SpMV | k_cg_step2r1x (hz.grid == 0: the three-launch turn)
+    bool held_z() const { return hz.grid > 0; }
     PRing ring{};  // three-launch leader turn with ring.k p buffers: x touched every ring.k-th turn (k_cg_step1x_fin)
     double *p_of_turn(int turn) const  // p that turn `turn` reads
     {
@@ -372,6 +374,7 @@ int ogl_solver::krylov_prepare(KrylovRun &k)
     for (int i = 0; i < ring_k; ++i) k.ring.b[i] = i == 0 ? d_p.p : i == 1 ? d_p2.p : d_pring[i - 2].p;
     k.ph = d_p_halo.p;
     k.z_kept = merged && precond ? d_z.p : nullptr;
+    OGL_TRY(plan_held_z(k));
 
     // StoppingCriterion ctor + build_dist_stopping_criterion (StoppingCriterion.H:164-234)
     k.is_final = cfg.rel_tol == 0.0;  // get_is_final, :242
@@ -683,6 +686,88 @@ int ogl_solver::turn_cg_three_launch(KrylovRun &k, int enq, int pe)
     return OGL_OK;
 }
 
+// The held-z turn, 2 launches: SpMV | [beta + step_2r + check + pending x update + step_1 of the NEXT turn] in one resident
+// kernel that keeps z = r / d on chip (k_cg_step2r1x); the first head is the stand-alone one.  The scalars: s -> s2 by the
+// first head, s2 in place from then on.
+int ogl_solver::turn_cg_held_z(KrylovRun &k, int enq, int pe)
+{
+    hipStream_t st = k.st;
+    const int n = k.n;
+    double *p_new = k.p_of_turn(enq + 1);
+    if (enq == 0) {
+        OGL_HIP_CHECK(hipEventRecord(k.ev_chk[0], st));
+        launch_cg_step1x_fin(st, n, k.p_of_turn(0), d_x.p, d_r.p, precond, k.s, k.s2, d_part0.p, d_part1.p, d_history.p, 1,
+                             k.lead, p_new, k.ring_of_turn(0));
+        OGL_HIP_CHECK(hipEventRecord(k.ev_chk[1], st));
+    }
+    if (pe >= 0) OGL_HIP_CHECK(hipEventRecord(prof_ev[2 * pe], st));
+    OGL_TRY(dist_spmv(SPMV_PLAIN, p_new, nullptr, d_q.p, SpmvDots{p_new, d_part2.p, nullptr}, k.s2));
+    if (pe >= 0) OGL_HIP_CHECK(hipEventRecord(prof_ev[2 * pe + 1], st));
+    // (the head in here is turn enq + 1's: it reads the p the SpMV above has used and writes the next one)
+    launch_cg_step2r1x(st, n, d_r.p, d_q.p, precond, p_new, k.p_of_turn(enq + 2), d_x.p, k.s2, d_part2.p, d_history.p, k.lead,
+                       k.ring_of_turn(enq + 1), k.hz);
+    return OGL_OK;
+}
+
+// Whether this solve runs the held-z turn: the leader turn of three launches (scalar Jacobi or none, one rank, p in place
+// or two p buffers), by default where it streams (property heldZ), within what the resident grid holds on chip
+// (heldZMaxChunks can only lower that) and only after a census launch has seen the whole grid on the chip at once.
+int ogl_solver::plan_held_z(KrylovRun &k)
+{
+    k.hz = HeldZ{};
+    props["heldZInUse"] = 0.0;
+    if (!(k.lead.box != nullptr && k.fused && !k.fused2 && !k.generic && !k.multi && (k.ring.k == 0 || k.ring.k == 2)))
+        return OGL_OK;
+    bool streams = false;
+    switch (spmv_layout) {
+    case SpmvLayout::Ell: streams = ell().stream; break;
+    case SpmvLayout::Sell: streams = sell().stream; break;
+    case SpmvLayout::Sym: streams = sym().stream; break;
+    case SpmvLayout::Symx: streams = symx().stream; break;
+    default: streams = csr().stream; break;
+    }
+    if (prop("heldZ", streams ? 1.0 : 0.0) == 0.0 || held_z_census < 0) return OGL_OK;
+    int per_wg = 0;
+    int grid = held_z_grid(&per_wg);
+    grid = std::min(grid, (int)prop("heldZGrid", (double)grid));  // (only ever fewer workgroups: tests reach LDS-held chunks with it)
+    if (grid < 2 * 16) return OGL_OK;  // (the 2 x 16 leaders of the sums)
+    const double cap = std::min((double)grid * per_wg, prop("heldZMaxChunks", (double)grid * per_wg));
+    if ((double)k.nc > cap) return OGL_OK;
+    hipStream_t st = k.st;
+    const size_t words = 4 * (size_t)k.nc;
+    if (!held_z_box || held_z_words < words) {
+        ledger::dev_free(held_z_box);
+        held_z_box = nullptr;
+        void *b = nullptr;
+        OGL_HIP_CHECK(ledger::dev_malloc(&b, words * sizeof(unsigned long long), /*fine_grained=*/true));
+        held_z_box = static_cast<unsigned long long *>(b);
+        held_z_words = words;
+    }
+    // (tags restart with every solve: no word of an earlier solve may survive)
+    OGL_HIP_CHECK(hipMemsetAsync(held_z_box, 0, held_z_words * sizeof(unsigned long long), st));
+    if (held_z_census == 0 || held_z_census_grid < grid) {
+        void *c = nullptr;
+        OGL_HIP_CHECK(ledger::dev_malloc(&c, 2 * sizeof(int)));
+        int timed_out = 1;
+        // (a census that cannot see everybody within a second has its answer)
+        const int rc = launch_resident_census(st, grid, static_cast<unsigned *>(c), static_cast<int *>(c) + 1,
+                                              (long long)(prop("heldZCensusS", 1.0) * 1e8));
+        hipError_t e = rc == 0 ? hipMemcpyAsync(&timed_out, static_cast<int *>(c) + 1, sizeof(int), hipMemcpyDeviceToHost, st)
+                               : hipErrorUnknown;
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        ledger::dev_free(c);
+        if (e != hipSuccess) return fail(OGL_ERR_HIP, "census of the held-z grid failed: %s", hipGetErrorString(e));
+        held_z_census = timed_out ? -1 : 1;
+        held_z_census_grid = grid;
+        if (timed_out) return OGL_OK;
+    }
+    k.hz.tagged = held_z_box;
+    k.hz.grid = grid;
+    k.hz.x_early = prop("heldZEarlyX", 1.0) != 0.0 ? 1 : 0;
+    props["heldZInUse"] = 1.0;
+    return OGL_OK;
+}
+
 // GKOCG on half storage between the single-workgroup finalisers, 4 launches: [pending x update + step_1 + SpMV] | beta |
 // step_2r (keeps z) | check; several ranks: the neighbours' step_2r has put z, p_new is formed at the halo columns here
 int ogl_solver::turn_cg_merged(KrylovRun &k, int enq, int pe)
@@ -820,6 +905,8 @@ int ogl_solver::krylov_enqueue(KrylovRun &k, int count)
             OGL_TRY(k.fused ? turn_cg_generic_led(k, enq, pe) : turn_cg_generic(k, enq, pe));
         else if (k.fused2)
             OGL_TRY(turn_cg_two_launch(k, enq, pe));
+        else if (k.held_z())
+            OGL_TRY(turn_cg_held_z(k, enq, pe));
         else if (k.fused)
             OGL_TRY(turn_cg_three_launch(k, enq, pe));
         else if (k.merged)
@@ -841,7 +928,8 @@ int ogl_solver::krylov_loop(KrylovRun &k)
     hipStream_t st = k.st;
     const bool fused = k.fused;
     auto poll_record = [&](int slot) -> int {
-        OGL_HIP_CHECK(hipMemcpyAsync(&h_scal[slot], k.bicg_fold ? k.slot_s[k.cur] : k.s, sizeof(DevScalars),
+        // (the held-z turn keeps the scalars in s2; every other folded CG turn ends with them in s)
+        OGL_HIP_CHECK(hipMemcpyAsync(&h_scal[slot], k.bicg_fold ? k.slot_s[k.cur] : (k.held_z() ? k.s2 : k.s), sizeof(DevScalars),
                                      hipMemcpyDeviceToHost, st));
         OGL_HIP_CHECK(hipEventRecord(poll_ev[slot], st));
         return OGL_OK;
@@ -886,6 +974,7 @@ int ogl_solver::krylov_loop(KrylovRun &k)
         default: break;  // (Csr, Csr21: csr() above)
         }
         visit(kh, k.lead);
+        visit(kh, k.hz);
         const uint64_t key = kh.h;
         if (!cg_graph || key != cg_graph_key) {
             if (cg_graph) {
@@ -941,7 +1030,9 @@ int ogl_solver::krylov_finish(KrylovRun &k, ogl_perf *perf)
     const int n = k.n, m = k.m;
     DevScalars *s = k.s, *s2 = k.s2;
     const bool bicg = k.bicg, gmres = k.gmres, fused = k.fused, bicg_fold = k.bicg_fold;
-    if (fused)  // the check that closes the last turn run so far (a plain copy s -> s2 when the solve has stopped)
+    // the check that closes the last turn run so far (a plain copy s -> s2 when the solve has stopped); the held-z turn's
+    // last kernel has run it already and left the scalars in s2
+    if (fused && !k.held_z())
         launch_cg_step1x_fin(st, n, k.p_of_turn(k.enq), d_x.p, k.generic ? d_z.p : d_r.p, k.generic ? nullptr : precond, s, s2,
                              d_part0.p, d_part1.p, d_history.p, 0, k.lead, k.p_of_turn(k.enq + 1), k.ring_of_turn(k.enq));
     if (bicg_fold) {  // the check that closes the last turn run so far (a plain copy of the scalars when the solve has stopped)
@@ -991,6 +1082,7 @@ int ogl_solver::krylov_finish(KrylovRun &k, ogl_perf *perf)
     OGL_HIP_CHECK(hipEventElapsedTime(&chk_ms, k.ev_chk[0], k.ev_chk[1]));
 
     // where the multi-rank turns of this solve waited (DevScalars, kernels.hpp; wall_clock64 counts 10 ns)
+    props["turnsEnqueued"] = (double)k.enq;  // (the host looks at the stop flag one batch late: at most two batches past the stop)
     props["haloWaits"] = (double)fin.halo_waits;
     props["haloWaitUs"] = (double)fin.halo_wait_ticks / 100.0;
     props["allreduceWaits"] = (double)fin.reduce_waits;

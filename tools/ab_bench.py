@@ -4,6 +4,10 @@ and with another one (e.g. tools/bin/libogl_amd_<commit>.so built from an earlie
 the in-loop SpMV time and the turn rate of every run.  Development tool.
 
   python tools/ab_bench.py tools/bin/libogl_amd_2c97ef6.so [rounds] [bench.py flags ...]
+
+Every run is a child process with a time limit of its own (OGL_AB_TIMEOUT_S, 300 s by default).  The first run that
+fails -- a non-zero exit, a time-out, no result line -- ends the whole A/B with exit status 1: nothing more is started on
+a device that a run may have left in a bad state.
 """
 import json
 import os
@@ -14,17 +18,26 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 other = os.path.abspath(sys.argv[1])
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 flags = sys.argv[3:]
+limit = float(os.environ.get("OGL_AB_TIMEOUT_S", "300"))
 runner = ("import sys, runpy; sys.path.insert(0, %r); from ogl_amd import capi; capi.LIB_PATH = sys.argv[1]; "
           "sys.argv = ['bench.py'] + sys.argv[2:]; runpy.run_path(%r, run_name='__main__')"
           % (ROOT, os.path.join(ROOT, "bench.py")))
 libs = [("in-tree", os.path.join(ROOT, "ogl_amd", "lib", "libogl_amd.so")), (os.path.basename(other), other)]
 for r in range(rounds):
     for name, lib in libs:
-        p = subprocess.run([sys.executable, "-c", runner, lib, "--steps", "3", "--warmup", "1", "--cpu-iters", "0", "--no-general-legs", *flags],
-                           cwd=ROOT, capture_output=True, text=True)
+        cmd = [sys.executable, "-c", runner, lib, "--steps", "3", "--warmup", "1", "--cpu-iters", "0", "--no-general-legs", *flags]
+        try:
+            p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=limit)
+        except subprocess.TimeoutExpired:
+            print("round %d %-28s TIMED OUT after %g s: stopping" % (r, name, limit), flush=True)
+            sys.exit(1)
+        if p.returncode != 0:
+            print("round %d %-28s FAILED with exit status %d: stopping\n%s" % (r, name, p.returncode, p.stderr[-800:]), flush=True)
+            sys.exit(1)
         try:
             d = json.loads(p.stdout.strip().splitlines()[-1])
             print("round %d %-28s %8.1f it/s  spmv %6.1f us  layout %s" % (
                 r, name, d["value"], 1e3 * d["roofline"]["avg_kernel_ms"], d["roofline"]["layout"]), flush=True)
         except Exception as e:
-            print("round %d %-28s FAILED %s\n%s" % (r, name, e, p.stderr[-800:]), flush=True)
+            print("round %d %-28s NO RESULT LINE (%s): stopping\n%s" % (r, name, e, p.stderr[-800:]), flush=True)
+            sys.exit(1)
