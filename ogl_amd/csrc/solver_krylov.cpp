@@ -716,6 +716,7 @@ int ogl_solver::plan_held_z(KrylovRun &k)
 {
     k.hz = HeldZ{};
     props["heldZInUse"] = 0.0;
+    props["heldZGridInUse"] = 0.0;  // (the workgroups the turn launches: whether heldZGrid was honoured or clipped by the device)
     if (!(k.lead.box != nullptr && k.fused && !k.fused2 && !k.generic && !k.multi && (k.ring.k == 0 || k.ring.k == 2)))
         return OGL_OK;
     bool streams = false;
@@ -765,6 +766,7 @@ int ogl_solver::plan_held_z(KrylovRun &k)
     k.hz.grid = grid;
     k.hz.x_early = prop("heldZEarlyX", 1.0) != 0.0 ? 1 : 0;
     props["heldZInUse"] = 1.0;
+    props["heldZGridInUse"] = (double)grid;
     return OGL_OK;
 }
 

@@ -7,6 +7,8 @@ plus a stated bound against the oracle in the reference executor's left-to-right
       batches of 8,192, device_common.hpp reduce_partials)
   (b) GKOCG + BJ and GKOCG (none) at 216^3, 30 turns: matrix, history, x, norm factor, iteration count
       (the STREAM instantiation of the half-storage SpMV with the band-aware workgroup order, inside a solve)
+      on the held-z turn, which these sizes run by default (asserted: heldZInUse, heldZGridInUse), and one 216^3 solve
+      stopped by its tolerance at evalFrequency 3, against the three-launch turn
   (c) 136^3 (one rank's share of configs[3]) with the merged step_1x + SpMV kernel ON BY DEFAULT, and 100^3
       (rows not a multiple of the chunk: the clamped tail gathers); 128^3 non-symmetric GKOBiCGStab + BJ
   (d) the first restart cycle of GKOGMRES(30) + BJ at 184^3 with shuffled cells (one rank's share of configs[4]),
@@ -49,6 +51,12 @@ def reg():
 @pytest.fixture(scope="module")
 def chunk_rows():
     return capi.lib().ogl_reduction_chunk_rows()
+
+
+def resident_grid():
+    """Four workgroups per compute unit: the grid of the held-z turn when nothing lowers it (1,024 on MI355X)."""
+    import torch
+    return 4.0 * torch.cuda.get_device_properties(0).multi_processor_count
 
 
 def cfg(**kw):
@@ -105,9 +113,12 @@ def test_cg_216_history_bit_equal(reg, oracle, chunk_rows, big, precond):
     x, perf = s.solve(b, np.zeros_like(b))
     hist = s.history()
     # every default left alone: the half storage, its STREAM instantiation (matrix + vectors exceed the Infinity
-    # Cache) and the five-launch turn -- what bench.py times
+    # Cache) and the held-z turn of two launches (SpMV | k_cg_step2r1x) on the device's full resident grid, every
+    # workgroup of it with 19 or 20 chunks -- what bench.py times
     assert s.get_property("symmetricHalf") == 1.0 and s.get_property("symmetricHalfPerChunk") == 0.0
     assert s.get_property("fusedTurnInUse") == 0.0 and s.get_property("fusedFinalizersInUse") == 0.0
+    assert s.get_property("leadFinalizersInUse") == 1.0
+    assert s.get_property("heldZInUse") == 1.0 and s.get_property("heldZGridInUse") == resident_grid()
     inv = oracle.jacobi_generate_scalar(rp, cols, vals) if precond else None
     kw = dict(tolerance=0.0, rel_tol=0.0, max_iter=TURNS)
     with blocked(oracle, chunk_rows):
@@ -127,13 +138,46 @@ def test_cg_216_history_bit_equal(reg, oracle, chunk_rows, big, precond):
     assert rel_dev(perf.norm_factor, seq.norm_factor) <= 1e-12
 
 
+def test_cg_216_stops_by_tolerance_on_the_held_z_turn(reg, big):
+    """The only tests at full load stop by max_iter: here the criterion inside k_cg_step2r1x ends a 216^3 solve by its
+    tolerance, at evalFrequency 3, with 19 or 20 chunks in every workgroup -- against the three-launch turn (heldZ 0); the
+    oracle would need minutes for this many turns at 10 M rows.  The tolerance is a value of the history itself: this
+    history rises above its first value and stays there for more than 45 turns, so a residual of turn 20 would stop the
+    solve at turn 0; it is the first record low from turn 20 on (of a probe run without tolerance), which puts the stop
+    inside the run by construction."""
+    case, A, (rp, cols, vals), b = big
+    probe = reg.solver("p_tol_off", cfg(max_iter=300)).set_matrix(case)
+    probe.set_property("heldZ", 0.0)
+    probe.upload_solution(None)
+    probe.solve(b, np.zeros_like(b))
+    h = probe.history()
+    k = next(k for k in range(20, h.size) if h[k] < h[:k].min())
+    out = {}
+    for held, name in ((1.0, "p_tol_on"), (0.0, "p_tol_off")):
+        s = reg.solver(name, cfg(tolerance=float(h[k]), max_iter=600, eval_frequency=3)).set_matrix(case)
+        s.set_property("heldZ", held)
+        s.upload_solution(None)
+        x, perf = s.solve(b, np.zeros_like(b))
+        assert s.get_property("heldZInUse") == held and s.get_property("leadFinalizersInUse") == 1.0
+        assert s.get_property("heldZGridInUse") == (resident_grid() if held else 0.0)
+        out[held] = (x, perf.n_iterations, s.history().copy(), perf.final_residual, perf.n_norm_evals)
+    on, off = out[1.0], out[0.0]
+    print(f"216^3: tolerance {h[k]:.6e} = the residual of turn {k}, stop after {on[1]} checks")
+    assert k < on[1] < 600 and on[1] % 3 == 1 and on[3] < h[k]
+    assert on[1] == off[1] and on[3] == off[3] and on[4] == off[4]
+    np.testing.assert_array_equal(on[2], off[2])
+    np.testing.assert_array_equal(on[0], off[0])
+
+
 # ------------------------------------------------------------------------------------------ (c)
 
 @pytest.mark.parametrize("edge,merged", [(136, True), (100, True), (160, False)])
 def test_cg_default_turn_kernels_bit_equal(reg, oracle, chunk_rows, edge, merged):
     """136^3 = one rank's share of configs[3]: the merged step_1x + SpMV kernel (k_cg_turn_sym_big) is what runs by
     default while matrix + vectors fit the Infinity Cache.  100^3: 1,000,000 rows = 1953 chunks + 64 rows (the tail
-    lanes of the last chunk gather at clamped indices).  160^3: the merged kernel stands down (streamed)."""
+    lanes of the last chunk gather at clamped indices).  160^3: the merged kernel stands down (streamed) and the held-z
+    turn takes over by default, on the full resident grid (8,000 chunks: 7 or 8 per workgroup, registers only); at the
+    cache-resident sizes it stays off."""
     case = synthetic.poisson_case(edge)
     s = reg.solver(f"c{edge}", cfg()).set_matrix(case)
     A, (rp, cols, vals) = oracle_matrix(oracle, case)
@@ -141,6 +185,8 @@ def test_cg_default_turn_kernels_bit_equal(reg, oracle, chunk_rows, edge, merged
     x, perf = s.solve(b, np.zeros_like(b))
     assert s.get_property("fusedTurnInUse") == (1.0 if merged else 0.0)
     assert s.get_property("fusedFinalizersInUse") == 0.0
+    assert s.get_property("heldZInUse") == (0.0 if merged else 1.0)
+    assert s.get_property("heldZGridInUse") == (0.0 if merged else resident_grid())
     inv = oracle.jacobi_generate_scalar(rp, cols, vals)
     with blocked(oracle, chunk_rows):
         ref = oracle.cg(A, b, np.zeros_like(b), inv, tolerance=0.0, rel_tol=0.0, max_iter=TURNS)
