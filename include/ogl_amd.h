@@ -61,7 +61,11 @@ typedef enum {
     OGL_PRECOND_GISAI = 3, /* Preconditioner.H:242-258  isai_type::general (M^-1 = W)              */
     OGL_PRECOND_IC = 4,    /* Preconditioner.H:106-126  factorization::Ic, A ~ L L^T, exact solves   */
     OGL_PRECOND_ILU = 5,   /* Preconditioner.H:106-126  factorization::Ilu, A ~ L U, exact solves    */
-    OGL_PRECOND_IRILU = 6  /* Preconditioner.H:147-178  the ILU factors, 5 Richardson sweeps each    */
+    OGL_PRECOND_IRILU = 6, /* Preconditioner.H:147-178  the ILU factors, 5 Richardson sweeps each    */
+    /* Preconditioner.H:259-341  aggregation AMG (Pgm + Multigrid), one V-cycle per apply.  Its keywords travel as
+     * properties: maxLevels (9), minCoarseRows (10), coarseSolverIters (4), cycle (0 = v; 1 = w and 2 = f are refused),
+     * zeroGuess (1; 0 is refused). */
+    OGL_PRECOND_MULTIGRID = 7
 } ogl_precond_kind;
 
 typedef enum { OGL_FORMAT_COO = 0, OGL_FORMAT_CSR = 1, OGL_FORMAT_ELL = 2 } ogl_matrix_format;
@@ -338,6 +342,14 @@ int ogl_solver_spmv(ogl_solver *s, const ogl_scalar *x, ogl_scalar *y);
 /* z = M^-1 r with the preconditioner of the last solve (r, z: host vectors of n_rows in the caller's cell order; the
  * local operator only).  OGL_ERR_STATE before the first solve. */
 int ogl_solver_apply_preconditioner(ogl_solver *s, const ogl_scalar *r, ogl_scalar *z);
+/* preconditioner Multigrid: the hierarchy of the last solve, level 0 = the local system matrix (property mgLevels = the
+ * number of levels).  dims: rows and entries of a level.  get: its CSR arrays (rows + 1, nnz, nnz entries) and, for every
+ * level but the coarsest, agg[rows] = the coarse row each row belongs to; NULL arguments are skipped.  OGL_ERR_STATE when
+ * the hierarchy is not current (as ogl_solver_apply_preconditioner), OGL_ERR_INVALID for a level that does not exist or
+ * agg of the coarsest level. */
+int ogl_solver_mg_level_dims(ogl_solver *s, int32_t level, ogl_label *rows, ogl_label *nnz);
+int ogl_solver_get_mg_level(ogl_solver *s, int32_t level, ogl_label *row_ptrs, ogl_label *cols, ogl_scalar *vals,
+                            ogl_label *agg);
 /* `repeats` back-to-back in-loop SpMVs (fused with the p.q dot, as in the CG loop) on resident
  * vectors, timed with HIP events on the solver's stream; avg_ms = per launch. */
 int ogl_solver_time_spmv(ogl_solver *s, int32_t repeats, double *avg_ms);

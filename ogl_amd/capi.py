@@ -18,6 +18,10 @@ ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_COMM, ERR_STATE, ERR_UNSUPPORTED, ERR_C
 SOLVER_CG, SOLVER_BICGSTAB, SOLVER_GMRES = 0, 1, 2
 PRECOND_NONE, PRECOND_BJ, PRECOND_ISAI, PRECOND_GISAI = 0, 1, 2, 3
 PRECOND_IC, PRECOND_ILU, PRECOND_IRILU = 4, 5, 6
+PRECOND_MULTIGRID = 7
+# keywords of the Multigrid sub-dictionary (Preconditioner.H:297-317): they travel as properties; cycle as a number
+MG_KEYWORDS = ("maxLevels", "minCoarseRows", "coarseSolverIters", "cycle", "zeroGuess")
+MG_CYCLE = {"v": 0, "w": 1, "f": 2}
 FORMAT_COO, FORMAT_CSR, FORMAT_ELL = 0, 1, 2
 RENUMBER_OFF, RENUMBER_ON, RENUMBER_AUTO = 0, 1, 2
 IFACE_PROCESSOR, IFACE_CYCLIC = 0, 1
@@ -88,6 +92,7 @@ EXPORTED_SYMBOLS = [
     "ogl_solver_get_property",
     "ogl_solver_set_property", "ogl_solver_apply_resident", "ogl_solver_upload_solution",
     "ogl_solver_upload_rhs", "ogl_solver_download_solution", "ogl_solver_spmv", "ogl_solver_apply_preconditioner",
+    "ogl_solver_mg_level_dims", "ogl_solver_get_mg_level",
     "ogl_solver_time_spmv", "ogl_solver_reduce", "ogl_reduction_chunk_rows",
     "ogl_solver_matrix_dims", "ogl_solver_get_local_matrix", "ogl_solver_get_non_local_matrix",
     "ogl_solver_get_comm_pattern", "ogl_host_init_local_sparsity", "ogl_host_symmetric_update",
@@ -362,6 +367,28 @@ class Solver:
         z = np.zeros_like(r)
         _check(lib().ogl_solver_apply_preconditioner(self._h, _ps(r), _ps(z)))
         return z
+
+    def set_multigrid(self, **kw):
+        """The Multigrid keywords (MG_KEYWORDS; cycle as 'v' | 'w' | 'f', zeroGuess as a bool) for the next solves."""
+        for k, v in kw.items():
+            if k not in MG_KEYWORDS:
+                raise KeyError(k)
+            self.set_property(k, float(MG_CYCLE[v] if k == "cycle" else v))
+        return self
+
+    def mg_level(self, level):
+        """(row_ptrs, cols, vals, agg) of level `level` of the Multigrid hierarchy of the last solve; agg (fine-to-coarse
+        map) is None on the coarsest level."""
+        rows, nnz = C.c_int32(), C.c_int32()
+        _check(lib().ogl_solver_mg_level_dims(self._h, level, C.byref(rows), C.byref(nnz)))
+        rp = np.zeros(rows.value + 1, np.int32)
+        cols = np.zeros(nnz.value, np.int32)
+        vals = np.zeros(nnz.value, np.float64)
+        last = level == int(self.get_property("mgLevels")) - 1
+        agg = None if last else np.zeros(rows.value, np.int32)
+        _check(lib().ogl_solver_get_mg_level(self._h, level, _pl(rp), _pl(cols), _ps(vals),
+                                             None if last else _pl(agg)))
+        return rp, cols, vals, agg
 
     def time_spmv(self, repeats):
         ms = C.c_double()

@@ -338,6 +338,77 @@ void launch_factor_gather_perm(hipStream_t st, int32_t n, const int32_t *new_id,
 void launch_factor_scatter_perm(hipStream_t st, int32_t n, const int32_t *new_id, const double *in, double *out,
                                 const DevScalars *gate);
 
+// Multigrid (kernels_mg.hip; Preconditioner.H:259-341): an aggregation hierarchy generated on the device and the kernels
+// of its V-cycle.  The contract is spelled out in DESIGN.md section 7b.
+struct MgCsr {  // one matrix of the hierarchy: columns ascending per row
+    int32_t n = 0, nnz = 0;
+    const int32_t *row_ptrs = nullptr, *cols = nullptr;
+    const double *vals = nullptr;
+};
+constexpr double MG_OMEGA = 0.9;  // the smoother's relaxation factor
+constexpr int MG_ROUNDS = 15;     // matching rounds per coarsening
+struct MgScalars {                // the coarsest level's CG
+    double rho, prev_rho, beta;
+};
+// the tail of the hierarchy as ONE single-workgroup kernel: levels first .. last of the V-cycle (the last one is the
+// coarsest), walked down, solved and walked up with barriers between the phases.  b: right-hand side of the first of
+// them, x: its answer; the levels' own vectors hold everything in between.
+struct MgTailLevel {
+    int32_t n = 0, n_coarse = 0;
+    const int32_t *row_ptrs = nullptr, *cols = nullptr, *agg = nullptr, *agg_ptr = nullptr, *agg_rows = nullptr;
+    const double *vals = nullptr, *inv_d = nullptr;
+    double *b = nullptr, *xa = nullptr, *xb = nullptr, *t = nullptr, *r = nullptr, *p = nullptr, *part = nullptr;
+};
+constexpr int MG_TAIL_MAX_LEVELS = 16;
+constexpr int MG_TAIL_DEFAULT_ROWS = 512;  // property mgTailRows
+constexpr int MG_TAIL_MAX_ROWS = 1024 * 512;  // (the finaliser's tree inside the workgroup: one partial per virtual thread)
+struct MgTail {
+    int32_t count = 0, cg_iters = 0;
+    MgTailLevel lev[MG_TAIL_MAX_LEVELS];
+};
+void launch_mg_tail(hipStream_t st, const MgTail &T, const double *b, double *x, const DevScalars *gate);
+// generation: diag[i] = A(i, i), inv_d[i] = 1 / A(i, i)
+void launch_mg_diag(hipStream_t st, const MgCsr &A, double *diag, double *inv_d);
+// s[i] = strongest unaggregated (want 0) / aggregated (want 1) neighbour of the unaggregated row i (-1 none, -2 row aggregated)
+void launch_mg_strongest(hipStream_t st, const MgCsr &A, const double *diag, const int32_t *agg, int want, int32_t *s);
+// mutual pairs become aggregates; *left += rows still unaggregated
+void launch_mg_match(hipStream_t st, int32_t n, const int32_t *s, int32_t *agg, int32_t *left);
+void launch_mg_join(hipStream_t st, int32_t n, const int32_t *s, int32_t *agg);
+void launch_mg_root_flag(hipStream_t st, int32_t n, const int32_t *agg, int32_t *flag);
+void launch_mg_coarse_index(hipStream_t st, int32_t n, const int32_t *agg, const int32_t *incl, int32_t *cidx, int32_t *rows);
+void launch_mg_member_ptr(hipStream_t st, int32_t n, int32_t nc, const int32_t *sorted, int32_t *agg_ptr);
+void launch_mg_keys(hipStream_t st, const MgCsr &A, const int32_t *cidx, unsigned long long *keys);
+void launch_mg_head_flag(hipStream_t st, int32_t m, const unsigned long long *keys, int32_t *flag);
+void launch_mg_compact(hipStream_t st, int32_t m, int32_t nc, const unsigned long long *keys, const double *vals,
+                       const int32_t *pos, int32_t *row_ptrs, int32_t *cols, double *out);
+// scan and stable radix sorts (hipcub); mg_temp_bytes: scratch that serves all three on a level of n rows, nnz entries
+size_t mg_temp_bytes(int32_t n, int32_t nnz);
+hipError_t mg_inclusive_sum(hipStream_t st, void *temp, size_t temp_bytes, const int32_t *in, int32_t *out, int32_t n);
+hipError_t mg_sort_rows(hipStream_t st, void *temp, size_t temp_bytes, const int32_t *keys, int32_t *keys_out,
+                        const int32_t *rows, int32_t *rows_out, int32_t n);
+hipError_t mg_sort_entries(hipStream_t st, void *temp, size_t temp_bytes, const unsigned long long *keys,
+                           unsigned long long *keys_out, const double *vals, double *vals_out, int32_t m);
+// apply: x = omega (b inv_d) | x_out = x + omega ((b - ax) inv_d) | x_out = x + xc[agg]
+void launch_mg_jacobi0(hipStream_t st, int32_t n, const double *b, const double *inv_d, double *x, const DevScalars *gate);
+void launch_mg_sweep_epi(hipStream_t st, int32_t n, const double *b, const double *ax, const double *inv_d, const double *x,
+                         double *x_out, const DevScalars *gate);
+void launch_mg_prolong(hipStream_t st, int32_t n, const double *x, const double *xc, const int32_t *agg, double *x_out,
+                       const DevScalars *gate);
+// one sweep on a CSR level (x_out != x); xc != nullptr: on t = x + xc[agg], the prolongation folded in
+void launch_mg_csr_sweep(hipStream_t st, const MgCsr &A, const double *inv_d, const double *b, const double *x,
+                         const double *xc, const int32_t *agg, double *x_out, const DevScalars *gate);
+void launch_mg_csr_spmv(hipStream_t st, const MgCsr &A, const double *x, double *y, const DevScalars *gate);
+// bc[I] = sum of b_i - (A x)_i over the members of I, ascending; ax != nullptr: the products are there already
+void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsr &A,
+                        const double *b, const double *x, const double *ax, double *bc, const DevScalars *gate);
+void launch_mg_cg_init(hipStream_t st, int32_t n, const double *b, double *r, double *x, double *p, const DevScalars *gate);
+// what 0: prev_rho <- rho (1 when first), rho <- sum(part); 1: beta <- sum(part) -- in the finaliser's tree
+void launch_mg_cg_fin(hipStream_t st, const double *part, int32_t n_part, int what, int first, MgScalars *s,
+                      const DevScalars *gate);
+void launch_mg_cg_step1(hipStream_t st, int32_t n, double *p, const double *r, const MgScalars *s, const DevScalars *gate);
+void launch_mg_cg_step2(hipStream_t st, int32_t n, double *x, double *r, const double *p, const double *q,
+                        const MgScalars *s, const DevScalars *gate);
+
 // renumbering (keyword `renumber`): host vectors arrive in the caller's cell order
 //   scatter: out[new_id[i]] = in[i]   (b, x on upload)      gather: out[i] = in[new_id[i]]   (x on copy-back)
 void launch_permute_scatter(hipStream_t st, int32_t n, const int32_t *new_id, const double *in, double *out);

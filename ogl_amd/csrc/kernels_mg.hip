@@ -1,0 +1,578 @@
+// kernels_mg.hip -- the Multigrid preconditioner (Preconditioner.H:259-341): generation of an aggregation hierarchy on
+// the device and the kernels of one V-cycle.  The contract is this build's restatement of
+// [UPSTREAM] Ginkgo's Pgm(deterministic) + Multigrid; everything is fp64, products and sums round separately, and no
+// kernel uses an atomic on a value: the result does not depend on scheduling.
+//
+// A repeated column of a row (cyclic patches) counts as ONE entry whose value is the sum of the repeats in stored order
+// (run_sum); the coarse matrices have one entry per column.
+#include <hipcub/hipcub.hpp>
+
+#include "device_common.hpp"
+
+namespace ogl {
+
+namespace {
+
+constexpr int MG_BLOCK = 256;
+inline int mg_grid(int64_t n) { return (int)((n + MG_BLOCK - 1) / MG_BLOCK); }
+
+// value of the entry that starts at position k of a row ending at `end`, repeats of its column included; next = the
+// position behind them
+__device__ __forceinline__ double run_sum(const int32_t *__restrict__ cols, const double *__restrict__ vals, int k,
+                                          int end, int &next)
+{
+    const int c = cols[k];
+    double v = vals[k];
+    int e = k + 1;
+    while (e < end && cols[e] == c) {
+        v = v + vals[e];
+        ++e;
+    }
+    next = e;
+    return v;
+}
+
+// A(row, col), 0 when the pattern has no such entry (columns ascending per row)
+__device__ __forceinline__ double entry_at(const MgCsr &A, int row, int col)
+{
+    int lo = A.row_ptrs[row];
+    const int end = A.row_ptrs[row + 1];
+    int hi = end;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (A.cols[mid] < col)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    if (lo >= end || A.cols[lo] != col) return 0.0;
+    int next;
+    return run_sum(A.cols, A.vals, lo, end, next);
+}
+
+// ------------------------------------------------------------------------------------------
+// generation
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_diag(MgCsr A, double *__restrict__ diag, double *__restrict__ inv_d)
+{
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i >= A.n) return;
+    const double d = entry_at(A, i, i);
+    diag[i] = d;
+    inv_d[i] = 1.0 / d;
+}
+
+// s[i] = the neighbour of the unaggregated row i with the largest strength among the unaggregated (want == 0) or the
+// aggregated (want == 1) ones, ties to the larger column; -1: none; -2: row i is aggregated already
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_strongest(MgCsr A, const double *__restrict__ diag,
+                                                           const int32_t *__restrict__ agg, int want,
+                                                           int32_t *__restrict__ s)
+{
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i >= A.n) return;
+    if (agg[i] != -1) {
+        s[i] = -2;
+        return;
+    }
+    const double di = fabs(diag[i]);
+    double best = -1.0;
+    int bj = -1;
+    const int end = A.row_ptrs[i + 1];
+    for (int k = A.row_ptrs[i]; k < end;) {
+        const int j = A.cols[k];
+        int next;
+        const double a = run_sum(A.cols, A.vals, k, end, next);
+        k = next;
+        if (j == i || (int)(agg[j] != -1) != want) continue;
+        const double w = 0.5 * (fabs(a) + fabs(entry_at(A, j, i)));
+        const double dj = fabs(diag[j]);
+        const double st = w / (di > dj ? di : dj);
+        if (st >= best) {
+            best = st;
+            bj = j;
+        }
+    }
+    s[i] = bj;
+}
+
+// mutual pairs become aggregates rooted at the smaller row; *left += rows still unaggregated
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_match(int n, const int32_t *__restrict__ s, int32_t *__restrict__ agg,
+                                                       int32_t *left)
+{
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    int un = 0;
+    if (i < n) {
+        const int j = s[i];
+        if (j != -2) {
+            if (j >= 0 && s[j] == i)
+                agg[i] = i < j ? i : j;
+            else
+                un = 1;
+        }
+    }
+    const int c = __syncthreads_count(un);
+    if (threadIdx.x == 0 && c) atomicAdd(left, c);
+}
+
+// leftovers: join the aggregate of s[i] as the rounds left it (those rows are not written here), else a singleton root
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_join(int n, const int32_t *__restrict__ s, int32_t *agg)
+{
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int j = s[i];
+    if (j == -2) return;
+    agg[i] = j >= 0 ? agg[j] : i;
+}
+
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_root_flag(int n, const int32_t *__restrict__ agg, int32_t *__restrict__ flag)
+{
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i < n) flag[i] = agg[i] == i ? 1 : 0;
+}
+
+// cidx[i] = rank of row i's root among the roots; rows[i] = i
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_coarse_index(int n, const int32_t *__restrict__ agg,
+                                                              const int32_t *__restrict__ incl, int32_t *__restrict__ cidx,
+                                                              int32_t *__restrict__ rows)
+{
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    cidx[i] = incl[agg[i]] - 1;
+    rows[i] = i;
+}
+
+// member lists from the rows sorted (stably) by coarse index
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_member_ptr(int n, int nc, const int32_t *__restrict__ sorted,
+                                                            int32_t *__restrict__ agg_ptr)
+{
+    const int p = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    if (p == 0 || sorted[p] != sorted[p - 1]) agg_ptr[sorted[p]] = p;
+    if (p == n - 1) agg_ptr[nc] = n;
+}
+
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_keys(MgCsr A, const int32_t *__restrict__ cidx,
+                                                      unsigned long long *__restrict__ keys)
+{
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i >= A.n) return;
+    const unsigned long long hi = (unsigned long long)(uint32_t)cidx[i] << 32;
+    for (int k = A.row_ptrs[i]; k < A.row_ptrs[i + 1]; ++k) keys[k] = hi | (uint32_t)cidx[A.cols[k]];
+}
+
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_head_flag(int m, const unsigned long long *__restrict__ keys,
+                                                           int32_t *__restrict__ flag)
+{
+    const int p = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (p < m) flag[p] = (p == 0 || keys[p] != keys[p - 1]) ? 1 : 0;
+}
+
+// one coarse entry per run of equal keys, summed in sorted (= ascending (i, stored position)) order
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_compact(int m, int nc, const unsigned long long *__restrict__ keys,
+                                                         const double *__restrict__ vals, const int32_t *__restrict__ pos,
+                                                         int32_t *__restrict__ row_ptrs, int32_t *__restrict__ cols,
+                                                         double *__restrict__ out)
+{
+    const int p = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (p >= m) return;
+    if (p == m - 1) row_ptrs[nc] = pos[p];
+    const unsigned long long key = keys[p];
+    if (p > 0 && keys[p - 1] == key) return;
+    const int o = pos[p] - 1;
+    double acc = vals[p];
+    for (int q = p + 1; q < m && keys[q] == key; ++q) acc = acc + vals[q];
+    cols[o] = (int32_t)(uint32_t)key;
+    out[o] = acc;
+    const int I = (int)(key >> 32);
+    if (p == 0 || (int)(keys[p - 1] >> 32) != I) row_ptrs[I] = o;
+}
+
+// ------------------------------------------------------------------------------------------
+// apply
+// ------------------------------------------------------------------------------------------
+#define MG_GATE() \
+    if (gate && gate->stop) return
+
+// first pre-sweep, from x = 0
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_jacobi0(int n, const double *__restrict__ b, const double *__restrict__ inv_d,
+                                                         double *__restrict__ x, const DevScalars *gate)
+{
+    MG_GATE();
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i < n) x[i] = MG_OMEGA * (b[i] * inv_d[i]);
+}
+
+// the sweep behind a product ax = A x that another kernel has formed
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_sweep_epi(int n, const double *__restrict__ b, const double *__restrict__ ax,
+                                                           const double *__restrict__ inv_d, const double *__restrict__ x,
+                                                           double *__restrict__ x_out, const DevScalars *gate)
+{
+    MG_GATE();
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i < n) x_out[i] = x[i] + MG_OMEGA * ((b[i] - ax[i]) * inv_d[i]);
+}
+
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_prolong(int n, const double *__restrict__ x, const double *__restrict__ xc,
+                                                         const int32_t *__restrict__ agg, double *__restrict__ x_out,
+                                                         const DevScalars *gate)
+{
+    MG_GATE();
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i < n) x_out[i] = x[i] + xc[agg[i]];
+}
+
+// one sweep on a CSR level, x_out != x; xc != nullptr: the sweep reads t_j = x_j + xc[agg[j]] (the prolongation folded in)
+template <bool PROLONG>
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_csr_sweep(MgCsr A, const double *__restrict__ inv_d,
+                                                           const double *__restrict__ b, const double *__restrict__ x,
+                                                           const double *__restrict__ xc, const int32_t *__restrict__ agg,
+                                                           double *__restrict__ x_out, const DevScalars *gate)
+{
+    MG_GATE();
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i >= A.n) return;
+    double s = 0.0;
+    for (int k = A.row_ptrs[i]; k < A.row_ptrs[i + 1]; ++k) {
+        const int j = A.cols[k];
+        double t = x[j];
+        if (PROLONG) t = t + xc[agg[j]];
+        s += A.vals[k] * t;
+    }
+    double ti = x[i];
+    if (PROLONG) ti = ti + xc[agg[i]];
+    x_out[i] = ti + MG_OMEGA * ((b[i] - s) * inv_d[i]);
+}
+
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_csr_spmv(MgCsr A, const double *__restrict__ x, double *__restrict__ y,
+                                                          const DevScalars *gate)
+{
+    MG_GATE();
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i >= A.n) return;
+    double s = 0.0;
+    for (int k = A.row_ptrs[i]; k < A.row_ptrs[i + 1]; ++k) s += A.vals[k] * x[A.cols[k]];
+    y[i] = s;
+}
+
+// b_c[I] = sum over the members i of I, ascending, of r_i = b_i - (A x)_i; AX: the products come from `ax`
+template <bool AX>
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_restrict(int nc, const int32_t *__restrict__ agg_ptr,
+                                                          const int32_t *__restrict__ agg_rows, MgCsr A,
+                                                          const double *__restrict__ b, const double *__restrict__ x,
+                                                          const double *__restrict__ ax, double *__restrict__ bc,
+                                                          const DevScalars *gate)
+{
+    MG_GATE();
+    const int I = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (I >= nc) return;
+    double acc = 0.0;
+    for (int m = agg_ptr[I]; m < agg_ptr[I + 1]; ++m) {
+        const int i = agg_rows[m];
+        double s;
+        if (AX) {
+            s = ax[i];
+        } else {
+            s = 0.0;
+            for (int k = A.row_ptrs[i]; k < A.row_ptrs[i + 1]; ++k) s += A.vals[k] * x[A.cols[k]];
+        }
+        acc += b[i] - s;
+    }
+    bc[I] = acc;
+}
+
+// coarsest level: unpreconditioned CG from x = 0 ([UPSTREAM] cg::initialize / step_1 / step_2, guards as k_cg_step1 / 2)
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_cg_init(int n, const double *__restrict__ b, double *__restrict__ r,
+                                                         double *__restrict__ x, double *__restrict__ p,
+                                                         const DevScalars *gate)
+{
+    MG_GATE();
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    r[i] = b[i];
+    x[i] = 0.0;
+    p[i] = 0.0;
+}
+
+// the finaliser's tree over the chunk partials; what == 0: prev_rho <- rho (1 before the first), rho <- sum; 1: beta <- sum
+__global__ __launch_bounds__(FIN_BLOCK) void k_mg_cg_fin(const double *part, int n_part, int what, int first, MgScalars *s,
+                                                         const DevScalars *gate)
+{
+    __shared__ double slot[FIN_WAVES];
+    MG_GATE();
+    const double *const parts[2] = {part, part};
+    double v[2];
+    reduce_partials<1>(parts, n_part, slot, v);
+    if (threadIdx.x != 0) return;
+    if (what == 0) {
+        s->prev_rho = first ? 1.0 : s->rho;
+        s->rho = v[0];
+    } else {
+        s->beta = v[0];
+    }
+}
+
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_cg_step1(int n, double *__restrict__ p, const double *__restrict__ r,
+                                                          const MgScalars *s, const DevScalars *gate)
+{
+    MG_GATE();
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double prev = s->prev_rho;
+    const double tmp = (prev == 0.0) ? 0.0 : s->rho / prev;
+    p[i] = r[i] + tmp * p[i];
+}
+
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_cg_step2(int n, double *__restrict__ x, double *__restrict__ r,
+                                                          const double *__restrict__ p, const double *__restrict__ q,
+                                                          const MgScalars *s, const DevScalars *gate)
+{
+    MG_GATE();
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double beta = s->beta;
+    if (beta == 0.0) return;
+    const double t = s->rho / beta;
+    x[i] += t * p[i];
+    r[i] -= t * q[i];
+}
+
+// ------------------------------------------------------------------------------------------
+// the tail: every level of at most mgTailRows rows in ONE workgroup -- down sweep, the coarsest CG, up sweep -- with a
+// barrier between phases instead of a launch (those levels are bound by the dispatch latency of dependent launches, not by
+// bytes).  The same operations in the same order as the kernels above, hence the same bits.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ double tail_row_product(const MgTailLevel &L, int i, const double *x, const double *xc)
+{
+    double s = 0.0;
+    for (int k = L.row_ptrs[i]; k < L.row_ptrs[i + 1]; ++k) {
+        const int j = L.cols[k];
+        double t = x[j];
+        if (xc) t = t + xc[L.agg[j]];
+        s += L.vals[k] * t;
+    }
+    return s;
+}
+
+// x_out = t + omega ((b - A t) inv_d), t = x (+ xc[agg]); x_out != x
+__device__ __forceinline__ void tail_sweep(const MgTailLevel &L, const double *b, const double *x, const double *xc,
+                                           double *x_out)
+{
+    for (int i = threadIdx.x; i < L.n; i += BLOCK) {
+        const double s = tail_row_product(L, i, x, xc);
+        double ti = x[i];
+        if (xc) ti = ti + xc[L.agg[i]];
+        x_out[i] = ti + MG_OMEGA * ((b[i] - s) * L.inv_d[i]);
+    }
+    __syncthreads();
+}
+
+// a . b in the loop's tree: per-chunk partials as k_partials forms them, then the finaliser's tree (<= FIN_BLOCK chunks)
+__device__ __forceinline__ double tail_dot(int n, const double *a, const double *b, double *part, double *lds)
+{
+    const int nc = (n + CHUNK_ROWS - 1) / CHUNK_ROWS;
+    for (int c = 0; c < nc; ++c) {
+        const RowPair r = my_rows(c, n);
+        const double2 va = ld2(a, r), vb = ld2(b, r);
+        double d = 0.0;
+        if (r.n > 0) d += va.x * vb.x;
+        if (r.n > 1) d += va.y * vb.y;
+        const double s = block_sum(d, lds);
+        if (threadIdx.x == 0) part[c] = s;
+    }
+    __syncthreads();
+    double pv[2][FIN_VT], out[2];
+    load_partials_as_finaliser<1>(part, nullptr, nc, pv);
+    reduce_partials_as_finaliser<1>(pv, nc, lds, out);
+    return out[0];
+}
+
+__global__ __launch_bounds__(BLOCK) void k_mg_tail(MgTail T, const double *b_in, double *x_out, const DevScalars *gate)
+{
+    __shared__ double lds[2 * FIN_WAVES];
+    MG_GATE();
+    const int last = T.count - 1;
+    for (int l = 0; l < last; ++l) {  // ---- down ----
+        const MgTailLevel &L = T.lev[l];
+        const double *b = l == 0 ? b_in : L.b;
+        for (int i = threadIdx.x; i < L.n; i += BLOCK) L.xa[i] = MG_OMEGA * (b[i] * L.inv_d[i]);
+        __syncthreads();
+        tail_sweep(L, b, L.xa, nullptr, L.xb);
+        double *bc = T.lev[l + 1].b;
+        for (int I = threadIdx.x; I < L.n_coarse; I += BLOCK) {
+            double acc = 0.0;
+            for (int m = L.agg_ptr[I]; m < L.agg_ptr[I + 1]; ++m) {
+                const int i = L.agg_rows[m];
+                acc += b[i] - tail_row_product(L, i, L.xb, nullptr);
+            }
+            bc[I] = acc;
+        }
+        __syncthreads();
+    }
+    {  // ---- the coarsest solver ----
+        const MgTailLevel &L = T.lev[last];
+        const double *b = last == 0 ? b_in : L.b;
+        double *x = last == 0 ? x_out : L.xb;
+        for (int i = threadIdx.x; i < L.n; i += BLOCK) {
+            L.r[i] = b[i];
+            x[i] = 0.0;
+            L.p[i] = 0.0;
+        }
+        __syncthreads();
+        double rho = 0.0;
+        for (int it = 0; it < T.cg_iters; ++it) {
+            const double prev = it == 0 ? 1.0 : rho;
+            rho = tail_dot(L.n, L.r, L.r, L.part, lds);
+            const double tmp = (prev == 0.0) ? 0.0 : rho / prev;
+            for (int i = threadIdx.x; i < L.n; i += BLOCK) L.p[i] = L.r[i] + tmp * L.p[i];
+            __syncthreads();
+            for (int i = threadIdx.x; i < L.n; i += BLOCK) L.t[i] = tail_row_product(L, i, L.p, nullptr);
+            __syncthreads();
+            const double beta = tail_dot(L.n, L.p, L.t, L.part, lds);
+            if (beta != 0.0) {
+                const double t = rho / beta;
+                for (int i = threadIdx.x; i < L.n; i += BLOCK) {
+                    x[i] += t * L.p[i];
+                    L.r[i] -= t * L.t[i];
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int l = last - 1; l >= 0; --l) {  // ---- up ----
+        const MgTailLevel &L = T.lev[l];
+        const double *b = l == 0 ? b_in : L.b;
+        tail_sweep(L, b, L.xb, T.lev[l + 1].xb, L.xa);
+        tail_sweep(L, b, L.xa, nullptr, l == 0 ? x_out : L.xb);
+    }
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------
+#define MG_LAUNCH(kernel, count, ...)                                                                    \
+    do {                                                                                                 \
+        if ((count) > 0) hipLaunchKernelGGL(kernel, dim3(mg_grid(count)), dim3(MG_BLOCK), 0, st, __VA_ARGS__); \
+    } while (0)
+
+void launch_mg_diag(hipStream_t st, const MgCsr &A, double *diag, double *inv_d) { MG_LAUNCH(k_mg_diag, A.n, A, diag, inv_d); }
+void launch_mg_strongest(hipStream_t st, const MgCsr &A, const double *diag, const int32_t *agg, int want, int32_t *s)
+{
+    MG_LAUNCH(k_mg_strongest, A.n, A, diag, agg, want, s);
+}
+void launch_mg_match(hipStream_t st, int32_t n, const int32_t *s, int32_t *agg, int32_t *left)
+{
+    MG_LAUNCH(k_mg_match, n, n, s, agg, left);
+}
+void launch_mg_join(hipStream_t st, int32_t n, const int32_t *s, int32_t *agg) { MG_LAUNCH(k_mg_join, n, n, s, agg); }
+void launch_mg_root_flag(hipStream_t st, int32_t n, const int32_t *agg, int32_t *flag)
+{
+    MG_LAUNCH(k_mg_root_flag, n, n, agg, flag);
+}
+void launch_mg_coarse_index(hipStream_t st, int32_t n, const int32_t *agg, const int32_t *incl, int32_t *cidx, int32_t *rows)
+{
+    MG_LAUNCH(k_mg_coarse_index, n, n, agg, incl, cidx, rows);
+}
+void launch_mg_member_ptr(hipStream_t st, int32_t n, int32_t nc, const int32_t *sorted, int32_t *agg_ptr)
+{
+    MG_LAUNCH(k_mg_member_ptr, n, n, nc, sorted, agg_ptr);
+}
+void launch_mg_keys(hipStream_t st, const MgCsr &A, const int32_t *cidx, unsigned long long *keys)
+{
+    MG_LAUNCH(k_mg_keys, A.n, A, cidx, keys);
+}
+void launch_mg_head_flag(hipStream_t st, int32_t m, const unsigned long long *keys, int32_t *flag)
+{
+    MG_LAUNCH(k_mg_head_flag, m, m, keys, flag);
+}
+void launch_mg_compact(hipStream_t st, int32_t m, int32_t nc, const unsigned long long *keys, const double *vals,
+                       const int32_t *pos, int32_t *row_ptrs, int32_t *cols, double *out)
+{
+    MG_LAUNCH(k_mg_compact, m, m, nc, keys, vals, pos, row_ptrs, cols, out);
+}
+
+size_t mg_temp_bytes(int32_t n, int32_t nnz)
+{
+    size_t a = 0, b = 0, c = 0;
+    (void)hipcub::DeviceScan::InclusiveSum(nullptr, a, (const int32_t *)nullptr, (int32_t *)nullptr, std::max(n, nnz));
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const int32_t *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr,
+                                             (int32_t *)nullptr, n);
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, c, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                             (const double *)nullptr, (double *)nullptr, nnz);
+    return std::max(a, std::max(b, c)) + 256;
+}
+hipError_t mg_inclusive_sum(hipStream_t st, void *temp, size_t temp_bytes, const int32_t *in, int32_t *out, int32_t n)
+{
+    return hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, in, out, n, st);
+}
+hipError_t mg_sort_rows(hipStream_t st, void *temp, size_t temp_bytes, const int32_t *keys, int32_t *keys_out,
+                        const int32_t *rows, int32_t *rows_out, int32_t n)
+{
+    return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys, keys_out, rows, rows_out, n, 0, 32, st);
+}
+hipError_t mg_sort_entries(hipStream_t st, void *temp, size_t temp_bytes, const unsigned long long *keys,
+                           unsigned long long *keys_out, const double *vals, double *vals_out, int32_t m)
+{
+    return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys, keys_out, vals, vals_out, m, 0, 64, st);
+}
+
+void launch_mg_jacobi0(hipStream_t st, int32_t n, const double *b, const double *inv_d, double *x, const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_jacobi0, n, n, b, inv_d, x, gate);
+}
+void launch_mg_sweep_epi(hipStream_t st, int32_t n, const double *b, const double *ax, const double *inv_d, const double *x,
+                         double *x_out, const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_sweep_epi, n, n, b, ax, inv_d, x, x_out, gate);
+}
+void launch_mg_prolong(hipStream_t st, int32_t n, const double *x, const double *xc, const int32_t *agg, double *x_out,
+                       const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_prolong, n, n, x, xc, agg, x_out, gate);
+}
+void launch_mg_csr_sweep(hipStream_t st, const MgCsr &A, const double *inv_d, const double *b, const double *x,
+                         const double *xc, const int32_t *agg, double *x_out, const DevScalars *gate)
+{
+    if (xc)
+        MG_LAUNCH(k_mg_csr_sweep<true>, A.n, A, inv_d, b, x, xc, agg, x_out, gate);
+    else
+        MG_LAUNCH(k_mg_csr_sweep<false>, A.n, A, inv_d, b, x, xc, agg, x_out, gate);
+}
+void launch_mg_csr_spmv(hipStream_t st, const MgCsr &A, const double *x, double *y, const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_csr_spmv, A.n, A, x, y, gate);
+}
+void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsr &A,
+                        const double *b, const double *x, const double *ax, double *bc, const DevScalars *gate)
+{
+    if (ax)
+        MG_LAUNCH(k_mg_restrict<true>, nc, nc, agg_ptr, agg_rows, A, b, x, ax, bc, gate);
+    else
+        MG_LAUNCH(k_mg_restrict<false>, nc, nc, agg_ptr, agg_rows, A, b, x, ax, bc, gate);
+}
+void launch_mg_cg_init(hipStream_t st, int32_t n, const double *b, double *r, double *x, double *p, const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_cg_init, n, n, b, r, x, p, gate);
+}
+void launch_mg_cg_fin(hipStream_t st, const double *part, int32_t n_part, int what, int first, MgScalars *s,
+                      const DevScalars *gate)
+{
+    hipLaunchKernelGGL(k_mg_cg_fin, dim3(1), dim3(FIN_BLOCK), 0, st, part, n_part, what, first, s, gate);
+}
+void launch_mg_cg_step1(hipStream_t st, int32_t n, double *p, const double *r, const MgScalars *s, const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_cg_step1, n, n, p, r, s, gate);
+}
+void launch_mg_cg_step2(hipStream_t st, int32_t n, double *x, double *r, const double *p, const double *q,
+                        const MgScalars *s, const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_cg_step2, n, n, x, r, p, q, s, gate);
+}
+
+void launch_mg_tail(hipStream_t st, const MgTail &T, const double *b, double *x, const DevScalars *gate)
+{
+    hipLaunchKernelGGL(k_mg_tail, dim3(1), dim3(BLOCK), 0, st, T, b, x, gate);
+}
+
+}  // namespace ogl

@@ -295,6 +295,9 @@ double ogl_solver::turn_extra_bytes() const
     if ((cfg.preconditioner == OGL_PRECOND_IC || cfg.preconditioner == OGL_PRECOND_ILU ||
          cfg.preconditioner == OGL_PRECOND_IRILU) && pat.renumbered())
         extra += 8.0 * N;  // the vector in the caller's order
+    // Multigrid: the coarse matrices (12 bytes per entry, about half the fine level's entries in all) and the fine level's
+    // inverse diagonal, aggregates and three vectors
+    if (cfg.preconditioner == OGL_PRECOND_MULTIGRID) extra += 6.0 * nnz + 36.0 * N;
     if (cfg.preconditioner != OGL_PRECOND_NONE && !(cfg.preconditioner == OGL_PRECOND_BJ && cfg.max_block_size == 1))
         extra += 16.0 * N;                                                      // materialised z (and the ISAI temporary)
     if (cfg.solver == OGL_SOLVER_BICGSTAB) extra += 32.0 * N;

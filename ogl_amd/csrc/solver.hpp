@@ -19,9 +19,34 @@
 
 namespace ogl {
 
+// One matrix of a Multigrid hierarchy with what its V-cycle needs (kernels_mg.hip).  Level 0 is the system matrix itself:
+// it keeps no copy of it, only 1 / diagonal, the aggregates and the vectors.
+struct MgLevel {
+    int32_t n = 0, nnz = 0, n_coarse = 0;      // n_coarse: rows of the next level (0: this is the coarsest)
+    // levels >= 1; level 0 only on a renumbered device copy (own: the system matrix in the CALLER's numbering, in which
+    // the hierarchy lives -- the products then run on it instead of the in-loop layout)
+    bool own = true;
+    DevBuf<int32_t> row_ptrs, cols;
+    DevBuf<double> vals, inv_d;
+    DevBuf<int32_t> agg, agg_ptr, agg_rows;    // fine-to-coarse map, members per coarse row (ascending)
+    DevBuf<double> b, xa, xb, t, r, p;         // right-hand side (levels >= 1), iterates, A x; r, p: the coarsest level's CG
+    DevBuf<double> part;                       // ... its per-chunk partials
+    MgCsr view() const
+    {
+        MgCsr A;
+        A.n = n;
+        A.nnz = nnz;
+        A.row_ptrs = row_ptrs.p;
+        A.cols = cols.p;
+        A.vals = vals.p;
+        return A;
+    }
+};
+
 // A generated preconditioner ("Cached_preconditinoner" holds one of these, Preconditioner.H:357)
 struct PrecondData {
-    int kind = 0;  // 0 none, 1 scalar Jacobi (inverse diagonal), 2 block Jacobi, 3 ISAI, 4 GISAI, 5 IC, 6 ILU, 7 IRILU
+    // 0 none, 1 scalar Jacobi (inverse diagonal), 2 block Jacobi, 3 ISAI, 4 GISAI, 5 IC, 6 ILU, 7 IRILU, 8 Multigrid
+    int kind = 0;
     size_t n_rows = 0;
     int stride = 0;  // block Jacobi: maxBlockSize
     int32_t n_blocks = 0;
@@ -58,6 +83,18 @@ struct PrecondData {
     DevBuf<int32_t> f_breakdown;  // first row with a zero / non-positive pivot (0x7f7f7f7f: none)
     std::vector<int32_t> f_fwd_ptr_h, f_bwd_ptr_h;
     int32_t f_nnz = 0;
+    // Multigrid (kind 8): the levels in use are mg[0 .. mg_levels); the objects behind them are kept from generation to
+    // generation so that their buffers only grow.  mg_work: what a generation needs besides (also only growing).
+    std::vector<std::unique_ptr<MgLevel>> mg;
+    int mg_levels = 0, mg_cg_iters = 0;
+    DevBuf<MgScalars> mg_scal;
+    DevBuf<int32_t> mg_map0;         // renumbered device copy: position in the device CSR of every entry of level 0
+    DevBuf<double> mg_in, mg_out;    // ... and the vectors of an apply in the caller's order
+    DevBuf<double> mg_diag, mg_vals_sorted;
+    DevBuf<int32_t> mg_s, mg_flag, mg_incl, mg_cidx, mg_rows, mg_sorted, mg_left;
+    DevBuf<unsigned long long> mg_keys, mg_keys_sorted;
+    DevBuf<uint8_t> mg_temp;
+    bool multigrid() const { return kind == 8; }
     uint64_t serial = 0;  // new value with every generation (an applier checks it still holds what it adopted)
     // the pattern-only part (block pointers / W and W^T patterns) is kept for as long as it was
     // derived from the same sparsity pattern: only the values are regenerated per solve
@@ -77,10 +114,11 @@ struct PrecondData {
     uint64_t gen_pat_id = 0;
     bool gen_device_numbering = false;
     bool caller_order_blocks() const { return kind == 2 && !by_device_row && !gen_device_numbering; }
-    bool factor() const { return kind >= 5; }
+    bool factor() const { return kind >= 5 && kind <= 7; }
     bool foreign_to(uint64_t id, bool renumbered) const
     {
         if (gen_pat_id == id) return false;
+        // (a Multigrid hierarchy is self-contained only when its generator kept a level 0 of its own)
         return gen_device_numbering || (renumbered && !caller_order_blocks() && !factor());
     }
 };
@@ -251,6 +289,14 @@ struct ogl_solver {
     ogl::DevBuf<double> d_V, d_gm;                      // GMRES: Krylov bases, dense state
     ogl::DevBuf<double> d_isai_tmp;                     // ISAI(spd): W r before W^T
     ogl::DevBuf<double> d_fac_tmp[3];  // IC / ILU / IRILU: vectors in the caller's order, IRILU's iterates
+    // Multigrid: generation of the hierarchy (per-round and per-level sizes are the only host round trips) and one V-cycle
+    int generate_multigrid(ogl::PrecondData &P);
+    void apply_multigrid(const double *in, double *out, const ogl::DevScalars *gate, double *dot_part);
+    void mg_cycle(int level, const double *b, double *x, const ogl::DevScalars *gate, int &launches);
+    // A x of a level (0: the system matrix on the in-loop layout, local part only)
+    void mg_product(int level, const double *x, double *y, const ogl::DevScalars *gate);
+    int check_multigrid_keywords();
+    int mg_tail_first = 0;  // first level the single-workgroup tail kernel takes in this solver's applies (mg_levels: none)
     bool precond_ready = false;        // a solve has set up precond_data (ogl_solver_apply_preconditioner)
     uint64_t precond_serial = 0, precond_pat = 0;  // ... the object's serial and this solver's pattern at that time
     bool precond_current() const;      // precond_data is still what the last solve set up, for this pattern

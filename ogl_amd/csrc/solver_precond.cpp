@@ -27,7 +27,11 @@ int ogl_solver::generate_preconditioner(PrecondData &P)
     const bool through_perm = pat.renumbered() && caller_numbering;
     if (P.struct_caller_numbering != caller_numbering) P.struct_pat_id = 0;  // (the switch was flipped: rebuild)
     P.struct_caller_numbering = caller_numbering;
-    if (cfg.preconditioner == OGL_PRECOND_IC || cfg.preconditioner == OGL_PRECOND_ILU ||
+    if (cfg.preconditioner == OGL_PRECOND_MULTIGRID) {
+        // Pgm + Multigrid (Preconditioner.H:259-341) on the local matrix in the caller's numbering; the aggregates depend on
+        // the values, so nothing of it is pattern-only (solver_mg.cpp)
+        OGL_TRY(generate_multigrid(P));
+    } else if (cfg.preconditioner == OGL_PRECOND_IC || cfg.preconditioner == OGL_PRECOND_ILU ||
         cfg.preconditioner == OGL_PRECOND_IRILU) {
         // factorization::Ic / Ilu (Preconditioner.H:106-126,147-178) on the local matrix in the caller's numbering.
         // Pattern-only part on the host (FactorStructure), values gathered and factored on the device level by level.
@@ -290,7 +294,7 @@ int ogl_solver::generate_preconditioner(PrecondData &P)
     P.serial = ++serials;
     P.gen_pat_id = pat_id;
     P.gen_device_numbering = pat.renumbered() && !(P.kind == 2 && P.through_perm && !P.by_device_row) &&
-                             !P.factor();  // (see PrecondData::foreign_to)
+                             !P.factor() && !P.multigrid();  // (see PrecondData::foreign_to)
     return OGL_OK;
 }
 
@@ -397,6 +401,10 @@ void ogl_solver::apply_preconditioner(const double *in, double *out, const DevSc
         apply_factor(in, out, gate, dot_part);
         return;
     }
+    if (precond_data->multigrid()) {
+        apply_multigrid(in, out, gate, dot_part);
+        return;
+    }
     // the last kernel of the apply also leaves the partials of in . out
     SpmvDots last{};
     if (dot_part) {
@@ -472,7 +480,9 @@ int ogl_solver::init_preconditioner()
     const bool isai = cfg.preconditioner == OGL_PRECOND_ISAI || cfg.preconditioner == OGL_PRECOND_GISAI;
     const bool factor = cfg.preconditioner == OGL_PRECOND_IC || cfg.preconditioner == OGL_PRECOND_ILU ||
                         cfg.preconditioner == OGL_PRECOND_IRILU;
-    if (cfg.preconditioner != OGL_PRECOND_BJ && !isai && !factor)
+    const bool mg = cfg.preconditioner == OGL_PRECOND_MULTIGRID;
+    if (mg) OGL_TRY(check_multigrid_keywords());
+    if (cfg.preconditioner != OGL_PRECOND_BJ && !isai && !factor && !mg)
         return fail(OGL_ERR_UNSUPPORTED, "preconditioner kind %d is not built", cfg.preconditioner);
     if (isai && (cfg.sparsity_power < 1 || cfg.sparsity_power > 8))
         return fail(OGL_ERR_INVALID, "ISAI sparsityPower %d outside [1, 8]", cfg.sparsity_power);
@@ -481,7 +491,7 @@ int ogl_solver::init_preconditioner()
                     MAX_JACOBI_BLOCK);
     if (cfg.preconditioner == OGL_PRECOND_ISAI)
         OGL_TRY(d_isai_tmp.alloc((size_t)pat.n_rows + 2, reg->stream));
-    const int kind = factor ? (cfg.preconditioner == OGL_PRECOND_IC ? 5 : (cfg.preconditioner == OGL_PRECOND_ILU ? 6 : 7))
+    const int kind = mg ? 8 : factor ? (cfg.preconditioner == OGL_PRECOND_IC ? 5 : (cfg.preconditioner == OGL_PRECOND_ILU ? 6 : 7))
                      : isai ? (cfg.preconditioner == OGL_PRECOND_ISAI ? 3 : 4)
                             : (cfg.max_block_size == 1 ? 1 : 2);
     const int stride = kind == 2 ? cfg.max_block_size : (isai ? cfg.sparsity_power : 0);
