@@ -440,13 +440,16 @@ __device__ __forceinline__ void lead_wave_sums(const LeadBox &L, uint32_t tag, c
 // word i of the mailbox: [tag : 32 | payload : 32], one atomic 8-byte store / load each (payload: half of a double)
 // Threads 0 .. n_words - 1 of a polling workgroup fetch one word each: half-word i of vals[] (the doubles the leaders
 // published, in mailbox order); returns (to every thread) false when a leader never published (time-out: a defect, not
-// a state of the solve -- the caller raises comm_error and leaves).
-__device__ __forceinline__ bool lead_wait(const LeadBox &L, int n_words, uint32_t tag, double *vals, int *timed_out)
+// a state of the solve -- the caller raises comm_error and leaves).  `first`: the mailbox word that half-word 0 of vals[] is
+// (a kernel that waits twice keeps its second set of sums in words of their own: a workgroup still polling for the first
+// set must never find its words overwritten).
+__device__ __forceinline__ bool lead_wait(const LeadBox &L, int n_words, uint32_t tag, double *vals, int *timed_out,
+                                          int first = 0)
 {
     if (threadIdx.x == 0) *timed_out = 0;
     __syncthreads();
     if ((int)threadIdx.x < n_words) {
-        const unsigned long long *src = L.box + (size_t)(blockIdx.x % LEAD_REPLICAS) * LEAD_REPLICA_STRIDE + threadIdx.x;
+        const unsigned long long *src = L.box + (size_t)(blockIdx.x % LEAD_REPLICAS) * LEAD_REPLICA_STRIDE + first + threadIdx.x;
         const long long t0 = wall_clock64();
         for (;;) {
             const unsigned long long w = __hip_atomic_load(src, __ATOMIC_RELAXED, LEAD_SCOPE);
@@ -464,6 +467,59 @@ __device__ __forceinline__ bool lead_wait(const LeadBox &L, int n_words, uint32_
     __syncthreads();
     return *timed_out == 0;
 }
+// a double as two tagged half-words [tag : 32 | payload : 32] (the held-z / held-q turns; no fence, no order between them)
+__device__ __forceinline__ void put_tagged(unsigned long long *w, uint32_t tag, double v)
+{
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
+    __hip_atomic_store(w, ((unsigned long long)tag << 32) | (uint32_t)bits, __ATOMIC_RELAXED, LEAD_SCOPE);
+    __hip_atomic_store(w + 1, ((unsigned long long)tag << 32) | (uint32_t)(bits >> 32), __ATOMIC_RELAXED, LEAD_SCOPE);
+}
+
+// lead_wave_sums over partials that arrive while it runs: partial i is words stride i, + 1 of `tagged` (put_tagged; the
+// caller points `tagged` at its array's pair of words); a word counts once it carries `tag`.  One wavefront, no staging: lane l is virtual thread 64 w + l and
+// adds its partials v, v + 1024, ... in that order -- with a grid of FIN_BLOCK workgroups the order in which workgroup v
+// produces them -- four at a time, so that only the last four are awaited after the chip's last chunk.  A partial that
+// never arrives: nothing is published, and every workgroup's wait for the box runs into its bound.
+__device__ __forceinline__ void lead_wave_sums_tagged(const LeadBox &L, uint32_t tag, const unsigned long long *tagged,
+                                                      int stride, int m, int w, int array)
+{
+    constexpr int Q = 4;
+    if (threadIdx.x >= WAVE) return;
+    const int lane = threadIdx.x;
+    const long long t0 = wall_clock64();
+    double s = 0.0;
+    bool arrived = true;
+    for (long i0 = w * WAVE + lane; arrived && i0 < m; i0 += (long)FIN_BLOCK * Q) {
+        unsigned long long lo[Q], hi[Q];
+        for (;;) {
+            bool all = true;
+#pragma unroll
+            for (int e = 0; e < Q; ++e) {
+                const long i = i0 + (long)FIN_BLOCK * e;
+                lo[e] = hi[e] = (unsigned long long)tag << 32;
+                if (i < m) {
+                    lo[e] = __hip_atomic_load(tagged + (size_t)stride * i, __ATOMIC_RELAXED, LEAD_SCOPE);
+                    hi[e] = __hip_atomic_load(tagged + (size_t)stride * i + 1, __ATOMIC_RELAXED, LEAD_SCOPE);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < Q; ++e) all = all && (uint32_t)(lo[e] >> 32) == tag && (uint32_t)(hi[e] >> 32) == tag;
+            if (all) break;
+            if (wall_clock64() - t0 > L.timeout_ticks) {
+                arrived = false;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(1);
+        }
+#pragma unroll
+        for (int e = 0; e < Q; ++e)
+            if (i0 + (long)FIN_BLOCK * e < m) s += __longlong_as_double((long long)((hi[e] << 32) | (uint32_t)lo[e]));
+    }
+    if (!__all(arrived)) return;  // (the whole wavefront: a sum that lacks one lane's partials must not go out)
+    s = wave_sum(s);
+    if (lane < LEAD_REPLICAS) put_tagged(L.box + (size_t)lane * LEAD_REPLICA_STRIDE + array * 2 * FIN_WAVES + 2 * w, tag, s);
+}
+
 // The leaders of a launch that finalises K partial arrays: workgroup b < 16 K is wavefront b % 16 of array b / 16.
 template <int K>
 __device__ __forceinline__ void lead_leaders(const LeadBox &L, uint32_t tag, const double *__restrict__ p0,

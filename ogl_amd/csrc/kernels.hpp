@@ -476,12 +476,27 @@ struct HeldZ {
     int32_t grid = 0;                      // workgroups, all resident at once; each owns chunks w, w + grid, ...
     int32_t x_early = 1;                   // 1: a head that updates x does so while the sums are awaited
 };
-int held_z_grid(int *chunks_per_workgroup);  // the largest resident grid of the kernel on this device (0: none)
+// the geometry both resident turn kernels share: B workgroups per CU, R chunks per workgroup held in registers, L in LDS
+constexpr int HZ_B = 4, HZ_R = 11, HZ_L = 9;
+int held_z_grid(int *chunks_per_workgroup);  // the largest resident grid of the kernels on this device (0: none)
 // every workgroup of `grid` waits, bounded, for all the others: *out = 1 afterwards when they were not all on the chip at once
 int launch_resident_census(hipStream_t st, int grid, unsigned *arrived, int *out, long long timeout_ticks);
 void launch_cg_step2r1x(hipStream_t st, int32_t n, double *r, const double *q, const double *inv_diag, double *p,
                         double *p_out, double *x, DevScalars *s, const double *part_beta, double *history,
                         const LeadBox &lead, const PRing &ring, const HeldZ &hz);
+// The held-q turn (kernels_spmv_sym.hip, k_cg_turn_held_q): the half-storage SpMV in front of that kernel, one launch per
+// turn -- q = A p stays on chip across the sum beta = p.q as z does across the later two.  The workgroups own POSITIONS of
+// the layout's launch order (slot i of workgroup w: position w + i grid), so the tagged box has 6 words per chunk.
+struct HeldQ {
+    int32_t on = 0;     // 1: the turns without an event pair run the one-launch kernel
+    int32_t n_pos = 0;  // positions of the launch order (DevSym::n_blocks, or xcd_grid(chunks) without a band order)
+};
+int held_q_positions(const DevSym &A);
+// occupancy (workgroups per CU) and static LDS bytes of the held-q instantiations: the minimum / the maximum over them
+int held_q_occupancy(int *per_cu, size_t *lds_bytes);
+void launch_cg_turn_held_q(hipStream_t st, const DevSym &A, double *r, const double *inv_diag, double *p, double *p_out,
+                           double *x, DevScalars *s, double *history, const LeadBox &lead, const PRing &ring,
+                           const HeldZ &hz, const HeldQ &hq);
 constexpr int FUSED_FIN_MAX_CHUNKS = 1024;  // up to 524,288 rows: one partial per virtual finaliser thread
 // step_1x_fin and the SpMV on half storage in one launch (p_new = z + (rho/rho') p recomputed at the gathered
 // columns; it goes to p_out != p_in for the own rows): a turn is this + step_2r_fin.  z: what step_2r_fin's z_out

@@ -603,58 +603,6 @@ __global__ __launch_bounds__(BLOCK) void k_cg_step2r_fin(int n, double *__restri
 // barriers of block_sum2 stand between), and workgroup 0 writes only after it has seen the sums of ALL partials.
 // Every spin is bounded by lead.timeout_ticks and ends the solve with comm_error.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void put_tagged(unsigned long long *w, uint32_t tag, double v)
-{
-    const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
-    __hip_atomic_store(w, ((unsigned long long)tag << 32) | (uint32_t)bits, __ATOMIC_RELAXED, LEAD_SCOPE);
-    __hip_atomic_store(w + 1, ((unsigned long long)tag << 32) | (uint32_t)(bits >> 32), __ATOMIC_RELAXED, LEAD_SCOPE);
-}
-
-// lead_wave_sums over partials that arrive while it runs: partial i of array a is words 4 i + 2 a, + 1 of `tagged`
-// (put_tagged); a word counts once it carries `tag`.  One wavefront, no staging: lane l is virtual thread 64 w + l and
-// adds its partials v, v + 1024, ... in that order -- with a grid of FIN_BLOCK workgroups the order in which workgroup v
-// produces them -- four at a time, so that only the last four are awaited after the chip's last chunk.  A partial that
-// never arrives: nothing is published, and every workgroup's wait for the box runs into its bound.
-__device__ __forceinline__ void lead_wave_sums_tagged(const LeadBox &L, uint32_t tag, const unsigned long long *tagged,
-                                                      int m, int w, int array)
-{
-    constexpr int Q = 4;
-    if (threadIdx.x >= WAVE) return;
-    const int lane = threadIdx.x;
-    const long long t0 = wall_clock64();
-    double s = 0.0;
-    bool arrived = true;
-    for (long i0 = w * WAVE + lane; arrived && i0 < m; i0 += (long)FIN_BLOCK * Q) {
-        unsigned long long lo[Q], hi[Q];
-        for (;;) {
-            bool all = true;
-#pragma unroll
-            for (int e = 0; e < Q; ++e) {
-                const long i = i0 + (long)FIN_BLOCK * e;
-                lo[e] = hi[e] = (unsigned long long)tag << 32;
-                if (i < m) {
-                    lo[e] = __hip_atomic_load(tagged + 4 * i + 2 * array, __ATOMIC_RELAXED, LEAD_SCOPE);
-                    hi[e] = __hip_atomic_load(tagged + 4 * i + 2 * array + 1, __ATOMIC_RELAXED, LEAD_SCOPE);
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < Q; ++e) all = all && (uint32_t)(lo[e] >> 32) == tag && (uint32_t)(hi[e] >> 32) == tag;
-            if (all) break;
-            if (wall_clock64() - t0 > L.timeout_ticks) {
-                arrived = false;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-#pragma unroll
-        for (int e = 0; e < Q; ++e)
-            if (i0 + (long)FIN_BLOCK * e < m) s += __longlong_as_double((long long)((hi[e] << 32) | (uint32_t)lo[e]));
-    }
-    if (!__all(arrived)) return;  // (the whole wavefront: a sum that lacks one lane's partials must not go out)
-    s = wave_sum(s);
-    if (lane < LEAD_REPLICAS) put_tagged(L.box + (size_t)lane * LEAD_REPLICA_STRIDE + array * 2 * FIN_WAVES + 2 * w, tag, s);
-}
-
 template <int R, int L, int B, int K>
 __global__ __launch_bounds__(BLOCK, B) void k_cg_step2r1x(int n, double *__restrict__ r, const double *__restrict__ q,
                                                           const double *__restrict__ inv_diag, double *p, double *p_out,
@@ -748,7 +696,10 @@ __global__ __launch_bounds__(BLOCK, B) void k_cg_step2r1x(int n, double *__restr
         }
     }
     // the sums of all partials: workgroup b < 32 is wavefront b % 16 of the finaliser for array b / 16
-    if (w < 2 * FIN_WAVES) lead_wave_sums_tagged(lead, tag, tagged, n_part, w % FIN_WAVES, w / FIN_WAVES);
+    // (into arrays 1 and 2 of the mailbox: array 0 keeps beta for a workgroup that still polls for it -- one that owns no
+    // chunk holds nobody's sums back)
+    if (w < 2 * FIN_WAVES)
+        lead_wave_sums_tagged(lead, tag, tagged + 2 * (w / FIN_WAVES), 4, n_part, w % FIN_WAVES, 1 + w / FIN_WAVES);
     // this head's term of x and the terms pending before it: ((x + t_1 p_1) + t p), the bits of single updates
     const bool own_term = beta != 0.0;
     const double t_own = own_term ? s_rho / beta : 0.0;
@@ -775,7 +726,7 @@ __global__ __launch_bounds__(BLOCK, B) void k_cg_step2r1x(int n, double *__restr
             update_x(rp, ld2(p, rp), K);
         }
     }
-    if (!lead_wait(lead, 4 * FIN_WAVES, tag, lead_words, &lead_timed_out)) {
+    if (!lead_wait(lead, 4 * FIN_WAVES, tag, lead_words, &lead_timed_out, 2 * FIN_WAVES)) {
         if (tx == 0) s->comm_error = s->stop = 1;
         return;
     }
@@ -1817,7 +1768,7 @@ void launch_cg_step2r_fin(hipStream_t st, int32_t n, double *r, const double *q,
 // The held-z turn's geometry: B workgroups per CU, z of R chunks in registers and of L in LDS per workgroup (116 / 118 of
 // 128 VGPRs, 36.5 of 40 KB of LDS, no scratch: DESIGN.md section 4.2 has the compiler's figures; a tenth chunk of LDS does
 // not fit, and 15 chunks in registers -- 5 in LDS next to a stage for the leaders -- spilled two registers)
-constexpr int HZ_B = 4, HZ_R = 11, HZ_L = 9;
+// (HZ_B, HZ_R, HZ_L: kernels.hpp -- the held-q turn of kernels_spmv_sym.hip shares them)
 #define OGL_HELD_Z(K) k_cg_step2r1x<HZ_R, HZ_L, HZ_B, K>
 
 int held_z_grid(int *chunks_per_workgroup)
@@ -1829,17 +1780,25 @@ int held_z_grid(int *chunks_per_workgroup)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[0], OGL_HELD_Z(0), BLOCK, 0) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[1], OGL_HELD_Z(2), BLOCK, 0) != hipSuccess)
         return 0;
+    // (the held-q turn runs the same grid: the minimum over its instantiations as well)
+    int per_cu_q = 0;
+    size_t lds_q = 0;
+    if (held_q_occupancy(&per_cu_q, &lds_q) != 0) return 0;
     // (never more than B per CU, whatever the runtime would admit: the capacity is the committed geometry's)
-    return prop.multiProcessorCount * std::min(HZ_B, std::min(per_cu[0], per_cu[1]));
+    return prop.multiProcessorCount * std::min(std::min(HZ_B, per_cu_q), std::min(per_cu[0], per_cu[1]));
 }
 
 int launch_resident_census(hipStream_t st, int grid, unsigned *arrived, int *out, long long timeout_ticks)
 {
     hipFuncAttributes fa;
     if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(OGL_HELD_Z(2))) != hipSuccess) return 1;
+    int per_cu_q = 0;
+    size_t lds_q = 0;  // (the larger LDS size of the two turn kernels)
+    if (held_q_occupancy(&per_cu_q, &lds_q) != 0) return 1;
+    const size_t lds = std::max((size_t)fa.sharedSizeBytes, lds_q);
     if (hipMemsetAsync(arrived, 0, sizeof(unsigned), st) != hipSuccess || hipMemsetAsync(out, 0, sizeof(int), st) != hipSuccess)
         return 1;
-    hipLaunchKernelGGL((k_resident_census<HZ_B>), dim3(grid), dim3(BLOCK), fa.sharedSizeBytes, st, arrived, out,
+    hipLaunchKernelGGL((k_resident_census<HZ_B>), dim3(grid), dim3(BLOCK), lds, st, arrived, out,
                        timeout_ticks);
     return 0;
 }

@@ -376,6 +376,7 @@ struct ogl_solver {
     int turn_cg_two_launch(KrylovRun &k, int enq, int pe);
     int turn_cg_three_launch(KrylovRun &k, int enq, int pe);
     int turn_cg_held_z(KrylovRun &k, int enq, int pe);
+    int turn_cg_held_q(KrylovRun &k, int enq, int pe);
     int plan_held_z(KrylovRun &k);
     int turn_cg_merged(KrylovRun &k, int enq, int pe);
     int turn_cg_five_launch(KrylovRun &k, int enq, int pe);

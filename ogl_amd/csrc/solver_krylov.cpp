@@ -214,6 +214,7 @@ struct ogl_solver::KrylovRun {
     double *gm_h(int i, int j) const { return gm + (size_t)j * (m + 1) + i; }
     HeldZ hz{};  // the held-z turn: SpMV | k_cg_step2r1x (hz.grid == 0: the three-launch turn)
     bool held_z() const { return hz.grid > 0; }
+    HeldQ hq{};  // the held-q turn: one launch (hq.on; needs the held-z turn's plan, which its profiled turns run)
     PRing ring{};  // three-launch leader turn with ring.k p buffers: x touched every ring.k-th turn (k_cg_step1x_fin)
     double *p_of_turn(int turn) const  // p that turn `turn` reads
     {
@@ -709,12 +710,34 @@ int ogl_solver::turn_cg_held_z(KrylovRun &k, int enq, int pe)
     return OGL_OK;
 }
 
+// The held-q turn, 1 launch: the half-storage SpMV, beta, step_2r, the check, the pending x update and step_1 of the NEXT
+// turn in one resident kernel that keeps q = A p and then z = r / d on chip (k_cg_turn_held_q).  A turn with an event pair
+// runs the two-launch held-z turn instead, so that the pair times the real stand-alone SpMV: both shapes leave the same
+// state behind (scalars in s2, launch_seq + 2, the p ring, the pending x), and a solve may mix them freely.
+int ogl_solver::turn_cg_held_q(KrylovRun &k, int enq, int pe)
+{
+    if (pe >= 0) return turn_cg_held_z(k, enq, pe);
+    hipStream_t st = k.st;
+    double *p_new = k.p_of_turn(enq + 1);
+    if (enq == 0) {
+        OGL_HIP_CHECK(hipEventRecord(k.ev_chk[0], st));
+        launch_cg_step1x_fin(st, k.n, k.p_of_turn(0), d_x.p, d_r.p, precond, k.s, k.s2, d_part0.p, d_part1.p, d_history.p, 1,
+                             k.lead, p_new, k.ring_of_turn(0));
+        OGL_HIP_CHECK(hipEventRecord(k.ev_chk[1], st));
+    }
+    launch_cg_turn_held_q(st, sym(), d_r.p, precond, p_new, k.p_of_turn(enq + 2), d_x.p, k.s2, d_history.p, k.lead,
+                          k.ring_of_turn(enq + 1), k.hz, k.hq);
+    return OGL_OK;
+}
+
 // Whether this solve runs the held-z turn: the leader turn of three launches (scalar Jacobi or none, one rank, p in place
 // or two p buffers), by default where it streams (property heldZ), within what the resident grid holds on chip
 // (heldZMaxChunks can only lower that) and only after a census launch has seen the whole grid on the chip at once.
 int ogl_solver::plan_held_z(KrylovRun &k)
 {
     k.hz = HeldZ{};
+    k.hq = HeldQ{};
+    props["heldQInUse"] = 0.0;
     props["heldZInUse"] = 0.0;
     props["heldZGridInUse"] = 0.0;  // (the workgroups the turn launches: whether heldZGrid was honoured or clipped by the device)
     if (!(k.lead.box != nullptr && k.fused && !k.fused2 && !k.generic && !k.multi && (k.ring.k == 0 || k.ring.k == 2)))
@@ -734,8 +757,18 @@ int ogl_solver::plan_held_z(KrylovRun &k)
     if (grid < 2 * 16) return OGL_OK;  // (the 2 x 16 leaders of the sums)
     const double cap = std::min((double)grid * per_wg, prop("heldZMaxChunks", (double)grid * per_wg));
     if ((double)k.nc > cap) return OGL_OK;
+    // ... and the held-q turn on top of it: half storage, by default where that layout streams (property heldQ), and
+    // only where the POSITIONS of its launch order -- the band order has holes, the default map is padded -- fit the slots.
+    // Position w + i G lands on the XCD the stand-alone SpMV runs it on only where the grid is a multiple of the 8 XCDs:
+    // any other grid (a device with such a CU count, heldZGrid) computes the same bits slower, and is on only by request.
+    bool held_q = false;
+    int n_pos = 0;
+    if (spmv_layout == SpmvLayout::Sym) {
+        n_pos = held_q_positions(sym());
+        held_q = prop("heldQ", sym().stream && grid % 8 == 0 ? 1.0 : 0.0) != 0.0 && (double)n_pos <= (double)grid * per_wg;
+    }
     hipStream_t st = k.st;
-    const size_t words = 4 * (size_t)k.nc;
+    const size_t words = (held_q ? 6 : 4) * (size_t)k.nc;  // (both turn kernels of a mixed solve use the one box: the tags tell)
     if (!held_z_box || held_z_words < words) {
         ledger::dev_free(held_z_box);
         held_z_box = nullptr;
@@ -767,6 +800,11 @@ int ogl_solver::plan_held_z(KrylovRun &k)
     k.hz.x_early = prop("heldZEarlyX", 1.0) != 0.0 ? 1 : 0;
     props["heldZInUse"] = 1.0;
     props["heldZGridInUse"] = (double)grid;
+    if (held_q) {
+        k.hq.on = 1;
+        k.hq.n_pos = n_pos;
+        props["heldQInUse"] = 1.0;
+    }
     return OGL_OK;
 }
 
@@ -908,7 +946,7 @@ int ogl_solver::krylov_enqueue(KrylovRun &k, int count)
         else if (k.fused2)
             OGL_TRY(turn_cg_two_launch(k, enq, pe));
         else if (k.held_z())
-            OGL_TRY(turn_cg_held_z(k, enq, pe));
+            OGL_TRY(k.hq.on ? turn_cg_held_q(k, enq, pe) : turn_cg_held_z(k, enq, pe));
         else if (k.fused)
             OGL_TRY(turn_cg_three_launch(k, enq, pe));
         else if (k.merged)
@@ -977,6 +1015,7 @@ int ogl_solver::krylov_loop(KrylovRun &k)
         }
         visit(kh, k.lead);
         visit(kh, k.hz);
+        visit(kh, k.hq);
         const uint64_t key = kh.h;
         if (!cg_graph || key != cg_graph_key) {
             if (cg_graph) {
