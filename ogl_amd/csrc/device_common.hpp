@@ -542,30 +542,93 @@ __device__ __forceinline__ double lead_total(const double *vals, int a)
     return sum;
 }
 
-// StoppingCriterion.C:71-151 on the device.  `norm` is sum|r| over all ranks.
+// ------------------------------------------------------------------------------------------
+// The stopping criterion (StoppingCriterion.C:71-151) on values: the one place where it is written out.  k_finalize reaches
+// it through criterion_check below; the folded heads (k_cg_step1x_fin, k_cg_turn_sym, k_bicg_fold1, k_bicg_fold3) and the
+// resident turn (resident_cg_turn.hpp) call criterion_verdict from their thread 0.
+// What stays with the caller, and has to:
+//   * it reads the criterion and the scalars FIELD BY FIELD at its top (load_criterion), before its first barrier or
+//     publish.  A by-value copy of DevScalars, or a `const DevScalars &` handed down, lives in scratch memory -- that is
+//     where k_finalize's scratch comes from, and a folded kernel with scratch costs more to dispatch than the finaliser
+//     launch it saves;
+//   * in the resident kernels every workgroup has read every field before it publishes its first partial: workgroup 0
+//     overwrites the one scalar slot after the sums;
+//   * everything around the verdict: sh[] / sh_stop, which workgroup stores, launch_seq, defer_valid / t_ring, BiCGStab's
+//     stop_phase / stop_turn / omega.
+// ------------------------------------------------------------------------------------------
+struct CritVals {
+    double tolerance, rel_tol;
+    int min_iter, max_iter, frequency, export_res;
+};
+__device__ __forceinline__ CritVals load_criterion(const DevCriterion &c)
+{
+    CritVals v;
+    v.tolerance = c.tolerance;
+    v.rel_tol = c.rel_tol;
+    v.min_iter = c.min_iter;
+    v.max_iter = c.max_iter;
+    v.frequency = c.frequency;
+    v.export_res = c.export_res;
+    return v;
+}
+struct Verdict {
+    int iter, n_evals;     // after this check
+    double init_res, res;  // res: only when evaluated
+    bool evaluated;        // the norm was looked at (n_evals, init_res, res are new)
+    int stop;
+};
+// `norm` is sum|r| over all ranks; `history`: null unless the caller is the workgroup that exports -- the store
+// history[iter] = res is the only memory access in here.
+__device__ __forceinline__ Verdict criterion_verdict(const CritVals &c, int iter, int n_evals, double init_res,
+                                                     double norm_factor, double norm, double *history)
+{
+    Verdict v;
+    v.iter = iter + 1;  // :143 (and :80, :86)
+    v.n_evals = n_evals;
+    v.init_res = init_res;
+    v.res = 0.0;
+    v.stop = 0;
+    v.evaluated = false;
+    if (iter > 0 && iter < c.min_iter) return v;  // :77-81
+    if (iter % c.frequency != 0) return v;        // :84-87
+    v.evaluated = true;
+    v.n_evals = n_evals + 1;
+    double res = norm;
+    if (iter == 0) v.init_res = res / norm_factor;                  // :102-111 (norm_factor set before)
+    res /= norm_factor;                                             // :113
+    if (c.export_res && history) history[iter] = res;               // :115-117
+    v.res = res;                                                    // :119
+    if (iter >= c.max_iter) v.stop = 1;                             // :124
+    if (res < c.tolerance) v.stop = 1;                              // :128
+    if (c.rel_tol > 0 && res < c.rel_tol * v.init_res) v.stop = 1;  // :132-136
+    return v;
+}
+// the verdict's stores, shared by the folded heads: iter always, the norm's three only when evaluated, stop only when set
+__device__ __forceinline__ void store_verdict(DevScalars *s, const Verdict &v)
+{
+    s->iter = v.iter;
+    if (v.evaluated) {
+        s->n_evals = v.n_evals;
+        s->init_res = v.init_res;
+        s->res = v.res;
+    }
+    if (v.stop) s->stop = 1;
+}
+// the same on k_finalize's private copy of the scalars: load fields, call, store fields -- with the stores it always had
+// (n_evals, init_res at the first check, res only when evaluated; stop only when set)
 __device__ inline void criterion_check(DevScalars *s, const DevCriterion &c, double norm, double *history)
 {
     const int iter = s->iter;
-    if (iter > 0 && iter < c.min_iter) {  // :77-81
-        s->iter = iter + 1;
+    const Verdict v = criterion_verdict(load_criterion(c), iter, s->n_evals, s->init_res, s->norm_factor, norm, history);
+    if (!v.evaluated) {
+        s->iter = v.iter;
         return;
     }
-    if (iter % c.frequency != 0) {  // :84-87
-        s->iter = iter + 1;
-        return;
-    }
-    s->n_evals += 1;
-    double res = norm;
-    if (iter == 0) s->init_res = res / s->norm_factor;  // :102-111 (norm_factor set before)
-    res /= s->norm_factor;                              // :113
-    if (c.export_res && history) history[iter] = res;   // :115-117
-    s->res = res;                                       // :119
-    bool stop = false;
-    if (iter >= c.max_iter) stop = true;                                  // :124
-    if (res < c.tolerance) stop = true;                                   // :128
-    if (c.rel_tol > 0 && res < c.rel_tol * s->init_res) stop = true;      // :132-136
-    s->iter = iter + 1;                                                   // :143
-    if (stop) s->stop = 1;
+    s->n_evals = v.n_evals;
+    if (iter == 0) s->init_res = v.init_res;
+    s->res = v.res;
+    s->iter = v.iter;
+    if (v.stop) s->stop = 1;
 }
 
 // Peer-write all-reduce (PeerArgs, kernels.hpp).  Called by every thread of a workgroup of >= 64

@@ -470,7 +470,9 @@ void launch_cg_step2r_fin(hipStream_t st, int32_t n, double *r, const double *q,
                           const double *part_beta, double *z_out = nullptr,  // z_out: z = r / d kept for k_cg_turn_sym
                           const LeadBox &lead = LeadBox{});
 // The held-z turn (kernels_krylov.hip, k_cg_step2r1x): step_2r_fin of a turn and step_1x_fin of the next in one resident
-// kernel that keeps z = r / d on chip.  `s` is read and rewritten in place; launch_seq advances by two.
+// kernel that keeps z = r / d on chip.  `s` is read and rewritten in place; launch_seq advances by two.  Its phases behind
+// the sum of beta are one body with the held-q turn's (resident_cg_turn.hpp); the check in it, as in every kernel that
+// checks, is criterion_verdict (device_common.hpp).
 struct HeldZ {
     unsigned long long *tagged = nullptr;  // 4 words per chunk, fine-grained: the chunk's two partials as tagged half-words
     int32_t grid = 0;                      // workgroups, all resident at once; each owns chunks w, w + grid, ...
@@ -484,9 +486,10 @@ int launch_resident_census(hipStream_t st, int grid, unsigned *arrived, int *out
 void launch_cg_step2r1x(hipStream_t st, int32_t n, double *r, const double *q, const double *inv_diag, double *p,
                         double *p_out, double *x, DevScalars *s, const double *part_beta, double *history,
                         const LeadBox &lead, const PRing &ring, const HeldZ &hz);
-// The held-q turn (kernels_spmv_sym.hip, k_cg_turn_held_q): the half-storage SpMV in front of that kernel, one launch per
-// turn -- q = A p stays on chip across the sum beta = p.q as z does across the later two.  The workgroups own POSITIONS of
-// the layout's launch order (slot i of workgroup w: position w + i grid), so the tagged box has 6 words per chunk.
+// The held-q turn (kernels_spmv_sym.hip, k_cg_turn_held_q): the half-storage SpMV in front of that kernel's body, one
+// launch per turn -- q = A p stays on chip across the sum beta = p.q as z does across the later two.  The workgroups own
+// POSITIONS of the layout's launch order (slot i of workgroup w: position w + i grid), so the tagged box has 6 words per
+// chunk.
 struct HeldQ {
     int32_t on = 0;     // 1: the turns without an event pair run the one-launch kernel
     int32_t n_pos = 0;  // positions of the launch order (DevSym::n_blocks, or xcd_grid(chunks) without a band order)

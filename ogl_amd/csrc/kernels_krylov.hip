@@ -1,6 +1,7 @@
 // kernels_krylov.hip -- vector steps of GKOCG / GKOBiCGStab / GKOGMRES, per-chunk partials and the finalisers
 // (geometry, reduction tree and the -ffp-contract=off rule: device_common.hpp)
 #include "device_common.hpp"
+#include "resident_cg_turn.hpp"
 
 namespace ogl {
 
@@ -342,9 +343,7 @@ __global__ __launch_bounds__(BLOCK) void k_cg_step1x_fin(int n, double *p, doubl
 #pragma unroll
     for (int i = 1; i < KQ; ++i) s_t[i] = sin->t_ring[i];
     const int s_iter = sin->iter, s_evals = sin->n_evals;
-    const double c_tol = sin->crit.tolerance, c_rel = sin->crit.rel_tol;
-    const int c_min = sin->crit.min_iter, c_max = sin->crit.max_iter, c_freq = sin->crit.frequency,
-              c_exp = sin->crit.export_res;
+    const CritVals crit = load_criterion(sin->crit);
     static_assert(sizeof(DevScalars) % 8 == 0, "copied as 8-byte words");
     if (blockIdx.x == 0 && threadIdx.x < sizeof(DevScalars) / 8)  // fields this kernel leaves alone
         reinterpret_cast<unsigned long long *>(sout)[threadIdx.x] =
@@ -417,27 +416,11 @@ __global__ __launch_bounds__(BLOCK) void k_cg_step1x_fin(int n, double *p, doubl
         reduce_partials_as_finaliser<2>(pv, n_part, red, v);  // (its barriers order the copy above before the stores below)
     }
     if (threadIdx.x == 0) {
-        // FIN_CG_CHECK: swap(prev_rho, rho) of the previous turn, then criterion_check (StoppingCriterion.C:71-151)
+        // FIN_CG_CHECK: swap(prev_rho, rho) of the previous turn, then the criterion
         const double prev_rho = s_rho, rho = v[0];
-        int iter = s_iter, n_evals = s_evals, stop = 0;
-        double init_res = s_init, res = 0.0;
-        bool evaluated = false;
-        if (iter > 0 && iter < c_min) {           // :77-81
-            iter += 1;
-        } else if (iter % c_freq != 0) {          // :84-87
-            iter += 1;
-        } else {
-            evaluated = true;
-            n_evals += 1;
-            res = v[1];
-            if (iter == 0) init_res = res / s_nf;  // :102-111
-            res /= s_nf;                           // :113
-            if (c_exp && history && blockIdx.x == 0) history[iter] = res;  // :115-117
-            if (iter >= c_max) stop = 1;                                   // :124
-            if (res < c_tol) stop = 1;                                     // :128
-            if (c_rel > 0 && res < c_rel * init_res) stop = 1;             // :132-136
-            iter += 1;                                                     // :143
-        }
+        const Verdict cv =
+            criterion_verdict(crit, s_iter, s_evals, s_init, s_nf, v[1], blockIdx.x == 0 ? history : nullptr);
+        const int stop = cv.stop;
         sh[0] = s_beta;
         sh[1] = prev_rho;
         sh[2] = rho;
@@ -445,14 +428,8 @@ __global__ __launch_bounds__(BLOCK) void k_cg_step1x_fin(int n, double *p, doubl
         if (blockIdx.x == 0) {
             sout->prev_rho = prev_rho;
             sout->rho = rho;
-            sout->iter = iter;
             sout->x_pending = 0;
-            if (evaluated) {
-                sout->n_evals = n_evals;
-                sout->init_res = init_res;
-                sout->res = res;
-            }
-            if (stop) sout->stop = 1;
+            store_verdict(sout, cv);
             if (LEAD) sout->launch_seq = seq + 1;
             // what is pending after this head (nothing when it has updated x itself or stops)
             sout->defer_valid = (defers && !stop) ? (int)(s_pending | (own_term ? 1u << phase : 0u)) : 0;
@@ -591,18 +568,32 @@ __global__ __launch_bounds__(BLOCK) void k_cg_step2r_fin(int n, double *__restri
 //   grid: G = CUs x B workgroups, all resident at once (the host asks the occupancy and runs a census launch first);
 //   workgroup w owns chunks w, w + G, w + 2 G, ... (one streaming front, as the chunk = block kernels have), at most
 //   R + L of them: z of the first R in registers (compile-time indexed), of the next L in LDS.
-//   phase 1 (step_2r): beta from the leaders as in k_cg_step2r_fin; r' = r - t q stored; the chunk's two partials -- same
+//   phase R (step_2r): beta from the leaders as in k_cg_step2r_fin; r' = r - t q stored; the chunk's two partials -- same
 //     tree as everywhere -- go out as tagged half-words [tag : 32 | payload : 32] in fine-grained memory, no fence;
 //   sums: the first 2 x 16 workgroups are the finaliser's wavefronts once more: they POLL the tagged partials of their
 //     virtual threads, add them in lead_wave_sums' order and publish to the LeadBox; everybody polls the box.  No vector
 //     data crosses workgroups, so nobody needs a release;
-//   phase 2 (head): the check on every workgroup's own copy of the scalars (workgroup 0 stores them), x += ... on a head
-//     that does not defer (before the wait when x_early: it needs the incoming rho and phase 1's beta only), and
+//   phase H (head): the check on every workgroup's own copy of the scalars (workgroup 0 stores them), x += ... on a head
+//     that does not defer (before the wait when x_early: it needs the incoming rho and phase R's beta only), and
 //     p_new = z + (rho / rho') p with the z kept.
 // The scalars stay in ONE slot: every workgroup has read every field it needs before it publishes its first partial (the
 // barriers of block_sum2 stand between), and workgroup 0 writes only after it has seen the sums of ALL partials.
 // Every spin is bounded by lead.timeout_ticks and ends the solve with comm_error.
+// Everything behind the leaders of beta is the body that the held-q turn (kernels_spmv_sym.hip) runs too:
+// resident_cg_turn.hpp.
 // ------------------------------------------------------------------------------------------
+// the held-z turn's slots: workgroup w owns chunks w, w + G, ...; q of a chunk is in memory; 4 tagged words per chunk
+struct HeldZSrc {
+    static constexpr bool Q_HELD = false;
+    static constexpr int STRIDE = 4, WORD = 0;
+    int G, n_partials;
+    const double *__restrict__ q;
+    __device__ __forceinline__ int chunk_of(int i) const
+    {
+        const int c = blockIdx.x + i * G;
+        return c < n_partials ? c : -1;
+    }
+};
 template <int R, int L, int B, int K>
 __global__ __launch_bounds__(BLOCK, B) void k_cg_step2r1x(int n, double *__restrict__ r, const double *__restrict__ q,
                                                           const double *__restrict__ inv_diag, double *p, double *p_out,
@@ -612,189 +603,21 @@ __global__ __launch_bounds__(BLOCK, B) void k_cg_step2r1x(int n, double *__restr
                                                           LeadBox lead, const double *p_pend, int ring_phase,
                                                           int x_early)
 {
-    // (p_pend, ring_phase: PRing::b[1] and PRing::phase of the head in here -- the whole ring would cost 16 SGPRs)
-    static_assert(K == 0 || K == 2, "p in place or two p buffers");
-    constexpr int D = 2;  // chunks whose rows are in flight ahead of the one at work
     __shared__ double zl[L > 0 ? L * CHUNK_ROWS : 1];
-    __shared__ double sh[4];
-    __shared__ int sh_stop;
-    __shared__ double slot[2 * N_WAVES];
-    __shared__ double lead_words[LEAD_BOX_WORDS / 2];
-    __shared__ int lead_timed_out;
-    static_assert(L * CHUNK_ROWS >= LEAD_STAGE, "the leaders of beta stage through zl, which is idle until phase 1");
-    const uint32_t seq = s->launch_seq;
-    lead_leaders<1>(lead, seq, part_beta, nullptr, nullptr, n_part, zl);  // (as step_2r_fin)
-    const int stopped = s->stop;
-    const double s_rho = s->rho, s_nf = s->norm_factor, s_init = s->init_res;
-    const int phase = K > 0 ? ring_phase : 0;
-    const bool defers = K > 0 && phase != 0;
-    const unsigned s_pending = K > 0 ? (unsigned)s->defer_valid : 0u;
-    const double s_t1 = K > 0 ? s->t_ring[1] : 0.0;
-    const int s_iter = s->iter, s_evals = s->n_evals;
-    const double c_tol = s->crit.tolerance, c_rel = s->crit.rel_tol;
-    const int c_min = s->crit.min_iter, c_max = s->crit.max_iter, c_freq = s->crit.frequency, c_exp = s->crit.export_res;
-    const int G = gridDim.x, w = blockIdx.x, tx = threadIdx.x;
-    const int mine = w < n_part ? (n_part - w + G - 1) / G : 0;  // chunks of this workgroup (<= R + L: the launcher's cap)
-    double2 fr[D], fq[D], fi[D];
-    auto ask = [&](int i, int d) {  // (past the last chunk: no rows, no loads)
-        const RowPair rp = my_rows(w + i * G, n);
-        fr[d] = ld2(r, rp);
-        fq[d] = ld2_stream(q, rp);
-        fi[d].x = fi[d].y = 1.0;
-        if (inv_diag) fi[d] = ld2_stream(inv_diag, rp);  // its only use in the turn
-    };
-#pragma unroll
-    for (int d = 0; d < D; ++d) ask(d, d);
-    if (stopped) return;  // (every workgroup sees the same flag: nobody polls, nobody writes)
-    if (!lead_wait(lead, 2 * FIN_WAVES, seq, lead_words, &lead_timed_out)) {
-        if (tx == 0) s->comm_error = s->stop = 1;
-        return;
-    }
-    if (tx == 0) sh[0] = lead_total(lead_words, 0);
-    __syncthreads();
-    const double beta = sh[0];  // FIN_BETA
-    const uint32_t tag = seq + 1;
-    double2 zr[R];
-#pragma unroll
-    for (int i = 0; i < R + L; ++i) {
-        if (i >= mine) continue;  // (workgroup-uniform; no break: the loop must unroll, zr[] is indexed at compile time)
-        const int chunk = w + i * G;
-        const RowPair rp = my_rows(chunk, n);
-        double2 vr = fr[i % D];
-        const double2 vq = fq[i % D], vi = fi[i % D];
-        if (i + D < R + L) ask(i + D, i % D);
-        if (beta != 0.0) {
-            const double t = s_rho / beta;
-            vr.x -= t * vq.x;
-            vr.y -= t * vq.y;
-            st2(r, rp, vr);
-        }
-        double2 vz = vr;
-        if (inv_diag) {
-            vz.x = vr.x * vi.x;
-            vz.y = vr.y * vi.y;
-        }
-        if (i < R) {
-            zr[i < R ? i : 0] = vz;
-        } else {
-            zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx] = vz.x;
-            zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx + 1] = vz.y;
-        }
-        double d = 0.0, a = 0.0;
-        if (rp.n > 0) {
-            d += vr.x * vz.x;
-            a += fabs(vr.x);
-        }
-        if (rp.n > 1) {
-            d += vr.y * vz.y;
-            a += fabs(vr.y);
-        }
-        block_sum2(d, a, slot);
-        if (tx == 0) {
-            put_tagged(tagged + 4 * (size_t)chunk, tag, d);
-            put_tagged(tagged + 4 * (size_t)chunk + 2, tag, a);
-        }
-    }
-    // the sums of all partials: workgroup b < 32 is wavefront b % 16 of the finaliser for array b / 16
-    // (into arrays 1 and 2 of the mailbox: array 0 keeps beta for a workgroup that still polls for it -- one that owns no
-    // chunk holds nobody's sums back)
-    if (w < 2 * FIN_WAVES)
-        lead_wave_sums_tagged(lead, tag, tagged + 2 * (w / FIN_WAVES), 4, n_part, w % FIN_WAVES, 1 + w / FIN_WAVES);
-    // this head's term of x and the terms pending before it: ((x + t_1 p_1) + t p), the bits of single updates
-    const bool own_term = beta != 0.0;
-    const double t_own = own_term ? s_rho / beta : 0.0;
-    auto update_x = [&](const RowPair &rp, const double2 &vp, int upto) {
-        const bool pend = K > 1 && 1 < upto && ((s_pending >> 1) & 1u);
-        if (!pend && !own_term) return;
-        double2 vx = ld2_stream(x, rp);
-        if (pend) {
-            const double2 v1 = ld2(p_pend, rp);
-            vx.x += s_t1 * v1.x;
-            vx.y += s_t1 * v1.y;
-        }
-        if (own_term) {
-            vx.x += t_own * vp.x;
-            vx.y += t_own * vp.y;
-        }
-        st2_stream(x, rp, vx);
-    };
-    const bool early = x_early != 0 && !defers;
-    if (early) {
-#pragma unroll 2
-        for (int i = 0; i < mine; ++i) {
-            const RowPair rp = my_rows(w + i * G, n);
-            update_x(rp, ld2(p, rp), K);
-        }
-    }
-    if (!lead_wait(lead, 4 * FIN_WAVES, tag, lead_words, &lead_timed_out, 2 * FIN_WAVES)) {
-        if (tx == 0) s->comm_error = s->stop = 1;
-        return;
-    }
-    if (tx == 0) {
-        // FIN_CG_CHECK, as in k_cg_step1x_fin
-        const double prev_rho = s_rho, rho = lead_total(lead_words, 0), norm = lead_total(lead_words, 1);
-        int iter = s_iter, n_evals = s_evals, stop = 0;
-        double init_res = s_init, res = 0.0;
-        bool evaluated = false;
-        if (iter > 0 && iter < c_min) {
-            iter += 1;
-        } else if (iter % c_freq != 0) {
-            iter += 1;
-        } else {
-            evaluated = true;
-            n_evals += 1;
-            res = norm;
-            if (iter == 0) init_res = res / s_nf;
-            res /= s_nf;
-            if (c_exp && history && w == 0) history[iter] = res;
-            if (iter >= c_max) stop = 1;
-            if (res < c_tol) stop = 1;
-            if (c_rel > 0 && res < c_rel * init_res) stop = 1;
-            iter += 1;
-        }
-        sh[1] = prev_rho;
-        sh[2] = rho;
-        sh_stop = stop;
-        if (w == 0) {
-            s->beta = beta;
-            s->prev_rho = prev_rho;
-            s->rho = rho;
-            s->iter = iter;
-            s->x_pending = 0;
-            if (evaluated) {
-                s->n_evals = n_evals;
-                s->init_res = init_res;
-                s->res = res;
-            }
-            if (stop) s->stop = 1;
-            s->launch_seq = seq + 2;
-            s->defer_valid = (defers && !stop) ? (int)(s_pending | (own_term ? 1u << phase : 0u)) : 0;
-            if (defers && own_term) s->t_ring[phase] = t_own;
-        }
-    }
-    __syncthreads();
-    const double prev = sh[1], rho = sh[2];
-    const int stop = sh_stop;
-    const double tmp = (prev == 0.0) ? 0.0 : rho / prev;
-#pragma unroll
-    for (int i = 0; i < R + L; ++i) {
-        if (i >= mine) continue;
-        const RowPair rp = my_rows(w + i * G, n);
-        double2 vp = ld2(p, rp);
-        if (!defers && !early) update_x(rp, vp, K);
-        if (defers && stop) update_x(rp, vp, phase);  // a deferring head that ends the solve: what is pending goes in now
-        if (stop) continue;
-        double2 vz;
-        if (i < R) {
-            vz = zr[i < R ? i : 0];
-        } else {
-            vz.x = zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx];
-            vz.y = zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx + 1];
-        }
-        vp.x = vz.x + tmp * vp.x;
-        vp.y = vz.y + tmp * vp.y;
-        st2(p_out, rp, vp);
-    }
+    __shared__ TurnLds lds;
+    static_assert(L * CHUNK_ROWS >= LEAD_STAGE, "the leaders of beta stage through zl, which is idle until phase R");
+    const TurnScalars ts = turn_prelude<K>(s, ring_phase);
+    lead_leaders<1>(lead, ts.seq, part_beta, nullptr, nullptr, n_part, zl);  // (as step_2r_fin)
+    const TurnArgs a{n, r, inv_diag, p, p_out, x, s, tagged, history, lead, p_pend, x_early};
+    const HeldZSrc src{(int)gridDim.x, n_part, q};  // (at most R + L chunks a workgroup: the launcher's cap)
+    TurnFront<HeldZSrc::Q_HELD> f;
+    turn_ask_first(src, a, f);
+    if (ts.stopped) return;  // (every workgroup sees the same flag: nobody polls, nobody writes)
+    double beta;
+    if (!turn_await_beta(a, ts, lds, beta)) return;
+    TurnSlots<R, L> z;
+    z.zl = zl;
+    resident_cg_turn<R, L, K>(src, a, ts, lds, z, f, beta);
 }
 
 // Census of a resident grid: every workgroup arrives and waits, bounded, until all have.  *out = 1 when some workgroup
@@ -981,9 +804,7 @@ __global__ __launch_bounds__(BLOCK) void k_bicg_fold1(int n, double *__restrict_
     const double s_rho = sin->rho, alpha = sin->alpha, omega = sin->omega, s_nf = sin->norm_factor,
                  s_init = sin->init_res;
     const int s_iter = sin->iter, s_evals = sin->n_evals;
-    const double c_tol = sin->crit.tolerance, c_rel = sin->crit.rel_tol;
-    const int c_min = sin->crit.min_iter, c_max = sin->crit.max_iter, c_freq = sin->crit.frequency,
-              c_exp = sin->crit.export_res;
+    const CritVals crit = load_criterion(sin->crit);
     if (blockIdx.x == 0 && threadIdx.x < sizeof(DevScalars) / 8)  // fields this kernel leaves alone
         reinterpret_cast<unsigned long long *>(sout)[threadIdx.x] =
             reinterpret_cast<const unsigned long long *>(sin)[threadIdx.x];
@@ -1010,41 +831,18 @@ __global__ __launch_bounds__(BLOCK) void k_bicg_fold1(int n, double *__restrict_
         reduce_partials_as_finaliser<2>(pv, n_part, red, vsum);
     }
     if (threadIdx.x == 0) {
-        // FIN_CG_CHECK: swap(prev_rho, rho) of the previous turn, then criterion_check (StoppingCriterion.C:71-151)
+        // FIN_CG_CHECK: swap(prev_rho, rho) of the previous turn, then the criterion
         const double prev_rho = s_rho, rho = vsum[0];
-        int iter = s_iter, n_evals = s_evals, stop = 0;
-        double init_res = s_init, res = 0.0;
-        bool evaluated = false;
-        if (iter > 0 && iter < c_min) {           // :77-81
-            iter += 1;
-        } else if (iter % c_freq != 0) {          // :84-87
-            iter += 1;
-        } else {
-            evaluated = true;
-            n_evals += 1;
-            res = vsum[1];
-            if (iter == 0) init_res = res / s_nf;  // :102-111
-            res /= s_nf;                           // :113
-            if (c_exp && history && blockIdx.x == 0) history[iter] = res;  // :115-117
-            if (iter >= c_max) stop = 1;                                   // :124
-            if (res < c_tol) stop = 1;                                     // :128
-            if (c_rel > 0 && res < c_rel * init_res) stop = 1;             // :132-136
-            iter += 1;                                                     // :143
-        }
+        const Verdict cv =
+            criterion_verdict(crit, s_iter, s_evals, s_init, s_nf, vsum[1], blockIdx.x == 0 ? history : nullptr);
         sh[0] = prev_rho;
         sh[1] = rho;
-        sh_stop = stop;
+        sh_stop = cv.stop;
         if (blockIdx.x == 0) {
             sout->prev_rho = prev_rho;
             sout->rho = rho;
-            sout->iter = iter;
             sout->x_pending = 0;
-            if (evaluated) {
-                sout->n_evals = n_evals;
-                sout->init_res = init_res;
-                sout->res = res;
-            }
-            if (stop) sout->stop = 1;
+            store_verdict(sout, cv);
             if (LEAD) sout->launch_seq = seq + 1;
         }
     }
@@ -1163,9 +961,7 @@ __global__ __launch_bounds__(BLOCK) void k_bicg_fold3(int n, double *__restrict_
     const int stopped = sin->stop;
     const double alpha = sin->alpha, s_nf = sin->norm_factor, s_init = sin->init_res;
     const int s_iter = sin->iter, s_evals = sin->n_evals;
-    const double c_tol = sin->crit.tolerance, c_rel = sin->crit.rel_tol;
-    const int c_min = sin->crit.min_iter, c_max = sin->crit.max_iter, c_freq = sin->crit.frequency,
-              c_exp = sin->crit.export_res;
+    const CritVals crit = load_criterion(sin->crit);
     if (blockIdx.x == 0 && threadIdx.x < sizeof(DevScalars) / 8)
         reinterpret_cast<unsigned long long *>(sout)[threadIdx.x] =
             reinterpret_cast<const unsigned long long *>(sin)[threadIdx.x];
@@ -1196,39 +992,16 @@ __global__ __launch_bounds__(BLOCK) void k_bicg_fold3(int n, double *__restrict_
         reduce_partials_as_finaliser<1>(pn, n_part, red, vnorm);
     }
     if (threadIdx.x == 0) {
-        // the mid-turn check on s (criterion_check, StoppingCriterion.C:71-151), then gamma = s.t, beta = t.t,
-        // omega = gamma / beta unless it stopped
-        int iter = s_iter, n_evals = s_evals, stop = 0;
-        double init_res = s_init, res = 0.0;
-        bool evaluated = false;
-        if (iter > 0 && iter < c_min) {
-            iter += 1;
-        } else if (iter % c_freq != 0) {
-            iter += 1;
-        } else {
-            evaluated = true;
-            n_evals += 1;
-            res = vnorm[0];
-            if (iter == 0) init_res = res / s_nf;
-            res /= s_nf;
-            if (c_exp && history && blockIdx.x == 0) history[iter] = res;
-            if (iter >= c_max) stop = 1;
-            if (res < c_tol) stop = 1;
-            if (c_rel > 0 && res < c_rel * init_res) stop = 1;
-            iter += 1;
-        }
+        // the mid-turn check on s (the criterion on sum|s|), then gamma = s.t, beta = t.t, omega = gamma / beta unless
+        // it stopped
+        const Verdict cv =
+            criterion_verdict(crit, s_iter, s_evals, s_init, s_nf, vnorm[0], blockIdx.x == 0 ? history : nullptr);
         const double omega = (vsum[1] != 0.0) ? vsum[0] / vsum[1] : 0.0;
         sh[0] = omega;
-        sh_stop = stop;
+        sh_stop = cv.stop;
         if (blockIdx.x == 0) {
-            sout->iter = iter;
-            if (evaluated) {
-                sout->n_evals = n_evals;
-                sout->init_res = init_res;
-                sout->res = res;
-            }
-            if (stop) {
-                sout->stop = 1;
+            store_verdict(sout, cv);
+            if (cv.stop) {
                 sout->stop_phase = 1;
                 sout->stop_turn = turn;
             } else {

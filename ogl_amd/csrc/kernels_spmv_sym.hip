@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "device_common.hpp"
+#include "resident_cg_turn.hpp"
 
 namespace ogl {
 
@@ -21,6 +22,16 @@ namespace {
 struct SymOffsets {
     int d[SYM_MAX_OFFSETS];
 };
+// the distances of a layout as a kernel argument; *fast: d[1] == 1 and the further distances even -- the straight-line
+// pair-load instantiations (FAST, below)
+SymOffsets sym_offsets(const DevSym &A, bool *fast)
+{
+    SymOffsets off;
+    for (int j = 0; j < SYM_MAX_OFFSETS; ++j) off.d[j] = A.d[j];
+    *fast = A.nd >= 2 && A.d[1] == 1;
+    for (int j = 2; j < A.nd; ++j) *fast = *fast && (A.d[j] % 2 == 0);
+    return off;
+}
 // FAST: d[1] == 1 and every further distance even (a box with an even line length) -- known at compile
 // time, so the kernel stays straight-line code (a run-time test of the parity splits the loads into basic
 // blocks that wait for each other: 130 us instead of 113, tools/sym_tune.hip var1/var2).  Then the two rows
@@ -312,9 +323,7 @@ __global__ __launch_bounds__(BLOCK) void k_cg_turn_sym(int n_rows, int n_chunks,
     const int stopped = sin->stop;
     const double s_rho = sin->rho, s_beta = sin->beta, s_nf = sin->norm_factor, s_init = sin->init_res;
     const int s_iter = sin->iter, s_evals = sin->n_evals;
-    const double c_tol = sin->crit.tolerance, c_rel = sin->crit.rel_tol;
-    const int c_min = sin->crit.min_iter, c_max = sin->crit.max_iter, c_freq = sin->crit.frequency,
-              c_exp = sin->crit.export_res;
+    const CritVals crit = load_criterion(sin->crit);
     if (lead && threadIdx.x < sizeof(DevScalars) / 8)
         reinterpret_cast<unsigned long long *>(sout)[threadIdx.x] =
             reinterpret_cast<const unsigned long long *>(sin)[threadIdx.x];
@@ -341,42 +350,18 @@ __global__ __launch_bounds__(BLOCK) void k_cg_turn_sym(int n_rows, int n_chunks,
         reduce_partials_as_finaliser<2>(pv, n_part, red, v);
     }
     if (threadIdx.x == 0) {
-        // FIN_CG_CHECK as in k_cg_step1x_fin (StoppingCriterion.C:71-151)
+        // FIN_CG_CHECK: swap(prev_rho, rho) of the previous turn, then the criterion
         const double prev_rho = s_rho, rho = v[0];
-        int iter = s_iter, n_evals = s_evals, stop = 0;
-        double init_res = s_init, res = 0.0;
-        bool evaluated = false;
-        if (iter > 0 && iter < c_min) {           // :77-81
-            iter += 1;
-        } else if (iter % c_freq != 0) {          // :84-87
-            iter += 1;
-        } else {
-            evaluated = true;
-            n_evals += 1;
-            res = v[1];
-            if (iter == 0) init_res = res / s_nf;  // :102-111
-            res /= s_nf;                           // :113
-            if (c_exp && history && lead) history[iter] = res;  // :115-117
-            if (iter >= c_max) stop = 1;                        // :124
-            if (res < c_tol) stop = 1;                          // :128
-            if (c_rel > 0 && res < c_rel * init_res) stop = 1;  // :132-136
-            iter += 1;                                          // :143
-        }
+        const Verdict cv = criterion_verdict(crit, s_iter, s_evals, s_init, s_nf, v[1], lead ? history : nullptr);
         sh[0] = s_beta;
         sh[1] = prev_rho;
         sh[2] = rho;
-        sh_stop = stop;
+        sh_stop = cv.stop;
         if (lead) {
             sout->prev_rho = prev_rho;
             sout->rho = rho;
-            sout->iter = iter;
             sout->x_pending = 0;
-            if (evaluated) {
-                sout->n_evals = n_evals;
-                sout->init_res = init_res;
-                sout->res = res;
-            }
-            if (stop) sout->stop = 1;
+            store_verdict(sout, cv);
             if (LEAD) sout->launch_seq = seq + 1;
         }
     }
@@ -473,9 +458,9 @@ __global__ __launch_bounds__(BLOCK) void k_cg_turn_sym_big(int n_rows, int n_chu
 
 // ------------------------------------------------------------------------------------------
 // The held-q turn (streamed single-rank GKOCG on half storage, scalar Jacobi or none): the SpMV in front of the held-z
-// kernel (kernels_krylov.hip, k_cg_step2r1x), ONE launch per turn.  q = A p, which the SpMV would write and step_2r read
-// back (16 N bytes per turn), stays where z will be: in registers (R slots per workgroup) and LDS (L slots); only the
-// grid-wide sum beta = p.q stands between the two.
+// turn (kernels_krylov.hip, k_cg_step2r1x; the body both kernels run: resident_cg_turn.hpp), ONE launch per turn.
+// q = A p, which the SpMV would write and step_2r read back (16 N bytes per turn), stays where z will be: in registers
+// (R slots per workgroup) and LDS (L slots); only the grid-wide sum beta = p.q stands between the two.
 //   turn = [ S: q = A p, held | beta | R: r' = r - t q, z in q's place | rho, sum |r'| | H: check, x, p_new ]
 //   slot i of workgroup w holds the chunk at POSITION w + i G of the SpMV's launch order (the band order with its -1
 //   holes, or xcd_chunk): with G a multiple of 8 a chunk's far neighbours sit on its own XCD, as in the stand-alone SpMV.
@@ -484,11 +469,26 @@ __global__ __launch_bounds__(BLOCK) void k_cg_turn_sym_big(int n_rows, int n_chu
 //   The same map in all three phases; holes and positions past the end own nothing.
 //   phase S: sym_rows on p; the chunk's partial of p.q goes out as a tagged word (6 words per chunk: beta | rho | sum|r'|),
 //     tag `seq`.  Sixteen workgroups poll those partials in the finaliser's order (lead_wave_sums_tagged: the bits of
-//     lead_leaders<1> over the stand-alone SpMV's partials) and publish where k_cg_step2r1x's first wait looks.
-//   phases R, the sums, H: k_cg_step2r1x's, with q from the slot.  With K = 0, H overwrites p in place: beta is complete
+//     lead_leaders<1> over the stand-alone SpMV's partials) and publish where the body's first wait looks.
+//   phases R, the sums, H: the shared body, with q from the slot.  With K = 0, H overwrites p in place: beta is complete
 //     only after every workgroup has finished S, and nobody passes the first wait before.
 // A stopped solve returns before any poll; every spin is bounded by lead.timeout_ticks and ends the solve with comm_error.
 // ------------------------------------------------------------------------------------------
+// the held-q turn's slots: positions of the SpMV's launch order with their holes; q of a chunk is in its slot; 6 tagged
+// words per chunk (beta | rho | sum|r'|)
+struct HeldQSrc {
+    static constexpr bool Q_HELD = true;
+    static constexpr int STRIDE = 6, WORD = 2;
+    int G, n_pos, n_partials;
+    const int *__restrict__ block_order;
+    __device__ __forceinline__ int chunk_of(int i) const  // -1: a hole of the order or a position past its end
+    {
+        const int pos = blockIdx.x + i * G;
+        if (pos >= n_pos) return -1;
+        const int c = block_order ? block_order[pos] : xcd_chunk(pos);
+        return c < n_partials ? c : -1;
+    }
+};
 template <int R, int L, int B, int K, int ND, bool FAST>
 __global__ __launch_bounds__(BLOCK, B) void k_cg_turn_held_q(int n, int n_chunks, int n_pos, SymOffsets off,
                                                              const uint8_t *__restrict__ mask,
@@ -499,235 +499,41 @@ __global__ __launch_bounds__(BLOCK, B) void k_cg_turn_held_q(int n, int n_chunks
                                                              unsigned long long *tagged, double *history, LeadBox lead,
                                                              const double *p_pend, int ring_phase, int x_early)
 {
-    static_assert(K == 0 || K == 2, "p in place or two p buffers");
-    constexpr int D = 2;   // chunks whose rows are in flight ahead of the one at work (phase R)
-    constexpr int TW = 6;  // tagged words per chunk
     __shared__ double zl[L > 0 ? L * CHUNK_ROWS : 1];
-    __shared__ double sh[4];
-    __shared__ int sh_stop;
-    __shared__ double slot[2 * N_WAVES];
-    __shared__ double lead_words[LEAD_BOX_WORDS / 2];
-    __shared__ int lead_timed_out;
-    const uint32_t seq = s->launch_seq;
-    const int stopped = s->stop;
-    const double s_rho = s->rho, s_nf = s->norm_factor, s_init = s->init_res;
-    const int phase = K > 0 ? ring_phase : 0;
-    const bool defers = K > 0 && phase != 0;
-    const unsigned s_pending = K > 0 ? (unsigned)s->defer_valid : 0u;
-    const double s_t1 = K > 0 ? s->t_ring[1] : 0.0;
-    const int s_iter = s->iter, s_evals = s->n_evals;
-    const double c_tol = s->crit.tolerance, c_rel = s->crit.rel_tol;
-    const int c_min = s->crit.min_iter, c_max = s->crit.max_iter, c_freq = s->crit.frequency, c_exp = s->crit.export_res;
-    const int G = gridDim.x, w = blockIdx.x, tx = threadIdx.x;
-    if (stopped) return;  // (every workgroup sees the same flag: nobody polls, nobody writes)
-    auto chunk_of = [&](int i) -> int {  // the chunk of slot i, -1: a hole of the order or a position past its end
-        const int pos = w + i * G;
-        if (pos >= n_pos) return -1;
-        const int c = block_order ? block_order[pos] : xcd_chunk(pos);
-        return c < n_chunks ? c : -1;
-    };
-    auto rows_of = [&](int chunk) -> RowPair {
-        if (chunk >= 0) return my_rows(chunk, n);
-        RowPair none;
-        none.row = none.n = 0;
-        return none;
-    };
+    __shared__ TurnLds lds;
+    const TurnScalars ts = turn_prelude<K>(s, ring_phase);
+    const TurnArgs a{n, r, inv_diag, p, p_out, x, s, tagged, history, lead, p_pend, x_early};
+    const HeldQSrc src{(int)gridDim.x, n_pos, n_chunks, block_order};
+    const int G = gridDim.x, w = blockIdx.x;
+    if (ts.stopped) return;  // (every workgroup sees the same flag: nobody polls, nobody writes)
     // phase S: q = A p of every slot's chunk, kept; the partials of p.q
-    double2 zr[R];
+    TurnSlots<R, L> z;
+    z.zl = zl;
 #pragma unroll
     for (int i = 0; i < R + L; ++i) {
-        const int chunk = chunk_of(i);
-        if (chunk < 0) continue;  // (workgroup-uniform; no break: the loop must unroll, zr[] is indexed at compile time)
+        const int chunk = src.chunk_of(i);
+        if (chunk < 0) continue;  // (workgroup-uniform; no break: the loop must unroll, see TurnSlots)
         const RowPair rp = my_rows(chunk, n);
         double2 xd;
         double2 vq = sym_rows<SPMV_PLAIN, ND, FAST, true>(chunk, rp, n, off, mask, planes, p, nullptr, xd);
         if (rp.n < 2) vq.y = 0.0;  // (rows past the end: what ld2_stream(q) gives the two-launch turn)
         if (rp.n < 1) vq.x = 0.0;
-        if (i < R) {
-            zr[i < R ? i : 0] = vq;
-        } else {
-            zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx] = vq.x;
-            zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx + 1] = vq.y;
-        }
+        z.put(i, vq);
         double d = 0.0;
         if (rp.n > 0) d += xd.x * vq.x;
         if (rp.n > 1) d += xd.y * vq.y;
-        const double sd = block_sum(d, slot);
-        if (tx == 0) put_tagged(tagged + TW * (size_t)chunk, seq, sd);
+        const double sd = block_sum(d, lds.slot);
+        if (threadIdx.x == 0) put_tagged(tagged + HeldQSrc::STRIDE * (size_t)chunk, ts.seq, sd);
     }
     // beta: sixteen workgroups -- behind the 2 x 16 of the later sums where the grid has them -- are the finaliser's wavefronts
     const int lead0 = G >= 3 * FIN_WAVES ? 2 * FIN_WAVES : 0;
-    if (w >= lead0 && w < lead0 + FIN_WAVES) lead_wave_sums_tagged(lead, seq, tagged, TW, n_chunks, w - lead0, 0);
-    double2 fr[D], fi[D];
-    auto ask = [&](int i, int d) {  // (a slot that owns nothing: no rows, no loads)
-        const RowPair rp = rows_of(chunk_of(i));
-        fr[d] = ld2(r, rp);
-        fi[d].x = fi[d].y = 1.0;
-        if (inv_diag) fi[d] = ld2_stream(inv_diag, rp);  // its only use in the turn
-    };
-#pragma unroll
-    for (int d = 0; d < D; ++d) ask(d, d);
-    if (!lead_wait(lead, 2 * FIN_WAVES, seq, lead_words, &lead_timed_out)) {
-        if (tx == 0) s->comm_error = s->stop = 1;
-        return;
-    }
-    if (tx == 0) sh[0] = lead_total(lead_words, 0);
-    __syncthreads();
-    const double beta = sh[0];  // FIN_BETA
-    const uint32_t tag = seq + 1;
-    // phase R (step_2r): r' = r - t q, z = r' / d into q's slot, the chunk's two partials
-#pragma unroll
-    for (int i = 0; i < R + L; ++i) {
-        const int chunk = chunk_of(i);
-        if (chunk < 0) {
-            if (i + D < R + L) ask(i + D, i % D);
-            continue;
-        }
-        const RowPair rp = my_rows(chunk, n);
-        double2 vr = fr[i % D];
-        const double2 vi = fi[i % D];
-        if (i + D < R + L) ask(i + D, i % D);
-        double2 vq;
-        if (i < R) {
-            vq = zr[i < R ? i : 0];
-        } else {
-            vq.x = zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx];
-            vq.y = zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx + 1];
-        }
-        if (beta != 0.0) {
-            const double t = s_rho / beta;
-            vr.x -= t * vq.x;
-            vr.y -= t * vq.y;
-            st2(r, rp, vr);
-        }
-        double2 vz = vr;
-        if (inv_diag) {
-            vz.x = vr.x * vi.x;
-            vz.y = vr.y * vi.y;
-        }
-        if (i < R) {
-            zr[i < R ? i : 0] = vz;
-        } else {  // (every thread reads and writes its own two words: no barrier)
-            zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx] = vz.x;
-            zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx + 1] = vz.y;
-        }
-        double d = 0.0, a = 0.0;
-        if (rp.n > 0) {
-            d += vr.x * vz.x;
-            a += fabs(vr.x);
-        }
-        if (rp.n > 1) {
-            d += vr.y * vz.y;
-            a += fabs(vr.y);
-        }
-        block_sum2(d, a, slot);
-        if (tx == 0) {
-            put_tagged(tagged + TW * (size_t)chunk + 2, tag, d);
-            put_tagged(tagged + TW * (size_t)chunk + 4, tag, a);
-        }
-    }
-    // the sums of all partials: workgroup b < 32 is wavefront b % 16 of the finaliser for array b / 16 (into arrays 1 and 2
-    // of the mailbox: array 0 keeps beta for a workgroup that still polls for it -- one that owns no chunk holds nobody back)
-    if (w < 2 * FIN_WAVES)
-        lead_wave_sums_tagged(lead, tag, tagged + 2 + 2 * (w / FIN_WAVES), TW, n_chunks, w % FIN_WAVES, 1 + w / FIN_WAVES);
-    // this head's term of x and the terms pending before it: ((x + t_1 p_1) + t p), the bits of single updates
-    const bool own_term = beta != 0.0;
-    const double t_own = own_term ? s_rho / beta : 0.0;
-    auto update_x = [&](const RowPair &rp, const double2 &vp, int upto) {
-        const bool pend = K > 1 && 1 < upto && ((s_pending >> 1) & 1u);
-        if (!pend && !own_term) return;
-        double2 vx = ld2_stream(x, rp);
-        if (pend) {
-            const double2 v1 = ld2(p_pend, rp);
-            vx.x += s_t1 * v1.x;
-            vx.y += s_t1 * v1.y;
-        }
-        if (own_term) {
-            vx.x += t_own * vp.x;
-            vx.y += t_own * vp.y;
-        }
-        st2_stream(x, rp, vx);
-    };
-    const bool early = x_early != 0 && !defers;
-    if (early) {
-#pragma unroll 2
-        for (int i = 0; i < R + L; ++i) {
-            const int chunk = chunk_of(i);
-            if (chunk < 0) continue;
-            const RowPair rp = my_rows(chunk, n);
-            update_x(rp, ld2(p, rp), K);
-        }
-    }
-    if (!lead_wait(lead, 4 * FIN_WAVES, tag, lead_words, &lead_timed_out, 2 * FIN_WAVES)) {
-        if (tx == 0) s->comm_error = s->stop = 1;
-        return;
-    }
-    if (tx == 0) {
-        // FIN_CG_CHECK, as in k_cg_step1x_fin
-        const double prev_rho = s_rho, rho = lead_total(lead_words, 0), norm = lead_total(lead_words, 1);
-        int iter = s_iter, n_evals = s_evals, stop = 0;
-        double init_res = s_init, res = 0.0;
-        bool evaluated = false;
-        if (iter > 0 && iter < c_min) {
-            iter += 1;
-        } else if (iter % c_freq != 0) {
-            iter += 1;
-        } else {
-            evaluated = true;
-            n_evals += 1;
-            res = norm;
-            if (iter == 0) init_res = res / s_nf;
-            res /= s_nf;
-            if (c_exp && history && w == 0) history[iter] = res;
-            if (iter >= c_max) stop = 1;
-            if (res < c_tol) stop = 1;
-            if (c_rel > 0 && res < c_rel * init_res) stop = 1;
-            iter += 1;
-        }
-        sh[1] = prev_rho;
-        sh[2] = rho;
-        sh_stop = stop;
-        if (w == 0) {
-            s->beta = beta;
-            s->prev_rho = prev_rho;
-            s->rho = rho;
-            s->iter = iter;
-            s->x_pending = 0;
-            if (evaluated) {
-                s->n_evals = n_evals;
-                s->init_res = init_res;
-                s->res = res;
-            }
-            if (stop) s->stop = 1;
-            s->launch_seq = seq + 2;
-            s->defer_valid = (defers && !stop) ? (int)(s_pending | (own_term ? 1u << phase : 0u)) : 0;
-            if (defers && own_term) s->t_ring[phase] = t_own;
-        }
-    }
-    __syncthreads();
-    const double prev = sh[1], rho = sh[2];
-    const int stop = sh_stop;
-    const double tmp = (prev == 0.0) ? 0.0 : rho / prev;
-#pragma unroll
-    for (int i = 0; i < R + L; ++i) {
-        const int chunk = chunk_of(i);
-        if (chunk < 0) continue;
-        const RowPair rp = my_rows(chunk, n);
-        double2 vp = ld2(p, rp);
-        if (!defers && !early) update_x(rp, vp, K);
-        if (defers && stop) update_x(rp, vp, phase);  // a deferring head that ends the solve: what is pending goes in now
-        if (stop) continue;
-        double2 vz;
-        if (i < R) {
-            vz = zr[i < R ? i : 0];
-        } else {
-            vz.x = zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx];
-            vz.y = zl[(i - R) * CHUNK_ROWS + ROWS_PER_THREAD * tx + 1];
-        }
-        vp.x = vz.x + tmp * vp.x;
-        vp.y = vz.y + tmp * vp.y;
-        st2(p_out, rp, vp);
-    }
+    if (w >= lead0 && w < lead0 + FIN_WAVES)
+        lead_wave_sums_tagged(lead, ts.seq, tagged, HeldQSrc::STRIDE, n_chunks, w - lead0, 0);
+    TurnFront<HeldQSrc::Q_HELD> f;
+    turn_ask_first(src, a, f);
+    double beta;
+    if (!turn_await_beta(a, ts, lds, beta)) return;
+    resident_cg_turn<R, L, K>(src, a, ts, lds, z, f, beta);
 }
 
 }  // namespace
@@ -741,11 +547,8 @@ void launch_spmv_sym(hipStream_t st, const DevSym &A, int mode, const double *x,
     if (A.n_rows == 0) return;
     const int nc = (int)n_chunks(A.n_rows);
     const dim3 grid(A.block_order ? A.n_blocks : xcd_grid(nc)), block(BLOCK);
-    SymOffsets off;
-    for (int j = 0; j < SYM_MAX_OFFSETS; ++j) off.d[j] = A.d[j];
-    // d[1] == 1 and the further distances even: the straight-line pair-load instantiation
-    bool fast = A.nd >= 2 && A.d[1] == 1;
-    for (int j = 2; j < A.nd; ++j) fast = fast && (A.d[j] % 2 == 0);
+    bool fast;
+    const SymOffsets off = sym_offsets(A, &fast);
 #define OGL_SYM_K(MODE, NDOT, ND, FAST, STREAM)                                                                          \
     hipLaunchKernelGGL((k_spmv_sym<MODE, NDOT, ND, FAST, STREAM>), grid, block, 0, st, A.n_rows, nc, off, A.mask, A.planes, \
                        x, b, y, dots.with, dots.part, dots.part_yy, gate, A.block_order, hf)
@@ -792,10 +595,8 @@ void launch_cg_turn_sym(hipStream_t st, const DevSym &A, const double *p_in, dou
     const int nc = (int)n_chunks(A.n_rows);
     const dim3 grid(A.block_order ? A.n_blocks : xcd_grid(nc)), block(BLOCK);
     const bool led = lead.box && nc >= 3 * FIN_WAVES;
-    SymOffsets off;
-    for (int j = 0; j < SYM_MAX_OFFSETS; ++j) off.d[j] = A.d[j];
-    bool fast = A.nd >= 2 && A.d[1] == 1;
-    for (int j = 2; j < A.nd; ++j) fast = fast && (A.d[j] % 2 == 0);
+    bool fast;
+    const SymOffsets off = sym_offsets(A, &fast);
 #define OGL_TURN_K(ND, FAST)                                                                                                  \
     do {                                                                                                                      \
         if (led)                                                                                                              \
@@ -831,10 +632,8 @@ void launch_cg_turn_sym_big(hipStream_t st, const DevSym &A, const double *p_in,
     if (A.n_rows == 0) return;
     const int nc = (int)n_chunks(A.n_rows);
     const dim3 grid(A.block_order ? A.n_blocks : xcd_grid(nc)), block(BLOCK);
-    SymOffsets off;
-    for (int j = 0; j < SYM_MAX_OFFSETS; ++j) off.d[j] = A.d[j];
-    bool fast = A.nd >= 2 && A.d[1] == 1;
-    for (int j = 2; j < A.nd; ++j) fast = fast && (A.d[j] % 2 == 0);
+    bool fast;
+    const SymOffsets off = sym_offsets(A, &fast);
 #define OGL_TURN_K(ND, FAST, STREAM)                                                                                \
     do {                                                                                                            \
         if (hf.chunk_bptr)                                                                                          \
@@ -903,10 +702,8 @@ void launch_cg_turn_held_q(hipStream_t st, const DevSym &A, double *r, const dou
     if (A.n_rows == 0) return;
     const int nc = (int)n_chunks(A.n_rows);
     const dim3 grid(hz.grid), block(BLOCK);
-    SymOffsets off;
-    for (int j = 0; j < SYM_MAX_OFFSETS; ++j) off.d[j] = A.d[j];
-    bool fast = A.nd >= 2 && A.d[1] == 1;
-    for (int j = 2; j < A.nd; ++j) fast = fast && (A.d[j] % 2 == 0);
+    bool fast;
+    const SymOffsets off = sym_offsets(A, &fast);
 #define OGL_HELD_Q_K(K, ND, FAST)                                                                                        \
     hipLaunchKernelGGL((OGL_HELD_Q(K, ND, FAST)), grid, block, 0, st, A.n_rows, nc, hq.n_pos, off, A.mask, A.planes,     \
                        A.block_order, r, inv_diag, p, K == 2 ? p_out : p, x, s, hz.tagged, history, lead,                \

@@ -1,8 +1,10 @@
-"""Every copy of the stopping criterion (StoppingCriterion.C:71-151) and every breakdown guard of the Krylov loop, on every
+"""Every caller of the stopping criterion (StoppingCriterion.C:71-151) and every breakdown guard of the Krylov loop, on every
 turn shape that carries one, bit for bit against the oracle run in the device's reduction tree.
 
-The criterion is written out in criterion_check (device_common.hpp, used by k_finalize), k_cg_step1x_fin, k_cg_step2r1x,
-k_bicg_fold1, k_bicg_fold3 (kernels_krylov.hip) and k_cg_turn_sym (kernels_spmv_sym.hip); Ginkgo's zero guards
+The criterion is written out once, in criterion_verdict (device_common.hpp); what each kernel does around the verdict is
+its own: k_finalize (through criterion_check), k_cg_step1x_fin, k_bicg_fold1, k_bicg_fold3 (kernels_krylov.hip),
+k_cg_turn_sym (kernels_spmv_sym.hip) and the resident turn body (resident_cg_turn.hpp) that k_cg_step2r1x and
+k_cg_turn_held_q run; Ginkgo's zero guards
 (prev_rho == 0, beta != 0, prev_rho * omega != 0, omega's v1 != 0, H(it, it) == 0) in each step kernel and finaliser.
 SHAPES names the properties that force each turn shape and the properties that prove it ran; both are set and asserted
 in every solve.  One handle per shape: the configuration changes between solves, the handle stays.

@@ -36,8 +36,9 @@ for r in range(rounds):
             sys.exit(1)
         try:
             d = json.loads(p.stdout.strip().splitlines()[-1])
-            print("round %d %-28s %8.1f it/s  spmv %6.1f us  layout %s" % (
-                r, name, d["value"], 1e3 * d["roofline"]["avg_kernel_ms"], d["roofline"]["layout"]), flush=True)
+            ms = d["roofline"]["avg_kernel_ms"]  # None where no turn is event-timed (--no-profile)
+            print("round %d %-28s %8.1f it/s  spmv %s us  layout %s" % (
+                r, name, d["value"], "%6.1f" % (1e3 * ms) if ms is not None else "   n/a", d["roofline"]["layout"]), flush=True)
         except Exception as e:
             print("round %d %-28s NO RESULT LINE (%s): stopping\n%s" % (r, name, e, p.stderr[-800:]), flush=True)
             sys.exit(1)
