@@ -476,7 +476,8 @@ void launch_cg_step2r_fin(hipStream_t st, int32_t n, double *r, const double *q,
 struct HeldZ {
     unsigned long long *tagged = nullptr;  // 4 words per chunk, fine-grained: the chunk's two partials as tagged half-words
     int32_t grid = 0;                      // workgroups, all resident at once; each owns chunks w, w + grid, ...
-    int32_t x_early = 1;                   // 1: a head that updates x does so while the sums are awaited
+    int32_t early_slots = 0;               // a head that updates x does so for its first early_slots slots while the sums are
+                                           // awaited, for the others in the loop that forms p_new (0: for all of them there)
 };
 // the geometry both resident turn kernels share: B workgroups per CU, R chunks per workgroup held in registers, L in LDS
 constexpr int HZ_B = 4, HZ_R = 11, HZ_L = 9;

@@ -574,8 +574,8 @@ __global__ __launch_bounds__(BLOCK) void k_cg_step2r_fin(int n, double *__restri
 //     virtual threads, add them in lead_wave_sums' order and publish to the LeadBox; everybody polls the box.  No vector
 //     data crosses workgroups, so nobody needs a release;
 //   phase H (head): the check on every workgroup's own copy of the scalars (workgroup 0 stores them), x += ... on a head
-//     that does not defer (before the wait when x_early: it needs the incoming rho and phase R's beta only), and
-//     p_new = z + (rho / rho') p with the z kept.
+//     that does not defer (before the wait for its first early_slots slots: it needs the incoming rho and phase R's beta
+//     only), and p_new = z + (rho / rho') p with the z kept.
 // The scalars stay in ONE slot: every workgroup has read every field it needs before it publishes its first partial (the
 // barriers of block_sum2 stand between), and workgroup 0 writes only after it has seen the sums of ALL partials.
 // Every spin is bounded by lead.timeout_ticks and ends the solve with comm_error.
@@ -601,14 +601,14 @@ __global__ __launch_bounds__(BLOCK, B) void k_cg_step2r1x(int n, double *__restr
                                                           const double *__restrict__ part_beta,
                                                           unsigned long long *tagged, int n_part, double *history,
                                                           LeadBox lead, const double *p_pend, int ring_phase,
-                                                          int x_early)
+                                                          int early_slots)
 {
     __shared__ double zl[L > 0 ? L * CHUNK_ROWS : 1];
     __shared__ TurnLds lds;
     static_assert(L * CHUNK_ROWS >= LEAD_STAGE, "the leaders of beta stage through zl, which is idle until phase R");
     const TurnScalars ts = turn_prelude<K>(s, ring_phase);
     lead_leaders<1>(lead, ts.seq, part_beta, nullptr, nullptr, n_part, zl);  // (as step_2r_fin)
-    const TurnArgs a{n, r, inv_diag, p, p_out, x, s, tagged, history, lead, p_pend, x_early};
+    const TurnArgs a{n, r, inv_diag, p, p_out, x, s, tagged, history, lead, p_pend, early_slots};
     const HeldZSrc src{(int)gridDim.x, n_part, q};  // (at most R + L chunks a workgroup: the launcher's cap)
     TurnFront<HeldZSrc::Q_HELD> f;
     turn_ask_first(src, a, f);
@@ -1584,10 +1584,10 @@ void launch_cg_step2r1x(hipStream_t st, int32_t n, double *r, const double *q, c
     if (nc == 0) return;
     if (ring.k == 2)
         hipLaunchKernelGGL((OGL_HELD_Z(2)), dim3(hz.grid), dim3(BLOCK), 0, st, n, r, q, inv_diag, p, p_out, x, s, part_beta,
-                           hz.tagged, nc, history, lead, ring.b[1], ring.phase, hz.x_early);
+                           hz.tagged, nc, history, lead, ring.b[1], ring.phase, hz.early_slots);
     else
         hipLaunchKernelGGL((OGL_HELD_Z(0)), dim3(hz.grid), dim3(BLOCK), 0, st, n, r, q, inv_diag, p, p, x, s, part_beta,
-                           hz.tagged, nc, history, lead, nullptr, 0, hz.x_early);
+                           hz.tagged, nc, history, lead, nullptr, 0, hz.early_slots);
 }
 #undef OGL_HELD_Z
 

@@ -497,12 +497,12 @@ __global__ __launch_bounds__(BLOCK, B) void k_cg_turn_held_q(int n, int n_chunks
                                                              const double *__restrict__ inv_diag, double *p, double *p_out,
                                                              double *__restrict__ x, DevScalars *s,
                                                              unsigned long long *tagged, double *history, LeadBox lead,
-                                                             const double *p_pend, int ring_phase, int x_early)
+                                                             const double *p_pend, int ring_phase, int early_slots)
 {
     __shared__ double zl[L > 0 ? L * CHUNK_ROWS : 1];
     __shared__ TurnLds lds;
     const TurnScalars ts = turn_prelude<K>(s, ring_phase);
-    const TurnArgs a{n, r, inv_diag, p, p_out, x, s, tagged, history, lead, p_pend, x_early};
+    const TurnArgs a{n, r, inv_diag, p, p_out, x, s, tagged, history, lead, p_pend, early_slots};
     const HeldQSrc src{(int)gridDim.x, n_pos, n_chunks, block_order};
     const int G = gridDim.x, w = blockIdx.x;
     if (ts.stopped) return;  // (every workgroup sees the same flag: nobody polls, nobody writes)
@@ -707,7 +707,7 @@ void launch_cg_turn_held_q(hipStream_t st, const DevSym &A, double *r, const dou
 #define OGL_HELD_Q_K(K, ND, FAST)                                                                                        \
     hipLaunchKernelGGL((OGL_HELD_Q(K, ND, FAST)), grid, block, 0, st, A.n_rows, nc, hq.n_pos, off, A.mask, A.planes,     \
                        A.block_order, r, inv_diag, p, K == 2 ? p_out : p, x, s, hz.tagged, history, lead,                \
-                       K == 2 ? (const double *)ring.b[1] : nullptr, K == 2 ? ring.phase : 0, hz.x_early)
+                       K == 2 ? (const double *)ring.b[1] : nullptr, K == 2 ? ring.phase : 0, hz.early_slots)
 #define OGL_HELD_Q_ND(K, ND)              \
     do {                                  \
         if (fast)                         \

@@ -64,7 +64,7 @@ inline void visit(KeyHasher &h, const DevSymx &a)
 OGL_VIEW_FIELDS(LeadBox, 24);
 inline void visit(KeyHasher &h, const LeadBox &a) { h(a.box), h(a.timeout_ticks), h(a.early_loads); }
 OGL_VIEW_FIELDS(HeldZ, 16);
-inline void visit(KeyHasher &h, const HeldZ &a) { h(a.tagged), h(a.grid), h(a.x_early); }
+inline void visit(KeyHasher &h, const HeldZ &a) { h(a.tagged), h(a.grid), h(a.early_slots); }
 OGL_VIEW_FIELDS(HeldQ, 8);
 inline void visit(KeyHasher &h, const HeldQ &a) { h(a.on), h(a.n_pos); }
 

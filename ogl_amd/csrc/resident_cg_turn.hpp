@@ -69,7 +69,7 @@ struct TurnArgs {
     double *history;
     LeadBox lead;
     const double *p_pend;  // PRing::b[1]
-    int x_early;
+    int early_slots;  // slots whose x a head that updates x writes before the second wait (HeldZ::early_slots)
 };
 
 // the LDS of the turn besides zl
@@ -238,15 +238,15 @@ __device__ __forceinline__ void turn_phase_h(const Src &src, const TurnArgs &a, 
         }
         st2_stream(a.x, rp, vx);
     };
-    const bool early = a.x_early != 0 && !ts.defers;
-    if (early) {
+    // x of the first n_early slots goes out while the sums are awaited, at the price of a second read of their p; the
+    // others follow in the last loop, from its one read of p.  (A run-time bound: this loop does not touch the slots.)
+    const int n_early = ts.defers ? 0 : min(a.early_slots, R + L);
 #pragma unroll 2
-        for (int i = 0; i < R + L; ++i) {
-            const int chunk = src.chunk_of(i);
-            if (chunk < 0) continue;
-            const RowPair rp = my_rows(chunk, a.n);
-            update_x(rp, ld2(a.p, rp), K);
-        }
+    for (int i = 0; i < n_early; ++i) {
+        const int chunk = src.chunk_of(i);
+        if (chunk < 0) continue;
+        const RowPair rp = my_rows(chunk, a.n);
+        update_x(rp, ld2(a.p, rp), K);
     }
     if (!lead_wait(a.lead, 4 * FIN_WAVES, tag, lds.lead_words, &lds.lead_timed_out, 2 * FIN_WAVES)) {
         if (threadIdx.x == 0) a.s->comm_error = a.s->stop = 1;
@@ -283,7 +283,7 @@ __device__ __forceinline__ void turn_phase_h(const Src &src, const TurnArgs &a, 
         if (chunk < 0) continue;
         const RowPair rp = my_rows(chunk, a.n);
         double2 vp = ld2(a.p, rp);
-        if (!ts.defers && !early) update_x(rp, vp, K);
+        if (!ts.defers && i >= n_early) update_x(rp, vp, K);
         // a deferring head that ends the solve: what is pending goes in now
         if (ts.defers && stop) update_x(rp, vp, ts.phase);
         if (stop) continue;

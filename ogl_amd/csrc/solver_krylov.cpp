@@ -797,7 +797,11 @@ int ogl_solver::plan_held_z(KrylovRun &k)
     }
     k.hz.tagged = held_z_box;
     k.hz.grid = grid;
-    k.hz.x_early = prop("heldZEarlyX", 1.0) != 0.0 ? 1 : 0;
+    // heldZEarlyX 0 switches early x off; heldZEarlySlots: for how many of a workgroup's slots it runs.  4 by default: the
+    // wait it covers is 6 us, a slot of it takes 2 us, and every slot more is 1/20 of p read twice.  Measured
+    // (profiles/r11_resident_waits.txt, section 3): 0 and 4 slots run level, all 20 are slower by 2 %.
+    const int early_slots = std::max(0, std::min(per_wg, (int)prop("heldZEarlySlots", 4.0)));
+    k.hz.early_slots = prop("heldZEarlyX", 1.0) != 0.0 ? early_slots : 0;
     props["heldZInUse"] = 1.0;
     props["heldZGridInUse"] = (double)grid;
     if (held_q) {
