@@ -420,8 +420,6 @@ extern "C" int ogl_solver_apply_preconditioner(ogl_solver *s, const ogl_scalar *
     if (!s->precond_data)  // (preconditioner none: the identity)
         OGL_HIP_CHECK(hipMemcpyAsync(s->d_q.p, s->d_w.p, (size_t)s->pat.n_rows * sizeof(double), hipMemcpyDeviceToDevice,
                                      s->reg->stream));
-    else if (s->precond_data->kind == 1)
-        launch_mul(s->reg->stream, s->pat.n_rows, s->d_q.p, s->d_w.p, s->precond_data->values.p, nullptr);
     else
         s->apply_preconditioner(s->d_w.p, s->d_q.p, nullptr);
     OGL_TRY(s->download_rows(z, s->d_q.p));

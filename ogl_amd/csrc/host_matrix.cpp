@@ -469,6 +469,54 @@ bool isai_pattern(const HostPattern &p, bool spd, int power, int max_row, std::v
     return true;
 }
 
+void transpose_pattern(ogl_label n, const std::vector<ogl_label> &row_ptrs, const std::vector<ogl_label> &cols,
+                       std::vector<ogl_label> &t_row_ptrs, std::vector<ogl_label> &t_cols, std::vector<ogl_label> &t_map)
+{
+    const size_t nnz = cols.size();
+    t_row_ptrs.assign((size_t)n + 1, 0);
+    t_cols.resize(nnz);
+    t_map.resize(nnz);
+    for (size_t k = 0; k < nnz; ++k) ++t_row_ptrs[(size_t)cols[k] + 1];
+    for (ogl_label r = 0; r < n; ++r) t_row_ptrs[(size_t)r + 1] += t_row_ptrs[(size_t)r];
+    std::vector<ogl_label> fill(t_row_ptrs.begin(), t_row_ptrs.end() - 1);
+    for (ogl_label r = 0; r < n; ++r)  // (source rows ascending: every transposed row comes out sorted by column)
+        for (ogl_label k = row_ptrs[(size_t)r]; k < row_ptrs[(size_t)r + 1]; ++k) {
+            const ogl_label e = fill[(size_t)cols[(size_t)k]]++;
+            t_cols[(size_t)e] = r;
+            t_map[(size_t)e] = k;
+        }
+}
+
+bool build_isai_structure(const HostPattern &p, bool spd, int power, bool caller_numbering, const IsaiRowClasses &rc,
+                          int64_t scratch_budget, IsaiStructure &S, ogl_label &first_wide_row)
+{
+    S = IsaiStructure{};
+    S.spd = spd;
+    if (!isai_pattern(p, spd, power, rc.max_row, S.row_ptrs, S.cols, first_wide_row, caller_numbering)) return false;
+    if (spd) transpose_pattern(p.n_rows, S.row_ptrs, S.cols, S.t_row_ptrs, S.t_cols, S.t_map);
+    S.huge_batches.assign(1, 0);
+    int64_t used = 0;
+    for (ogl_label r = 0; r < p.n_rows; ++r) {
+        const int32_t len = S.row_ptrs[(size_t)r + 1] - S.row_ptrs[(size_t)r];
+        S.max_row = std::max(S.max_row, len);
+        if (len > rc.wave_row) {
+            const int64_t need = (int64_t)len * len;
+            if (used + need > scratch_budget && used > 0) {
+                S.huge_batches.push_back((int32_t)S.huge_rows.size());
+                used = 0;
+            }
+            S.huge_rows.push_back(r);
+            S.huge_off.push_back(used);
+            used += need;
+            S.scratch_len = std::max(S.scratch_len, used);
+        } else if (len > rc.thread_row) {
+            S.wide_rows.push_back(r);
+        }
+    }
+    S.huge_batches.push_back((int32_t)S.huge_rows.size());
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------
 // Renumbering
 // ---------------------------------------------------------------------------------------
@@ -1672,20 +1720,8 @@ bool build_factor_structure(const HostPattern &p, bool ic, FactorStructure &F, o
         level[(size_t)i] = l;
     }
     level_schedule(level, F.fwd_ptr, F.fwd_rows);
-    if (ic) {  // L^T: counting transpose, rows sorted by column (the diagonal comes first)
-        F.t_row_ptrs.assign((size_t)N + 1, 0);
-        F.t_cols.resize((size_t)nf);
-        F.t_map.resize((size_t)nf);
-        for (int32_t e = 0; e < nf; ++e) ++F.t_row_ptrs[(size_t)F.cols[(size_t)e] + 1];
-        for (ogl_label r = 0; r < N; ++r) F.t_row_ptrs[(size_t)r + 1] += F.t_row_ptrs[(size_t)r];
-        std::vector<int32_t> fill(F.t_row_ptrs.begin(), F.t_row_ptrs.end() - 1);
-        for (ogl_label r = 0; r < N; ++r)
-            for (int32_t e = F.row_ptrs[(size_t)r]; e < F.row_ptrs[(size_t)r + 1]; ++e) {
-                const int32_t t = fill[(size_t)F.cols[(size_t)e]]++;
-                F.t_cols[(size_t)t] = r;
-                F.t_map[(size_t)t] = e;
-            }
-    }
+    // L^T: rows sorted by column (the diagonal comes first)
+    if (ic) transpose_pattern(N, F.row_ptrs, F.cols, F.t_row_ptrs, F.t_cols, F.t_map);
     // backward levels over the strictly upper part (U, or L^T for IC), rows descending
     const std::vector<int32_t> &urp = ic ? F.t_row_ptrs : F.row_ptrs;
     const std::vector<int32_t> &uc = ic ? F.t_cols : F.cols;

@@ -232,6 +232,34 @@ int choose_numbering(HostPattern &p, int mode, bool try_sell, SellLayout *sell_o
 bool isai_pattern(const HostPattern &p, bool spd, int power, int max_row, std::vector<ogl_label> &w_row_ptrs,
                   std::vector<ogl_label> &w_cols, ogl_label &first_wide_row, bool caller_numbering = true);
 
+// Counting transpose of an n x n CSR pattern: the rows of the transpose come out sorted by column; t_map[e] = position
+// in the source of transposed entry e.  (L^T of IC, W^T of ISAI)
+void transpose_pattern(ogl_label n, const std::vector<ogl_label> &row_ptrs, const std::vector<ogl_label> &cols,
+                       std::vector<ogl_label> &t_row_ptrs, std::vector<ogl_label> &t_cols, std::vector<ogl_label> &t_map);
+
+// Everything of ISAI / GISAI that depends on the pattern only, built once per pattern; the device fills the values.
+// Rows by length (the generation kernels' limits, kernels.hpp): up to thread_row entries one thread each; up to
+// wave_row one wavefront each (wide_rows); beyond that, up to max_row, one workgroup each with its dense system of
+// len * len doubles in global scratch (huge_rows).
+struct IsaiRowClasses {
+    int thread_row = 0, wave_row = 0, max_row = 0;
+};
+struct IsaiStructure {
+    bool spd = false;
+    std::vector<int32_t> row_ptrs, cols;             // W (isai_pattern)
+    std::vector<int32_t> t_row_ptrs, t_cols, t_map;  // spd: W^T, t_map = position in W
+    int32_t max_row = 0;                             // longest row of W
+    std::vector<int32_t> wide_rows, huge_rows;       // ascending
+    // huge_off[k] = start of row huge_rows[k]'s system in the scratch; rows huge_batches[b] .. huge_batches[b + 1] of
+    // huge_rows share the scratch at one time: a batch stays within the budget unless it is a single row
+    std::vector<int64_t> huge_off;
+    std::vector<int32_t> huge_batches;
+    int64_t scratch_len = 0;  // doubles the largest batch needs
+};
+// scratch_budget in doubles.  false (first_wide_row set): a row of W would get more than rc.max_row entries.
+bool build_isai_structure(const HostPattern &p, bool spd, int power, bool caller_numbering, const IsaiRowClasses &rc,
+                          int64_t scratch_budget, IsaiStructure &S, ogl_label &first_wide_row);
+
 // HostMatrix.C:180-207: concatenated bouCoeffs of the (non-)processor interfaces, times -1.
 void collect_interface_coeffs(const ogl_ldu_view &ldu, bool local, ogl_scalar *out);
 

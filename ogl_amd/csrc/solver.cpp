@@ -222,9 +222,7 @@ ogl_registry::~ogl_registry()
     solvers.clear();
     comm.reset();
     peer_close();
-    cached_precond.values.release();
-    cached_precond.block_ptrs.release();
-    cached_precond.row_block.release();
+    cached_precond.release();
     if (comm_stream) {
         (void)hipStreamSynchronize(comm_stream);
         stream_destroy(comm_stream);

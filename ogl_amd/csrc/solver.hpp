@@ -43,22 +43,69 @@ struct MgLevel {
     }
 };
 
-// A generated preconditioner ("Cached_preconditinoner" holds one of these, Preconditioner.H:357)
-struct PrecondData {
-    // 0 none, 1 scalar Jacobi (inverse diagonal), 2 block Jacobi, 3 ISAI, 4 GISAI, 5 IC, 6 ILU, 7 IRILU, 8 Multigrid
-    int kind = 0;
-    size_t n_rows = 0;
-    int stride = 0;  // block Jacobi: maxBlockSize
+// The preconditioner kinds.  precond_kind_of is the only place that turns the configuration (the public OGL_PRECOND_*
+// value + maxBlockSize) into one, precond_name the only place that holds the names the error messages use.
+enum class PrecondKind { None, Jacobi, BlockJacobi, Isai, Gisai, Ic, Ilu, Irilu, Multigrid };
+inline PrecondKind precond_kind_of(const ogl_config &cfg)  // (None also for a value that is not built)
+{
+    switch (cfg.preconditioner) {
+    case OGL_PRECOND_BJ: return cfg.max_block_size == 1 ? PrecondKind::Jacobi : PrecondKind::BlockJacobi;
+    case OGL_PRECOND_ISAI: return PrecondKind::Isai;
+    case OGL_PRECOND_GISAI: return PrecondKind::Gisai;
+    case OGL_PRECOND_IC: return PrecondKind::Ic;
+    case OGL_PRECOND_ILU: return PrecondKind::Ilu;
+    case OGL_PRECOND_IRILU: return PrecondKind::Irilu;
+    case OGL_PRECOND_MULTIGRID: return PrecondKind::Multigrid;
+    default: return PrecondKind::None;
+    }
+}
+inline const char *precond_name(PrecondKind k)
+{
+    static const char *const names[] = {"none", "BJ", "BJ", "ISAI", "GISAI", "IC", "ILU", "IRILU", "Multigrid"};
+    return names[(int)k];
+}
+inline bool is_isai(PrecondKind k) { return k == PrecondKind::Isai || k == PrecondKind::Gisai; }
+inline bool is_factor(PrecondKind k) { return k == PrecondKind::Ic || k == PrecondKind::Ilu || k == PrecondKind::Irilu; }
+
+// ---- what each kind owns: its buffers, its pattern-only record, and the views its kernels take (kernels.hpp) ----
+
+// Block Jacobi: the inverted blocks.  Scalar Jacobi keeps its inverse diagonal (n_rows + 2) in `values` too.
+struct BlockJacobiPart {
     int32_t n_blocks = 0;
-    bool uniform_blocks = false;  // block Jacobi: every block but the last has exactly `stride` rows
-    bool through_perm = false;    // block Jacobi: block_ptrs / row_block are positions in the caller's numbering
+    bool uniform_blocks = false;  // every block but the last has exactly `stride` rows
+    bool through_perm = false;    // block_ptrs / row_block are positions in the caller's numbering
     uint64_t perm_pat_id = 0;     // ... of THIS pattern's permutation
     bool by_device_row = false;   // block rows stored at their device rows (direct apply) instead of block-major (staged)
-    DevBuf<double> values;  // inverse diagonal (n_rows + 2) or inverted blocks
+    DevBuf<double> values;
     DevBuf<int32_t> block_ptrs, row_block;
-    // ISAI (kind 3: spd, M^-1 = W^T W; kind 4: general, M^-1 = W): CSR arrays padded like the
-    // system matrix so the CSR-stream SpMV kernel applies them; wt_map = position in W of every
-    // entry of W^T
+    void release()
+    {
+        values.release();
+        block_ptrs.release();
+        row_block.release();
+    }
+    // rows / pos: the permutation the blocks are reached through (the generating or the applying solver's), or nullptr
+    DevBlockJacobi view(int32_t n_rows, int stride, const int32_t *rows, const int32_t *pos, int32_t perm_xcd_group = 0) const
+    {
+        DevBlockJacobi J;
+        J.n_rows = n_rows;
+        J.n_blocks = n_blocks;
+        J.stride = stride;
+        J.block_ptrs = block_ptrs.p;
+        J.row_block = row_block.p;
+        J.blocks = values.p;
+        J.uniform = uniform_blocks ? 1 : 0;
+        J.rows = rows;
+        J.pos = pos;
+        J.by_device_row = rows && by_device_row ? 1 : 0;
+        J.perm_xcd_group = perm_xcd_group;
+        return J;
+    }
+};
+
+// ISAI (spd, M^-1 = W^T W) and GISAI (general, M^-1 = W): CSR arrays padded like the system matrix so the CSR-stream
+// SpMV kernel applies them; wt_map = position in W of every entry of W^T (IsaiStructure, host_matrix.hpp)
+struct IsaiPart {
     DevBuf<int32_t> w_row_ptrs, w_cols, wt_row_ptrs, wt_cols, wt_map;
     DevBuf<double> w_vals, wt_vals;
     int32_t w_nnz = 0, w_max_row = 0;
@@ -74,51 +121,186 @@ struct PrecondData {
     std::vector<int32_t> huge_batches;
     int32_t n_huge_rows = 0;
     SellDev w_sell, wt_sell;  // compressed copies the apply runs on when compress_indices is set
-    // incomplete factorisations (kinds 5 IC, 6 ILU, 7 IRILU; FactorStructure, host_matrix.hpp): the factor in the CALLER's
-    // numbering -- self-contained, applied through the applying solver's permutation -- with its value map, update
-    // lists, L^T (IC) and the level schedules
-    DevBuf<int32_t> f_row_ptrs, f_cols, f_diag, f_map_ptr, f_map, f_upd_ptr, f_upd_a, f_upd_b;
-    DevBuf<int32_t> ft_row_ptrs, ft_cols, ft_map, f_fwd_ptr, f_fwd_rows, f_bwd_ptr, f_bwd_rows;
-    DevBuf<double> f_vals, ft_vals, f_inv_d;
-    DevBuf<int32_t> f_breakdown;  // first row with a zero / non-positive pivot (0x7f7f7f7f: none)
-    std::vector<int32_t> f_fwd_ptr_h, f_bwd_ptr_h;
-    int32_t f_nnz = 0;
-    // Multigrid (kind 8): the levels in use are mg[0 .. mg_levels); the objects behind them are kept from generation to
-    // generation so that their buffers only grow.  mg_work: what a generation needs besides (also only growing).
-    std::vector<std::unique_ptr<MgLevel>> mg;
-    int mg_levels = 0, mg_cg_iters = 0;
-    DevBuf<MgScalars> mg_scal;
-    DevBuf<int32_t> mg_map0;         // renumbered device copy: position in the device CSR of every entry of level 0
-    DevBuf<double> mg_in, mg_out;    // ... and the vectors of an apply in the caller's order
-    DevBuf<double> mg_diag, mg_vals_sorted;
-    DevBuf<int32_t> mg_s, mg_flag, mg_incl, mg_cidx, mg_rows, mg_sorted, mg_left;
-    DevBuf<unsigned long long> mg_keys, mg_keys_sorted;
-    DevBuf<uint8_t> mg_temp;
-    bool multigrid() const { return kind == 8; }
+    void release()
+    {
+        for (DevBuf<int32_t> *b : {&w_row_ptrs, &w_cols, &wt_row_ptrs, &wt_cols, &wt_map, &wide_rows, &huge_rows}) b->release();
+        for (DevBuf<double> *b : {&w_vals, &wt_vals, &huge_scratch}) b->release();
+        huge_off.release();
+        w_sell.release();
+        wt_sell.release();
+    }
+    DevCsr w_view(int32_t n_rows, bool stream) const { return csr_view(n_rows, stream, w_row_ptrs, w_cols, w_vals); }
+    DevCsr wt_view(int32_t n_rows, bool stream) const { return csr_view(n_rows, stream, wt_row_ptrs, wt_cols, wt_vals); }
+
+private:
+    DevCsr csr_view(int32_t n_rows, bool stream, const DevBuf<int32_t> &rp, const DevBuf<int32_t> &c,
+                    const DevBuf<double> &v) const
+    {
+        DevCsr W;
+        W.n_rows = n_rows;
+        W.nnz = w_nnz;
+        W.row_ptrs = rp.p;
+        W.cols = c.p;
+        W.vals = v.p;
+        W.stream = stream;
+        return W;
+    }
+};
+
+// Incomplete factorisations (IC, ILU, IRILU; FactorStructure, host_matrix.hpp): the factor in the CALLER's numbering --
+// self-contained, applied through the applying solver's permutation -- with its value map, update lists, L^T (IC) and
+// the level schedules.  ILU and IRILU share the factor.
+struct FactorPart {
+    int32_t n_rows = 0, nnz = 0;
+    bool ic = false;
+    DevBuf<int32_t> row_ptrs, cols, diag, map_ptr, map, upd_ptr, upd_a, upd_b;
+    DevBuf<int32_t> t_row_ptrs, t_cols, t_map, fwd_ptr, fwd_rows, bwd_ptr, bwd_rows;
+    DevBuf<double> vals, t_vals, inv_d;
+    DevBuf<int32_t> breakdown;  // first row with a zero / non-positive pivot (0x7f7f7f7f: none)
+    std::vector<int32_t> fwd_ptr_h, bwd_ptr_h;
+    void release()
+    {
+        for (DevBuf<int32_t> *b : {&row_ptrs, &cols, &diag, &map_ptr, &map, &upd_ptr, &upd_a, &upd_b, &t_row_ptrs, &t_cols, &t_map,
+                                   &fwd_ptr, &fwd_rows, &bwd_ptr, &bwd_rows, &breakdown})
+            b->release();
+        for (DevBuf<double> *b : {&vals, &t_vals, &inv_d}) b->release();
+    }
+    DevFactor factor_view() const
+    {
+        DevFactor F;
+        F.n_rows = n_rows;
+        F.ic = ic ? 1 : 0;
+        F.row_ptrs = row_ptrs.p;
+        F.cols = cols.p;
+        F.diag = diag.p;
+        F.vals = vals.p;
+        F.upd_ptr = upd_ptr.p;
+        F.upd_a = upd_a.p;
+        F.upd_b = upd_b.p;
+        F.breakdown = breakdown.p;
+        return F;
+    }
+    DevTri lower() const  // (ILU: unit diagonal)
+    {
+        DevTri L;
+        L.beg = row_ptrs.p;
+        L.end = diag.p;
+        L.cols = cols.p;
+        L.vals = vals.p;
+        L.unit = ic ? 0 : 1;
+        return L;
+    }
+    DevTri upper() const  // (IC: L^T)
+    {
+        DevTri U;
+        U.upper = 1;
+        U.beg = ic ? t_row_ptrs.p : diag.p;
+        U.end = (ic ? t_row_ptrs.p : row_ptrs.p) + 1;
+        U.cols = ic ? t_cols.p : cols.p;
+        U.vals = ic ? t_vals.p : vals.p;
+        return U;
+    }
+};
+
+// Multigrid: the levels in use are levels[0 .. n_levels); the objects behind them are kept from generation to
+// generation so that their buffers only grow.  The work buffers: what a generation needs besides (also only growing).
+struct MultigridPart {
+    std::vector<std::unique_ptr<MgLevel>> levels;
+    int n_levels = 0, cg_iters = 0;
+    DevBuf<MgScalars> scal;
+    DevBuf<int32_t> map0;      // renumbered device copy: position in the device CSR of every entry of level 0
+    DevBuf<double> in, out;    // ... and the vectors of an apply in the caller's order
+    DevBuf<double> diag, vals_sorted;
+    DevBuf<int32_t> s, flag, incl, cidx, rows, sorted, left;
+    DevBuf<unsigned long long> keys, keys_sorted;
+    DevBuf<uint8_t> temp;
+    void release()
+    {
+        levels.clear();
+        n_levels = 0;
+        scal.release();
+        for (DevBuf<int32_t> *b : {&map0, &s, &flag, &incl, &cidx, &rows, &sorted, &left}) b->release();
+        for (DevBuf<double> *b : {&in, &out, &diag, &vals_sorted}) b->release();
+        keys.release();
+        keys_sorted.release();
+        temp.release();
+    }
+};
+
+// A generated preconditioner ("Cached_preconditinoner" holds one of these, Preconditioner.H:357): what is common to all
+// kinds, and one part per family of kinds.  All parts are present at all times and the parts of the OTHER kinds are
+// NOT released when the object changes kind: the store is registry-wide, so a case with ISAI on p and block Jacobi on
+// U alternates kinds with every time step, and no allocation after the first steps is promised.
+// That is why the parts are members and not a variant.
+struct PrecondData {
+    PrecondKind kind = PrecondKind::None;
+    size_t n_rows = 0;
+    int stride = 0;  // block Jacobi: maxBlockSize; ISAI / GISAI: sparsityPower
+    BlockJacobiPart bj;
+    IsaiPart isai;
+    FactorPart fac;
+    MultigridPart mg;
+    void release()
+    {
+        bj.release();
+        isai.release();
+        fac.release();
+        mg.release();
+    }
+    bool materialises_z() const { return kind != PrecondKind::None && kind != PrecondKind::Jacobi; }  // (Jacobi: fused)
+    bool is_isai() const { return ogl::is_isai(kind); }
+    bool factor() const { return is_factor(kind); }
+    bool multigrid() const { return kind == PrecondKind::Multigrid; }
     uint64_t serial = 0;  // new value with every generation (an applier checks it still holds what it adopted)
-    // the pattern-only part (block pointers / W and W^T patterns) is kept for as long as it was
-    // derived from the same sparsity pattern: only the values are regenerated per solve
+    // the pattern-only part (block pointers / W and W^T patterns / the factor's structure / Multigrid's level 0) is kept
+    // for as long as it was derived from the same sparsity pattern: only the values are regenerated per solve
     uint64_t struct_pat_id = 0;
-    int struct_kind = 0, struct_stride = 0;
+    PrecondKind struct_kind = PrecondKind::None;
+    int struct_stride = 0;
     bool struct_caller_numbering = true;
-    bool has_structure(uint64_t id, int k, int st) const
+    bool has_structure(uint64_t id, PrecondKind k, int st) const
     {
         return id != 0 && struct_pat_id == id && struct_kind == k && struct_stride == st;
     }
-    bool matches(int k, size_t n, int st) const { return kind == k && n_rows == n && stride == st; }
+    void set_structure(uint64_t id, PrecondKind k, int st)
+    {
+        struct_pat_id = id;
+        struct_kind = k;
+        struct_stride = st;
+    }
+    bool matches(PrecondKind k, size_t n, int st) const { return kind == k && n_rows == n && stride == st; }
     // Which numbering the VALUES are laid out in.  The store is shared by all fields (Preconditioner.H:357), so the
-    // object may be applied by a solver other than the one that generated it: that is sound when both see the caller's
-    // numbering, or when the object is a block Jacobi kept block-major in the caller's order (the applying solver carries
-    // the vectors through ITS permutation); everything else -- inverse diagonal, W / W^T, block rows stored by device
-    // row, the backend's own blocks -- belongs to the generating pattern's device numbering.
+    // object may be applied by a solver other than the one that generated it.  Generated on a renumbered device copy,
+    // these keep the caller's order all the same: the factors, a Multigrid hierarchy (it then has a level 0 of its own),
+    // and a block Jacobi kept block-major in the caller's order (the applying solver carries the vectors through ITS
+    // permutation).  Everything else -- inverse diagonal, W / W^T, block rows stored by device row, the backend's own
+    // blocks -- then belongs to the generating pattern's device numbering.
     uint64_t gen_pat_id = 0;
     bool gen_device_numbering = false;
-    bool caller_order_blocks() const { return kind == 2 && !by_device_row && !gen_device_numbering; }
-    bool factor() const { return kind >= 5 && kind <= 7; }
+    bool keeps_caller_order() const
+    {
+        return factor() || multigrid() || (kind == PrecondKind::BlockJacobi && bj.through_perm && !bj.by_device_row);
+    }
+    bool caller_order_blocks() const
+    {
+        return kind == PrecondKind::BlockJacobi && !bj.by_device_row && !gen_device_numbering;
+    }
+    // May a solver with pattern `id` (renumbered or not) apply this object?  Own pattern: always.  Another pattern:
+    //
+    //   kind                                         generator renumbered   applier renumbered   ->
+    //   Jacobi, ISAI, GISAI                          yes                    any                  foreign
+    //                                                no                     yes                  foreign
+    //                                                no                     no                   own
+    //   block Jacobi, block-major in caller's order  any                    any                  own (through the applier's permutation)
+    //   block Jacobi, by device row / backend blocks yes                    any                  foreign
+    //   IC, ILU, IRILU                               any                    any                  own (through the applier's permutation)
+    //   Multigrid                                    any                    yes                  foreign
+    //                                                any                    no                   own
+    //
+    // (a Multigrid hierarchy is self-contained only when its generator kept a level 0 of its own)
     bool foreign_to(uint64_t id, bool renumbered) const
     {
         if (gen_pat_id == id) return false;
-        // (a Multigrid hierarchy is self-contained only when its generator kept a level 0 of its own)
         return gen_device_numbering || (renumbered && !caller_order_blocks() && !factor());
     }
 };
@@ -344,11 +526,18 @@ struct ogl_solver {
     int upload_vec(ogl::DevBuf<double> &dst, const double *src);
     int ensure_vectors();
     int init_preconditioner();
+    // generate_preconditioner dispatches on the kind; each generator: pattern-only part if the object does not hold it
+    // for this pattern, then the values (generate_multigrid: above)
     int generate_preconditioner(ogl::PrecondData &P);
+    int generate_jacobi(ogl::PrecondData &P);
+    int generate_block_jacobi(ogl::PrecondData &P, bool through_perm);
+    int generate_isai(ogl::PrecondData &P, bool caller_numbering);
+    int generate_factor(ogl::PrecondData &P);
+    int prepare_apply();  // this solver's scratch and launch schedule for applies of precond_data
     void apply_factor(const double *in, double *out, const ogl::DevScalars *gate, double *dot_part);
     int check_factor_breakdown(int32_t word);
-    // out = M^-1 in for the block-Jacobi / ISAI / GISAI / IC / ILU / IRILU kinds; dot_part != nullptr: also the per-chunk
-    // partials of sum_i in_i * out_i (CG's rho), out of the same kernel
+    // out = M^-1 in for every kind (the Krylov loops fuse scalar Jacobi through `precond` instead); dot_part != nullptr:
+    // also the per-chunk partials of sum_i in_i * out_i (CG's rho), out of the same kernel where the kind has one
     void apply_preconditioner(const double *in, double *out, const ogl::DevScalars *gate,
                               double *dot_part = nullptr);
     // prepacked: the kernel that produced x has put the halo values already (begin_halo_put)

@@ -261,7 +261,7 @@ int ogl_solver::krylov_plan(KrylovRun &k)
     k.ldv = (int64_t)n + 2;
     // block Jacobi (maxBlockSize > 1): z = M^-1 r is materialised by its own kernel; the scalar
     // case stays fused into the step kernels
-    const bool generic = k.generic = precond_data && precond_data->kind >= 2;  // block Jacobi, ISAI, GISAI
+    const bool generic = k.generic = precond_data && precond_data->materialises_z();  // (every kind but scalar Jacobi)
     k.has_diag = precond != nullptr;
     const bool multi = k.multi = reg->comm->multi();
     const bool small = !multi && nc >= 1 &&
@@ -1087,7 +1087,7 @@ int ogl_solver::krylov_finish(KrylovRun &k, ogl_perf *perf)
     }
     DevScalars *fin_s = bicg_fold ? k.slot_s[k.cur] : (fused ? s2 : s);
     if (precond_data && precond_data->factor())  // (the factor's breakdown word travels with the final scalars)
-        OGL_HIP_CHECK(hipMemcpyAsync(&fin_s->factor_breakdown, precond_data->f_breakdown.p, sizeof(int32_t),
+        OGL_HIP_CHECK(hipMemcpyAsync(&fin_s->factor_breakdown, precond_data->fac.breakdown.p, sizeof(int32_t),
                                      hipMemcpyDeviceToDevice, st));
     OGL_HIP_CHECK(hipStreamSynchronize(st));
     OGL_HIP_CHECK(hipGetLastError());

@@ -49,10 +49,11 @@ int ogl_solver::generate_multigrid(PrecondData &P)
     hipStream_t st = reg->stream;
     const int max_levels = (int)prop("maxLevels", 9.0);
     const int32_t min_coarse = (int32_t)prop("minCoarseRows", 10.0);
-    P.mg_cg_iters = (int)prop("coarseSolverIters", 4.0);
-    OGL_TRY(grow(P.mg_scal, 1, st));
-    OGL_TRY(grow(P.mg_left, 1, st));
-    if (P.mg.empty()) P.mg.emplace_back(new MgLevel);
+    MultigridPart &M = P.mg;
+    M.cg_iters = (int)prop("coarseSolverIters", 4.0);
+    OGL_TRY(grow(M.scal, 1, st));
+    OGL_TRY(grow(M.left, 1, st));
+    if (M.levels.empty()) M.levels.emplace_back(new MgLevel);
     const DevCsr A0 = csr(false);
     MgCsr cur;
     cur.n = pat.n_rows;
@@ -60,12 +61,12 @@ int ogl_solver::generate_multigrid(PrecondData &P)
     cur.row_ptrs = A0.row_ptrs;
     cur.cols = A0.cols;
     cur.vals = A0.vals;
-    MgLevel &L0 = *P.mg[0];
+    MgLevel &L0 = *M.levels[0];
     L0.own = pat.renumbered();
     if (L0.own) {
         // the hierarchy is that of the CALLER's numbering: level 0 = the device copy carried back through the permutation
         // (pattern and value map once per pattern on the host, the values gathered on the device per generation)
-        if (!P.has_structure(pat_id, 8, 0)) {
+        if (!P.has_structure(pat_id, PrecondKind::Multigrid, 0)) {
             P.struct_pat_id = 0;
             OGL_TRY(download_local_pattern(pat));
             const int32_t N = pat.n_rows;
@@ -88,133 +89,129 @@ int ogl_solver::generate_multigrid(PrecondData &P)
             }
             OGL_TRY(grow(L0.row_ptrs, rp.size(), st));
             OGL_TRY(grow(L0.cols, cc.size(), st));
-            OGL_TRY(grow(P.mg_map0, map.size(), st));
+            OGL_TRY(grow(M.map0, map.size(), st));
             OGL_TRY(reg->stager.h2d(L0.row_ptrs.p, rp.data(), rp.size() * sizeof(int32_t), st));
             if (!cc.empty()) {
                 OGL_TRY(reg->stager.h2d(L0.cols.p, cc.data(), cc.size() * sizeof(int32_t), st));
-                OGL_TRY(reg->stager.h2d(P.mg_map0.p, map.data(), map.size() * sizeof(int32_t), st));
+                OGL_TRY(reg->stager.h2d(M.map0.p, map.data(), map.size() * sizeof(int32_t), st));
             }
-            P.struct_pat_id = pat_id;
-            P.struct_kind = 8;
-            P.struct_stride = 0;
+            P.set_structure(pat_id, PrecondKind::Multigrid, 0);
         }
         OGL_TRY(grow(L0.vals, (size_t)cur.nnz, st));
-        OGL_TRY(grow(P.mg_in, (size_t)cur.n + 2, st));
-        OGL_TRY(grow(P.mg_out, (size_t)cur.n + 2, st));
-        launch_gather_coeffs(st, cur.nnz, P.mg_map0.p, A0.vals, L0.vals.p);
+        OGL_TRY(grow(M.in, (size_t)cur.n + 2, st));
+        OGL_TRY(grow(M.out, (size_t)cur.n + 2, st));
+        launch_gather_coeffs(st, cur.nnz, M.map0.p, A0.vals, L0.vals.p);
         cur.row_ptrs = L0.row_ptrs.p;
         cur.cols = L0.cols.p;
         cur.vals = L0.vals.p;
-    } else if (P.struct_kind == 8) {
+    } else if (P.struct_kind == PrecondKind::Multigrid) {
         P.struct_pat_id = 0;
     }
     int l = 0;
     for (;; ++l) {
-        MgLevel &L = *P.mg[(size_t)l];
+        MgLevel &L = *M.levels[(size_t)l];
         const int32_t n = cur.n, m = cur.nnz;
         L.n = n;
         L.nnz = m;
         L.n_coarse = 0;
         OGL_TRY(grow(L.inv_d, (size_t)n + 2, st));
-        OGL_TRY(grow(P.mg_diag, (size_t)n, st));
+        OGL_TRY(grow(M.diag, (size_t)n, st));
         for (DevBuf<double> *v : {&L.xa, &L.xb, &L.t}) OGL_TRY(grow(*v, (size_t)n + 2, st));
-        launch_mg_diag(st, cur, P.mg_diag.p, L.inv_d.p);
+        launch_mg_diag(st, cur, M.diag.p, L.inv_d.p);
         if (l >= max_levels || n <= min_coarse || n < 2) break;
         // ---- aggregation: up to MG_ROUNDS matching rounds, then the leftovers ----
         OGL_TRY(grow(L.agg, (size_t)n, st));
-        for (DevBuf<int32_t> *v : {&P.mg_s, &P.mg_flag, &P.mg_incl, &P.mg_cidx, &P.mg_rows, &P.mg_sorted, &L.agg_rows})
+        for (DevBuf<int32_t> *v : {&M.s, &M.flag, &M.incl, &M.cidx, &M.rows, &M.sorted, &L.agg_rows})
             OGL_TRY(grow(*v, (size_t)std::max(n, m), st));
         OGL_HIP_CHECK(hipMemsetAsync(L.agg.p, 0xff, (size_t)n * sizeof(int32_t), st));
         int32_t prev_left = n;
         for (int round = 0; round < MG_ROUNDS; ++round) {
-            OGL_HIP_CHECK(hipMemsetAsync(P.mg_left.p, 0, sizeof(int32_t), st));
-            launch_mg_strongest(st, cur, P.mg_diag.p, L.agg.p, 0, P.mg_s.p);
-            launch_mg_match(st, n, P.mg_s.p, L.agg.p, P.mg_left.p);
+            OGL_HIP_CHECK(hipMemsetAsync(M.left.p, 0, sizeof(int32_t), st));
+            launch_mg_strongest(st, cur, M.diag.p, L.agg.p, 0, M.s.p);
+            launch_mg_match(st, n, M.s.p, L.agg.p, M.left.p);
             int32_t left = 0;
-            OGL_TRY(read_i32(P.mg_left.p, &left, st));
+            OGL_TRY(read_i32(M.left.p, &left, st));
             if (left == 0 || left == prev_left || (double)left < 0.05 * (double)n) break;
             prev_left = left;
         }
-        launch_mg_strongest(st, cur, P.mg_diag.p, L.agg.p, 1, P.mg_s.p);
-        launch_mg_join(st, n, P.mg_s.p, L.agg.p);
+        launch_mg_strongest(st, cur, M.diag.p, L.agg.p, 1, M.s.p);
+        launch_mg_join(st, n, M.s.p, L.agg.p);
         // ---- numbering: roots in ascending order ----
         const size_t temp_bytes = mg_temp_bytes(n, m);
-        OGL_TRY(grow(P.mg_temp, temp_bytes, st));
-        launch_mg_root_flag(st, n, L.agg.p, P.mg_flag.p);
-        OGL_HIP_CHECK(mg_inclusive_sum(st, P.mg_temp.p, temp_bytes, P.mg_flag.p, P.mg_incl.p, n));
+        OGL_TRY(grow(M.temp, temp_bytes, st));
+        launch_mg_root_flag(st, n, L.agg.p, M.flag.p);
+        OGL_HIP_CHECK(mg_inclusive_sum(st, M.temp.p, temp_bytes, M.flag.p, M.incl.p, n));
         int32_t nc = 0;
-        OGL_TRY(read_i32(P.mg_incl.p + (n - 1), &nc, st));
+        OGL_TRY(read_i32(M.incl.p + (n - 1), &nc, st));
         if (nc >= n) break;  // (a coarsening that does not shrink is dropped and ends the hierarchy)
-        launch_mg_coarse_index(st, n, L.agg.p, P.mg_incl.p, P.mg_cidx.p, P.mg_rows.p);
-        OGL_HIP_CHECK(hipMemcpyAsync(L.agg.p, P.mg_cidx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        launch_mg_coarse_index(st, n, L.agg.p, M.incl.p, M.cidx.p, M.rows.p);
+        OGL_HIP_CHECK(hipMemcpyAsync(L.agg.p, M.cidx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
         // ---- the members of every coarse row, ascending ----
         OGL_TRY(grow(L.agg_ptr, (size_t)nc + 1, st));
-        OGL_HIP_CHECK(mg_sort_rows(st, P.mg_temp.p, temp_bytes, P.mg_cidx.p, P.mg_sorted.p, P.mg_rows.p, L.agg_rows.p, n));
-        launch_mg_member_ptr(st, n, nc, P.mg_sorted.p, L.agg_ptr.p);
+        OGL_HIP_CHECK(mg_sort_rows(st, M.temp.p, temp_bytes, M.cidx.p, M.sorted.p, M.rows.p, L.agg_rows.p, n));
+        launch_mg_member_ptr(st, n, nc, M.sorted.p, L.agg_ptr.p);
         // ---- A_c: stable sort of the entries by (agg(i), agg(j)), one entry per run, summed in sorted order ----
-        OGL_TRY(grow(P.mg_keys, (size_t)m, st));
-        OGL_TRY(grow(P.mg_keys_sorted, (size_t)m, st));
-        OGL_TRY(grow(P.mg_vals_sorted, (size_t)m, st));
-        launch_mg_keys(st, cur, L.agg.p, P.mg_keys.p);
-        OGL_HIP_CHECK(mg_sort_entries(st, P.mg_temp.p, temp_bytes, P.mg_keys.p, P.mg_keys_sorted.p, cur.vals,
-                                      P.mg_vals_sorted.p, m));
-        launch_mg_head_flag(st, m, P.mg_keys_sorted.p, P.mg_flag.p);
-        OGL_HIP_CHECK(mg_inclusive_sum(st, P.mg_temp.p, temp_bytes, P.mg_flag.p, P.mg_incl.p, m));
+        OGL_TRY(grow(M.keys, (size_t)m, st));
+        OGL_TRY(grow(M.keys_sorted, (size_t)m, st));
+        OGL_TRY(grow(M.vals_sorted, (size_t)m, st));
+        launch_mg_keys(st, cur, L.agg.p, M.keys.p);
+        OGL_HIP_CHECK(mg_sort_entries(st, M.temp.p, temp_bytes, M.keys.p, M.keys_sorted.p, cur.vals,
+                                      M.vals_sorted.p, m));
+        launch_mg_head_flag(st, m, M.keys_sorted.p, M.flag.p);
+        OGL_HIP_CHECK(mg_inclusive_sum(st, M.temp.p, temp_bytes, M.flag.p, M.incl.p, m));
         int32_t mc = 0;
-        OGL_TRY(read_i32(P.mg_incl.p + (m - 1), &mc, st));
-        if (P.mg.size() < (size_t)l + 2) P.mg.emplace_back(new MgLevel);
-        MgLevel &C = *P.mg[(size_t)l + 1];
+        OGL_TRY(read_i32(M.incl.p + (m - 1), &mc, st));
+        if (M.levels.size() < (size_t)l + 2) M.levels.emplace_back(new MgLevel);
+        MgLevel &C = *M.levels[(size_t)l + 1];
         OGL_TRY(grow(C.row_ptrs, (size_t)nc + 1, st));
         OGL_TRY(grow(C.cols, (size_t)mc, st));
         OGL_TRY(grow(C.vals, (size_t)mc, st));
         OGL_TRY(grow(C.b, (size_t)nc + 2, st));
-        launch_mg_compact(st, m, nc, P.mg_keys_sorted.p, P.mg_vals_sorted.p, P.mg_incl.p, C.row_ptrs.p, C.cols.p, C.vals.p);
+        launch_mg_compact(st, m, nc, M.keys_sorted.p, M.vals_sorted.p, M.incl.p, C.row_ptrs.p, C.cols.p, C.vals.p);
         L.n_coarse = nc;
         C.n = nc;
         C.nnz = mc;
         cur = C.view();
     }
-    P.mg_levels = l + 1;
-    MgLevel &last = *P.mg[(size_t)l];
+    M.n_levels = l + 1;
+    MgLevel &last = *M.levels[(size_t)l];
     OGL_TRY(grow(last.r, (size_t)last.n + 2, st));
     OGL_TRY(grow(last.p, (size_t)last.n + 2, st));
     OGL_TRY(grow(last.part, n_chunks(last.n) + 1, st));
     // what the hierarchy looks like (mgLevels counts the matrices, the fine one included)
-    props["mgLevels"] = (double)P.mg_levels;
+    props["mgLevels"] = (double)M.n_levels;
     double total = 0.0;
-    for (int k = 0; k < P.mg_levels; ++k) {
-        props["mgRows" + std::to_string(k)] = (double)P.mg[(size_t)k]->n;
-        props["mgNnz" + std::to_string(k)] = (double)P.mg[(size_t)k]->nnz;
-        total += (double)P.mg[(size_t)k]->nnz;
+    for (int k = 0; k < M.n_levels; ++k) {
+        props["mgRows" + std::to_string(k)] = (double)M.levels[(size_t)k]->n;
+        props["mgNnz" + std::to_string(k)] = (double)M.levels[(size_t)k]->nnz;
+        total += (double)M.levels[(size_t)k]->nnz;
     }
-    props["mgOperatorComplexity"] = P.mg[0]->nnz > 0 ? total / (double)P.mg[0]->nnz : 1.0;
-    P.kind = 8;
-    P.stride = 0;
+    props["mgOperatorComplexity"] = M.levels[0]->nnz > 0 ? total / (double)M.levels[0]->nnz : 1.0;
     return OGL_OK;
 }
 
 void ogl_solver::mg_product(int level, const double *x, double *y, const DevScalars *gate)
 {
-    if (!precond_data->mg[(size_t)level]->own)
+    if (!precond_data->mg.levels[(size_t)level]->own)
         spmv_on(spmv_layout, SPMV_PLAIN, x, nullptr, y, SpmvDots{}, gate);
     else
-        launch_mg_csr_spmv(reg->stream, precond_data->mg[(size_t)level]->view(), x, y, gate);
+        launch_mg_csr_spmv(reg->stream, precond_data->mg.levels[(size_t)level]->view(), x, y, gate);
 }
 
 // x = the V-cycle's answer to A_level x = b, from x = 0; x is none of the level's own vectors' aliases the cycle reads
 void ogl_solver::mg_cycle(int level, const double *b, double *x, const DevScalars *gate, int &launches)
 {
     hipStream_t st = reg->stream;
-    const PrecondData &P = *precond_data;
-    const MgLevel &L = *P.mg[(size_t)level];
+    const MultigridPart &M = precond_data->mg;
+    const MgLevel &L = *M.levels[(size_t)level];
     const int32_t n = L.n;
     if (level >= mg_tail_first) {
         // this level and everything below it: one single-workgroup kernel (kernels_mg.hip, k_mg_tail)
         MgTail T;
-        T.count = P.mg_levels - level;
-        T.cg_iters = P.mg_cg_iters;
+        T.count = M.n_levels - level;
+        T.cg_iters = M.cg_iters;
         for (int k = 0; k < T.count; ++k) {
-            const MgLevel &S = *P.mg[(size_t)(level + k)];
+            const MgLevel &S = *M.levels[(size_t)(level + k)];
             MgTailLevel &D = T.lev[k];
             MgCsr A = S.view();
             if (!S.own) {  // (level 0 in the caller's numbering: the system matrix's own CSR arrays)
@@ -244,13 +241,13 @@ void ogl_solver::mg_cycle(int level, const double *b, double *x, const DevScalar
         ++launches;
         return;
     }
-    if (level == P.mg_levels - 1) {
+    if (level == M.n_levels - 1) {
         // the coarsest solver: coarseSolverIters iterations of unpreconditioned CG, no criterion; dots in the loop's tree
-        MgScalars *sc = P.mg_scal.p;
+        MgScalars *sc = M.scal.p;
         const int n_part = (int)n_chunks(n);
         launch_mg_cg_init(st, n, b, L.r.p, x, L.p.p, gate);
         ++launches;
-        for (int it = 0; it < P.mg_cg_iters; ++it) {
+        for (int it = 0; it < M.cg_iters; ++it) {
             launch_partials_dot(st, n, L.r.p, L.r.p, L.part.p, gate);
             launch_mg_cg_fin(st, L.part.p, n_part, 0, it == 0, sc, gate);
             launch_mg_cg_step1(st, n, L.p.p, L.r.p, sc, gate);
@@ -262,7 +259,7 @@ void ogl_solver::mg_cycle(int level, const double *b, double *x, const DevScalar
         }
         return;
     }
-    const MgLevel &C = *P.mg[(size_t)level + 1];
+    const MgLevel &C = *M.levels[(size_t)level + 1];
     const MgCsr A = L.view();
     // 2 pre-sweeps (the first from x = 0: no product), residual and restriction
     launch_mg_jacobi0(st, n, b, L.inv_d.p, L.xa.p, gate);
@@ -299,20 +296,20 @@ void ogl_solver::mg_cycle(int level, const double *b, double *x, const DevScalar
 void ogl_solver::apply_multigrid(const double *in, double *out, const DevScalars *gate, double *dot_part)
 {
     int launches = 0;
-    const PrecondData &P = *precond_data;
+    const MultigridPart &M = precond_data->mg;
     // the tail: the levels of at most mgTailRows rows (this solver's own property, also on a stored hierarchy); never
     // more than the kernel's level table and reduction tree hold
     const double tail_rows = std::min(prop("mgTailRows", (double)MG_TAIL_DEFAULT_ROWS), (double)MG_TAIL_MAX_ROWS);
-    mg_tail_first = P.mg_levels;
-    while (mg_tail_first > 0 && P.mg_levels - mg_tail_first < MG_TAIL_MAX_LEVELS &&
-           (double)P.mg[(size_t)mg_tail_first - 1]->n <= tail_rows)
+    mg_tail_first = M.n_levels;
+    while (mg_tail_first > 0 && M.n_levels - mg_tail_first < MG_TAIL_MAX_LEVELS &&
+           (double)M.levels[(size_t)mg_tail_first - 1]->n <= tail_rows)
         --mg_tail_first;
-    props["mgTailLevels"] = (double)(P.mg_levels - mg_tail_first);
+    props["mgTailLevels"] = (double)(M.n_levels - mg_tail_first);
     props["mgTailRows"] = tail_rows;
     if (pat.renumbered()) {  // (the vectors carried into the caller's order and back, as apply_factor does)
-        launch_factor_gather_perm(reg->stream, pat.n_rows, d_new_id.p, in, P.mg_in.p, gate);
-        mg_cycle(0, P.mg_in.p, P.mg_out.p, gate, launches);
-        launch_factor_scatter_perm(reg->stream, pat.n_rows, d_new_id.p, P.mg_out.p, out, gate);
+        launch_factor_gather_perm(reg->stream, pat.n_rows, d_new_id.p, in, M.in.p, gate);
+        mg_cycle(0, M.in.p, M.out.p, gate, launches);
+        launch_factor_scatter_perm(reg->stream, pat.n_rows, d_new_id.p, M.out.p, out, gate);
         launches += 2;
     } else {
         mg_cycle(0, in, out, gate, launches);
@@ -330,15 +327,15 @@ static int mg_current(ogl_solver *s, int32_t level, const char *who)
     if (!s->matrix_set || !s->precond_ready || !s->precond_current() || !s->precond_data || !s->precond_data->multigrid())
         return fail(OGL_ERR_STATE, "%s: no current Multigrid hierarchy (none was set up by the last solve, another field "
                                    "regenerated the shared one, or the pattern changed): solve again first", who);
-    if (level < 0 || level >= s->precond_data->mg_levels)
-        return fail(OGL_ERR_INVALID, "%s: level %d outside [0, %d)", who, level, s->precond_data->mg_levels);
+    if (level < 0 || level >= s->precond_data->mg.n_levels)
+        return fail(OGL_ERR_INVALID, "%s: level %d outside [0, %d)", who, level, s->precond_data->mg.n_levels);
     return OGL_OK;
 }
 
 extern "C" int ogl_solver_mg_level_dims(ogl_solver *s, int32_t level, ogl_label *rows, ogl_label *nnz)
 {
     OGL_TRY(mg_current(s, level, "ogl_solver_mg_level_dims"));
-    const MgLevel &L = *s->precond_data->mg[(size_t)level];
+    const MgLevel &L = *s->precond_data->mg.levels[(size_t)level];
     if (rows) *rows = L.n;
     if (nnz) *nnz = L.nnz;
     return OGL_OK;
@@ -351,7 +348,7 @@ extern "C" int ogl_solver_get_mg_level(ogl_solver *s, int32_t level, ogl_label *
         OGL_TRY(mg_current(s, level, "ogl_solver_get_mg_level"));
         OGL_HIP_CHECK(hipSetDevice(s->reg->device));
         hipStream_t st = s->reg->stream;
-        const MgLevel &L = *s->precond_data->mg[(size_t)level];
+        const MgLevel &L = *s->precond_data->mg.levels[(size_t)level];
         MgCsr A = L.view();
         if (!L.own) {
             const DevCsr A0 = s->csr(false);

@@ -56,7 +56,11 @@ def test_host_layout_builders_under_sanitizers(tmp_path):
     """The pure-host part of the library (pattern -> per-chunk half storage, compressed chunked ELL; the code the GPU
     AddressSanitizer of this pool cannot reach) built with -fsanitize=address,undefined and run on one pattern of every
     class: multi-block meshes with even and odd line lengths, random bands with an odd row count, a box, one cell, an
-    octree and a Voronoi mesh.  Any report makes the run exit non-zero."""
+    octree and a Voronoi mesh.  Any report makes the run exit non-zero.  The same program checks the preconditioners'
+    pattern-only host structures on these patterns (the shared counting transpose and build_isai_structure, spd and
+    general, sparsityPower 3): maps, sorted rows, transpose of the transpose, the wide / huge row lists and the scratch
+    batches under a budget of 60,000 doubles -- the largest rows of the octree and Voronoi patterns need 150^2 and 689^2,
+    so both split into several batches and the Voronoi mesh has single rows above the budget."""
     import numpy as np
     from ogl_amd import capi, synthetic
     exe = tmp_path / "host_sanitize"
@@ -88,3 +92,8 @@ def test_host_layout_builders_under_sanitizers(tmp_path):
     assert r.stdout.count("symx rc=0") == len(cases) and "ERROR" not in r.stderr
     # ... and the numbering code (reverse Cuthill-McKee, Hilbert order, the renumbered pattern with and without centres)
     assert r.stdout.count("numbering rcm rc=0") == len(cases) and r.stdout.count("hilbert rc=0") == len(cases), r.stdout[-2000:]
+    # ... and the ISAI structures: every property holds, and the two unstructured patterns did split into batches
+    assert r.stdout.count("isai spd ok=1") == len(cases) and r.stdout.count("isai general ok=1") == len(cases), r.stdout[-3000:]
+    import re
+    batches = [int(m) for m in re.findall(r"isai \w+ ok=1 max=\d+ wide=\d+ huge=\d+ batches=(\d+)", r.stdout)]
+    assert sum(1 for k in batches if k > 1) == 4, r.stdout[-3000:]

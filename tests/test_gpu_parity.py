@@ -265,6 +265,70 @@ def test_preconditioner_caching_rules(reg, oracle):
         r.close()
 
 
+# the kinds in the order the walk visits them: (field tag, solver, configuration)
+KIND_WALK = [
+    ("jacobi", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_BJ, max_block_size=1)),
+    ("bj4", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_BJ, max_block_size=4)),
+    ("isai", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_ISAI)),
+    ("gisai", capi.SOLVER_BICGSTAB, dict(preconditioner=capi.PRECOND_GISAI)),
+    ("ic", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_IC)),
+    ("ilu", capi.SOLVER_BICGSTAB, dict(preconditioner=capi.PRECOND_ILU)),
+    ("irilu", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_IRILU)),
+    ("mg", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_MULTIGRID)),
+    ("jacobi", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_BJ, max_block_size=1)),
+    ("bj4", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_BJ, max_block_size=4)),
+]
+WALK_CASES = [
+    # 12^3 = 1,728 rows: four chunks, the last one partial
+    ("box12", lambda: synthetic.poisson_case(12), capi.RENUMBER_OFF),
+    # the smallest shuffled box of test_gpu_renumber.py, renumbered as there
+    ("shuffled14", lambda: synthetic.renumber_case(synthetic.poisson_case(14), 700, seed=1), capi.RENUMBER_ON),
+]
+
+
+@pytest.mark.parametrize("caching", [0, 2])
+@pytest.mark.parametrize("name,make,renumber", WALK_CASES, ids=[c[0] for c in WALK_CASES])
+def test_one_store_walked_through_every_kind(name, make, renumber, caching):
+    """The preconditioner store is registry-wide (Preconditioner.H:357) and keeps the buffers of every kind it has held
+    (PrecondData, solver.hpp): one registry, one field per kind, solved in the order Jacobi -> BJ(4) -> ISAI -> GISAI ->
+    IC -> ILU -> IRILU -> Multigrid -> Jacobi -> BJ(4), so that the store changes kind with every solve.  Every solve's
+    x, residual history and counters are bit-equal to the same solve in a fresh registry that has seen nothing else, and
+    a second lap allocates nothing (the ledger's deviceBytesInUse stays where the first lap left it).  (updateInitGuess:
+    a field's later solves start from the zero vector handed in, like its first, not from the solution left on the device.)"""
+    case = make()
+    b = synthetic.apply_case(case, synthetic.x_star(case.global_index, case.global_n))
+
+    def solve_in(r, tag, solver, kw):
+        s = r.solver(f"walk_{tag}", cg_cfg(solver=solver, max_iter=6, caching=caching, renumber=renumber,
+                                            update_init_guess=1, **kw))
+        s.set_matrix(case)
+        x, perf = s.solve(b, np.zeros_like(b))
+        counters = (perf.n_iterations, perf.n_norm_evals, perf.initial_residual, perf.final_residual, perf.norm_factor)
+        return s, x, s.history().copy(), counters
+
+    fresh = {}
+    for tag, solver, kw in KIND_WALK[:8]:
+        r = capi.Registry()
+        try:
+            fresh[tag] = solve_in(r, tag, solver, kw)[1:]
+        finally:
+            r.close()
+    r = capi.Registry()
+    try:
+        in_use = []
+        for lap in range(2):
+            for step, (tag, solver, kw) in enumerate(KIND_WALK):
+                s, x, hist, counters = solve_in(r, tag, solver, kw)
+                fx, fhist, fcounters = fresh[tag]
+                np.testing.assert_array_equal(x, fx, err_msg=f"lap {lap} step {step} {tag}")
+                np.testing.assert_array_equal(hist, fhist, err_msg=f"lap {lap} step {step} {tag}")
+                assert counters == fcounters, (lap, step, tag)
+            in_use.append(s.get_property("deviceBytesInUse"))
+        assert in_use[1] == in_use[0]
+    finally:
+        r.close()
+
+
 def test_errors(reg):
     s = reg.solver("err", cg_cfg())
     with pytest.raises(capi.OglError) as e:

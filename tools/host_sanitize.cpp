@@ -1,5 +1,5 @@
-// host_sanitize.cpp -- the host-side layout builders (per-chunk half storage, compressed chunked ELL) and numbering code on patterns read
-// from files, meant for an AddressSanitizer / UBSan build (tests/test_cpp_host.py builds and runs it):
+// host_sanitize.cpp -- the host-side layout builders (per-chunk half storage, compressed chunked ELL), the numbering code and the
+// preconditioners' pattern-only structures (counting transpose, ISAI row classes and scratch batches) on patterns read from files, meant for an AddressSanitizer / UBSan build (tests/test_cpp_host.py builds and runs it):
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -I include -I ogl_amd/csrc tools/host_sanitize.cpp \
 //       ogl_amd/csrc/host_matrix.cpp ogl_amd/csrc/common.cpp -lpthread -ldl -o host_sanitize && ./host_sanitize pattern.bin ...
 // pattern.bin: int32 n_rows, int32 nnz, int32 row_ptrs[n_rows + 1], int32 cols[nnz]
@@ -7,7 +7,95 @@
 #include <cstdint>
 #include <vector>
 #include "ogl_amd.h"
+#include "host_matrix.hpp"
+
+// The shared counting transpose and build_isai_structure (host_matrix.hpp) on one pattern, spd and general, at
+// sparsityPower 3 so that an unstructured mesh has rows beyond the wavefront limit.  The row classes are those of the
+// generation kernels (32 / 64 / 2048 entries).  The scratch budget of 60,000 doubles is small enough that the huge rows
+// of tests/test_cpp_host.py's octree and Voronoi patterns fall into several batches: their largest rows (printed as
+// `max`) have 150 and 689 entries (general; 71 and 286 spd), i.e. systems of 22,500 and 474,721 doubles -- batches of a
+// few rows on the octree, and rows that are a batch of their own above the budget on the Voronoi mesh.  Returns the
+// number of violated properties.
+static const int64_t ISAI_BUDGET = 60000;
+static int check_isai(const char *name, int32_t n, const std::vector<int32_t> &rp, const std::vector<int32_t> &cols)
+{
+    using namespace ogl;
+    int bad = 0;
+    auto expect = [&](bool ok, const char *what) {
+        if (!ok) {
+            ++bad;
+            printf("   isai FAILED %s: %s\n", name, what);
+        }
+    };
+    HostPattern p;
+    p.n_rows = n;
+    p.local_nnz = (int32_t)cols.size();
+    p.row_ptrs = rp;
+    p.cols = cols;
+    const IsaiRowClasses rc{32, 64, 2048};
+    for (int spd = 0; spd < 2; ++spd) {
+        IsaiStructure S;
+        int32_t wide = -1;
+        if (!build_isai_structure(p, spd != 0, 3, true, rc, ISAI_BUDGET, S, wide)) {
+            printf("   isai %s: row %d beyond %d entries\n", spd ? "spd" : "general", wide, rc.max_row);
+            continue;
+        }
+        // the transpose: map points at the source entry with (row, column) swapped; rows sorted; T(T(W)) = W
+        std::vector<int32_t> trp, tc, tmap, back_rp, back_c, back_map;
+        transpose_pattern(n, S.row_ptrs, S.cols, trp, tc, tmap);
+        if (spd) expect(trp == S.t_row_ptrs && tc == S.t_cols && tmap == S.t_map, "W^T is the shared transpose of W");
+        std::vector<int32_t> row_of(S.cols.size());
+        for (int32_t r = 0; r < n; ++r)
+            for (int32_t k = S.row_ptrs[r]; k < S.row_ptrs[r + 1]; ++k) row_of[k] = r;
+        bool map_ok = trp.size() == (size_t)n + 1 && tc.size() == S.cols.size(), sorted = true;
+        for (int32_t c = 0; map_ok && c < n; ++c)
+            for (int32_t e = trp[c]; e < trp[c + 1]; ++e) {
+                const int32_t k = tmap[e];
+                map_ok = map_ok && k >= 0 && (size_t)k < S.cols.size() && S.cols[k] == c && row_of[k] == tc[e];
+                sorted = sorted && (e == trp[c] || tc[e - 1] < tc[e]);
+            }
+        expect(map_ok, "every transposed entry maps to its source entry");
+        expect(sorted, "transposed rows sorted by column");
+        transpose_pattern(n, trp, tc, back_rp, back_c, back_map);
+        expect(back_rp == S.row_ptrs && back_c == S.cols, "transpose of the transpose is the original");
+        // wide / huge lists partition exactly the rows above the two thresholds
+        std::vector<int32_t> w, h;
+        int32_t max_row = 0;
+        for (int32_t r = 0; r < n; ++r) {
+            const int32_t len = S.row_ptrs[r + 1] - S.row_ptrs[r];
+            max_row = len > max_row ? len : max_row;
+            if (len > rc.wave_row) h.push_back(r);
+            else if (len > rc.thread_row) w.push_back(r);
+        }
+        expect(w == S.wide_rows && h == S.huge_rows && max_row == S.max_row, "wide and huge rows partition the long rows");
+        // batches: within the budget unless a single row; offsets of a batch tile [0, used) without overlap
+        const std::vector<int32_t> &B = S.huge_batches;
+        bool shape = !B.empty() && B.front() == 0 && B.back() == (int32_t)h.size() && S.huge_off.size() == h.size();
+        bool fits = true, tiles = true;
+        int64_t most = 0;
+        for (size_t b = 0; shape && b + 1 < B.size(); ++b) {
+            shape = shape && B[b] <= B[b + 1] && (B[b] < B[b + 1] || h.empty());
+            int64_t used = 0;
+            for (int32_t k = B[b]; k < B[b + 1]; ++k) {
+                const int64_t len = S.row_ptrs[S.huge_rows[k] + 1] - S.row_ptrs[S.huge_rows[k]];
+                tiles = tiles && S.huge_off[k] == used;
+                used += len * len;
+            }
+            fits = fits && (used <= ISAI_BUDGET || B[b + 1] - B[b] == 1);
+            most = used > most ? used : most;
+        }
+        expect(shape, "batches cover the huge rows in order");
+        expect(fits, "every batch within the budget unless it is a single row");
+        expect(tiles, "offsets within a batch do not overlap");
+        expect(most == S.scratch_len, "scratch length is the largest batch");
+        printf("   isai %s ok=%d max=%d wide=%zu huge=%zu batches=%zu\n", spd ? "spd" : "general", bad == 0, S.max_row,
+               S.wide_rows.size(), S.huge_rows.size(), h.empty() ? (size_t)0 : B.size() - 1);
+    }
+    return bad;
+}
+
 int main(int argc, char **argv) {
+    int bad = 0;
     for (int i = 1; i < argc; ++i) {
         FILE *f = fopen(argv[i], "rb");
         int32_t hdr[2];
@@ -62,6 +150,7 @@ int main(int argc, char **argv) {
                                                       ids.data(), sz.data(), snd.data(), nid.data());
         }
         printf("   numbering rcm rc=%d ratio %.3f  hilbert rc=%d ratio %.3f  renumbered %d\n", rc, r_rcm, rc_h, r_h, renumbered);
+        bad += check_isai(argv[i], n, rp, cols);
     }
-    return 0;
+    return bad ? 5 : 0;
 }
