@@ -339,6 +339,19 @@ int ogl_solver_download_solution(ogl_solver *s, ogl_scalar *psi);
 
 /* y = A x through the in-loop SpMV kernel (dist_mtx::apply, StoppingCriterion.C:29). */
 int ogl_solver_spmv(ogl_solver *s, const ogl_scalar *x, ogl_scalar *y);
+/* Mixed precision for GKOCG (property mixedPrecision 1, with innerRelTol 1e-4 and innerMaxIter 1000; DESIGN.md section
+ * 7c): the Krylov turns run in single precision on a single-precision copy of the matrix, as the inner solver of a
+ * double-precision iterative refinement -- residual, criterion, norm factor and x stay the double path's own, so the
+ * answer meets the same criterion on the true residual; refinement costs 10-30 % more turns.  Applies to GKOCG on one
+ * rank with preconditioner none or BJ with maxBlockSize 1; anything else with the property set fails the solve with
+ * OGL_ERR_UNSUPPORTED, a coefficient that overflows single precision with OGL_ERR_INVALID.  After a solve the properties
+ * mixedPrecisionInUse, mixedOuterSteps, mixedInnerTurns, mixedStopReason (0 criterion, 1 maxIter, 2 no progress, 3 inner
+ * breakdown) and mixedInnerLayout (2 half storage, 0 single-precision values beside the device CSR) describe it;
+ * ogl_perf::n_iterations is inner turns + 1.
+ * This call: y = A32 x through the inner SpMV of the layout in use (A32 = the coefficients rounded to single precision;
+ * x, y: host vectors of n_rows in the caller's cell order, every row summed from 0 in ascending column order in single
+ * precision).  One rank only. */
+int ogl_solver_spmv_f32(ogl_solver *s, const float *x, float *y);
 /* z = M^-1 r with the preconditioner of the last solve (r, z: host vectors of n_rows in the caller's cell order; the
  * local operator only).  OGL_ERR_STATE before the first solve. */
 int ogl_solver_apply_preconditioner(ogl_solver *s, const ogl_scalar *r, ogl_scalar *z);

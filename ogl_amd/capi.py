@@ -91,7 +91,7 @@ EXPORTED_SYMBOLS = [
     "ogl_solver_solve", "ogl_solver_history", "ogl_solver_export_system",
     "ogl_solver_get_property",
     "ogl_solver_set_property", "ogl_solver_apply_resident", "ogl_solver_upload_solution",
-    "ogl_solver_upload_rhs", "ogl_solver_download_solution", "ogl_solver_spmv", "ogl_solver_apply_preconditioner",
+    "ogl_solver_upload_rhs", "ogl_solver_download_solution", "ogl_solver_spmv", "ogl_solver_spmv_f32", "ogl_solver_apply_preconditioner",
     "ogl_solver_mg_level_dims", "ogl_solver_get_mg_level",
     "ogl_solver_time_spmv", "ogl_solver_reduce", "ogl_reduction_chunk_rows",
     "ogl_solver_matrix_dims", "ogl_solver_get_local_matrix", "ogl_solver_get_non_local_matrix",
@@ -360,6 +360,23 @@ class Solver:
         y = np.zeros_like(x)
         _check(lib().ogl_solver_spmv(self._h, _ps(x), _ps(y)))
         return y
+
+    def spmv_f32(self, x):
+        """y = A32 x through the inner SpMV of the mixed-precision mode (float32 in, float32 out, caller's cell order)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        y = np.zeros_like(x)
+        fp = C.POINTER(C.c_float)
+        _check(lib().ogl_solver_spmv_f32(self._h, x.ctypes.data_as(fp), y.ctypes.data_as(fp)))
+        return y
+
+    def set_mixed_precision(self, on=True, inner_rel_tol=None, inner_max_iter=None):
+        """The keywords mixedPrecision / innerRelTol / innerMaxIter for the next solves."""
+        self.set_property("mixedPrecision", 1.0 if on else 0.0)
+        if inner_rel_tol is not None:
+            self.set_property("innerRelTol", float(inner_rel_tol))
+        if inner_max_iter is not None:
+            self.set_property("innerMaxIter", float(inner_max_iter))
+        return self
 
     def apply_preconditioner(self, r):
         """z = M^-1 r with the preconditioner of the last solve (caller's cell order, local operator)."""

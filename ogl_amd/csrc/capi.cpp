@@ -406,6 +406,18 @@ extern "C" int ogl_solver_spmv(ogl_solver *s, const ogl_scalar *x, ogl_scalar *y
     OGL_GUARD_END
 }
 
+extern "C" int ogl_solver_spmv_f32(ogl_solver *s, const float *x, float *y)
+{
+    OGL_GUARD_BEGIN
+    if (!s || !x || !y) return fail(OGL_ERR_INVALID, "NULL argument");
+    if (!s->matrix_set) return fail(OGL_ERR_STATE, "spmv_f32 before set_matrix");
+    if (s->reg->comm && s->reg->comm->multi())
+        return fail(OGL_ERR_UNSUPPORTED, "spmv_f32: the mixed-precision mode runs on one rank (%d ranks)", s->reg->comm->n_ranks);
+    OGL_HIP_CHECK(hipSetDevice(s->reg->device));
+    return s->spmv_f32(x, y);
+    OGL_GUARD_END
+}
+
 extern "C" int ogl_solver_apply_preconditioner(ogl_solver *s, const ogl_scalar *r, ogl_scalar *z)
 {
     OGL_GUARD_BEGIN

@@ -687,4 +687,47 @@ void launch_finalize(hipStream_t st, int phase, DevScalars *s, const FinArgs &a)
 // cg::initialize scalars: rho = 0? (unused), prev_rho = 1, iter = 0, stop = 0, norm_factor = 1
 void launch_reset_scalars(hipStream_t st, DevScalars *s, const DevCriterion &crit);
 
+// --- mixed precision for GKOCG (kernels_mixed.hip; the contract: DESIGN.md section 7c) ---
+// fp32 inner CG on an fp32 copy of the matrix under an fp64 iterative refinement.  The scalars of both loops, resident on
+// the device like DevScalars: every inner kernel returns at once when inner_stop or outer_stop is set, the outer kernels
+// (the double path's own) gate on DevScalars::stop, which the outer check raises together with outer_stop.
+enum MixedStop { MIXED_STOP_CRITERION = 0, MIXED_STOP_MAX_ITER = 1, MIXED_STOP_NO_PROGRESS = 2, MIXED_STOP_BREAKDOWN = 3,
+                 MIXED_STOP_INVALID = 4 /* a value not representable in binary32: the solve fails */ };
+struct MixedScalars {
+    double rho, prev_rho, pi, tau, tau0;  // inner CG: wide sums (fp64)
+    double theta;                         // this outer step's inner tolerance on tau / tau0
+    double S, S_prev;                     // sum |r| of the fp64 residual at this / the previous outer check
+    double norm_factor, init_res, res;    // the criterion's (the double path's norm factor)
+    double inner_rel_tol;                 // keyword innerRelTol
+    float a32, b32;                       // fl32(rho / pi), fl32(rho / rho_prev)
+    int32_t use_beta;                     // 0: p = z (first turn of an inner solve, rho_prev == 0)
+    int32_t inner_stop, inner_turns, inner_cap, inner_nonfinite;
+    int32_t outer_stop, stop_reason, outer_steps, total_turns, n_evals;
+    int32_t bad_coef, bad_invd;           // first matrix value / inverse-diagonal row that overflows binary32 (INT_MAX: none)
+    int32_t inner_max_iter;               // keyword innerMaxIter
+    DevCriterion crit;
+};
+// out[i] = fl32(src[map[i]]) (0 where map[i] < 0; map == nullptr: src[i]); *bad = min(*bad, i) where a finite value overflows
+void launch_mixed_refresh(hipStream_t st, int64_t n, const int32_t *map, const double *src, float *out, int32_t *bad);
+void launch_mixed_reset(hipStream_t st, MixedScalars *m, const DevCriterion &crit, double inner_rel_tol, int inner_max_iter);
+// y = A32 x on the fp32 twin of the half storage's planes / on the fp32 value array beside the device CSR; every row from
+// 0.0f in ascending column order.  part != nullptr: the per-chunk partials of sum (double)x_i (double)y_i
+void launch_mixed_spmv_sym(hipStream_t st, const DevSym &A, const float *planes, const float *x, float *y, double *part,
+                           const MixedScalars *gate);
+void launch_mixed_spmv_csr(hipStream_t st, const DevCsr &A, const float *vals, const float *x, float *y, double *part,
+                           const MixedScalars *gate);
+// the check of an outer step on the partials of sum |r|, then the step's inner tolerance and budget (one workgroup)
+void launch_mixed_head(hipStream_t st, MixedScalars *m, DevScalars *s, const double *part, int32_t n_part, double *history);
+// r32 = fl32(r / S), z = r32 * inv_d (inv_d == nullptr: z is r32 itself and not written), u = 0; + the finaliser of rho, tau0
+void launch_mixed_start(hipStream_t st, int32_t n, const double *r, const float *inv_d, float *r32, float *z, float *u,
+                        double *part_rho, double *part_tau, MixedScalars *m);
+void launch_mixed_step1(hipStream_t st, int32_t n, float *p, const float *z, const MixedScalars *m);
+void launch_mixed_fin_pi(hipStream_t st, MixedScalars *m, const double *part, int32_t n_part);
+// u += a p, r -= a q, z = r * inv_d; + the finaliser of rho, tau and the inner stop gate
+void launch_mixed_step2(hipStream_t st, int32_t n, float *u, float *r, const float *p, const float *q, const float *inv_d,
+                        float *z, double *part_rho, double *part_tau, MixedScalars *m);
+void launch_mixed_add(hipStream_t st, int32_t n, double *x, const float *u, const MixedScalars *m);
+// scatter: out[new_id[i]] = in[i]; gather: out[i] = in[new_id[i]]
+void launch_mixed_permute(hipStream_t st, int32_t n, const int32_t *new_id, const float *in, float *out, bool gather);
+
 }  // namespace ogl

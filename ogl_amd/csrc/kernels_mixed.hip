@@ -1,0 +1,579 @@
+// kernels_mixed.hip -- mixed precision for GKOCG: the fp32 inner CG of an fp64 iterative
+// refinement.  Vectors and matrix values of the inner solve are binary32; every scalar is formed in fp64 from the wide
+// sums (products of the float64 casts, summed in the loop's reduction tree: device_common.hpp) and rounded once; there is
+// no fp32 division or square root.  Geometry as everywhere: one workgroup = one chunk of CHUNK_ROWS rows, thread t owns
+// rows 2t, 2t + 1 (one 8-byte load per vector), one partial per chunk.
+// (-ffp-contract=off: every fp32 product and every fp32 sum rounds once)
+#include <algorithm>
+#include <climits>
+
+#include "device_common.hpp"
+
+namespace ogl {
+
+namespace {
+
+__device__ __forceinline__ float2 ld2f(const float *__restrict__ p, const RowPair &r)
+{
+    float2 v;
+    if (r.n == 2) {
+        v = *reinterpret_cast<const float2 *>(p + r.row);
+    } else {
+        v.x = r.n == 1 ? p[r.row] : 0.0f;
+        v.y = 0.0f;
+    }
+    return v;
+}
+__device__ __forceinline__ void st2f(float *__restrict__ p, const RowPair &r, float2 v)
+{
+    if (r.n == 2)
+        *reinterpret_cast<float2 *>(p + r.row) = v;
+    else if (r.n == 1)
+        p[r.row] = v.x;
+}
+__device__ __forceinline__ bool mx_gated(const MixedScalars *m) { return m && (m->outer_stop || m->inner_stop); }
+__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }  // (false for NaN)
+
+// out[i] = fl32(map ? src[map[i]] (0 where map[i] < 0) : src[i]); *bad = the smallest i whose value is finite in fp64
+// and not in fp32
+__global__ __launch_bounds__(BLOCK) void k_mx_refresh(long n, const int *__restrict__ map, const double *__restrict__ src,
+                                                      float *__restrict__ out, int *bad)
+{
+    for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * BLOCK) {
+        double v = 0.0;
+        if (map) {
+            const int k = map[i];
+            if (k >= 0) v = src[k];
+        } else {
+            v = src[i];
+        }
+        const float f = (float)v;
+        out[i] = f;
+        if (finite_d(v) && !(fabsf(f) <= 3.402823466e38f)) atomicMin(bad, (int)min(i, (long)(INT_MAX - 1)));
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// the inner SpMV on the fp32 twin of the half storage (k_spmv_sym's loads and order of additions: furthest lower entry
+// first, diagonal, upper entries -- ascending columns, every row from 0.0f) with the partial of pi = wide(p, q)
+// ------------------------------------------------------------------------------------------
+struct MxOffsets {
+    int d[SYM_MAX_OFFSETS];
+};
+template <int ND, bool FAST>
+__global__ __launch_bounds__(BLOCK) void k_mx_spmv_sym(int n_rows, int n_chunks, MxOffsets off,
+                                                       const uint8_t *__restrict__ mask, const float *__restrict__ planes,
+                                                       const float *__restrict__ x, float *__restrict__ y,
+                                                       double *__restrict__ part, const MixedScalars *gate,
+                                                       const int *__restrict__ block_order)
+{
+    __shared__ double slot[N_WAVES];
+    if (mx_gated(gate)) return;
+    const int chunk = block_order ? block_order[blockIdx.x] : xcd_chunk(blockIdx.x);
+    if (chunk < 0 || chunk >= n_chunks) return;
+    const RowPair rp = my_rows(chunk, n_rows);
+    const int t = threadIdx.x, row = rp.row;
+    const unsigned mm = *reinterpret_cast<const unsigned short *>(mask + row);
+    const unsigned m0 = mm & 0xffu, m1 = mm >> 8;
+    float2 up[ND];
+    const float *own = planes + (long)chunk * (ND * CHUNK_ROWS) + t * ROWS_PER_THREAD;
+#pragma unroll
+    for (int j = 0; j < ND; ++j) up[j] = *reinterpret_cast<const float2 *>(own + (long)j * CHUNK_ROWS);
+    const float2 xd = ld2f(x, rp);
+    // every load is issued whatever the mask says, at an index clamped into its array (the mask decides what is used)
+    const int last = n_rows - 1, last_pair = last & ~1;  // (the vectors are allocated past n_rows)
+    float2 lo[ND], xl[ND], xu[ND];
+#pragma unroll
+    for (int j = 1; j < ND; ++j) {
+        const int r0 = max(row - off.d[j], 0), r1 = max(row + 1 - off.d[j], 0);
+        const long a0 = (long)(r0 >> 9) * (ND * CHUNK_ROWS) + (long)j * CHUNK_ROWS + (r0 & (CHUNK_ROWS - 1));
+        const long a1 = (long)(r1 >> 9) * (ND * CHUNK_ROWS) + (long)j * CHUNK_ROWS + (r1 & (CHUNK_ROWS - 1));
+        if (FAST && j >= 2) {  // even distance: an aligned pair of one chunk's plane
+            lo[j] = *reinterpret_cast<const float2 *>(planes + a0);
+            xl[j] = *reinterpret_cast<const float2 *>(x + min(max(row - off.d[j], 0), last_pair));
+            xu[j] = *reinterpret_cast<const float2 *>(x + min(row + off.d[j], last_pair));
+        } else if (FAST) {     // d = 1: A(row + 1, row) is this lane's own upper entry of row
+            lo[j].x = planes[a0];
+            lo[j].y = up[1].x;
+            xl[j].x = x[min(max(row - 1, 0), last)];
+            xl[j].y = xd.x;
+            xu[j].x = xd.y;
+            xu[j].y = x[min(row + 2, last)];
+        } else {
+            lo[j].x = planes[a0];
+            lo[j].y = planes[a1];
+            xl[j].x = x[min(max(row - off.d[j], 0), last)];
+            xl[j].y = x[min(max(row + 1 - off.d[j], 0), last)];
+            xu[j].x = x[min(row + off.d[j], last)];
+            xu[j].y = x[min(row + 1 + off.d[j], last)];
+        }
+    }
+    static_assert(CHUNK_ROWS == 512, "row >> 9 above");
+    float2 acc;
+    acc.x = acc.y = 0.0f;
+#pragma unroll
+    for (int j = ND - 1; j >= 1; --j) {
+        if ((m0 >> (ND - 1 - j)) & 1u) acc.x = acc.x + lo[j].x * xl[j].x;
+        if ((m1 >> (ND - 1 - j)) & 1u) acc.y = acc.y + lo[j].y * xl[j].y;
+    }
+    if ((m0 >> (ND - 1)) & 1u) acc.x = acc.x + up[0].x * xd.x;
+    if ((m1 >> (ND - 1)) & 1u) acc.y = acc.y + up[0].y * xd.y;
+#pragma unroll
+    for (int j = 1; j < ND; ++j) {
+        if ((m0 >> (ND - 1 + j)) & 1u) acc.x = acc.x + up[j].x * xu[j].x;
+        if ((m1 >> (ND - 1 + j)) & 1u) acc.y = acc.y + up[j].y * xu[j].y;
+    }
+    st2f(y, rp, acc);
+    if (part) {
+        double d = 0.0;
+        if (rp.n > 0) d += (double)xd.x * (double)acc.x;
+        if (rp.n > 1) d += (double)xd.y * (double)acc.y;
+        const double s = block_sum(d, slot);
+        if (threadIdx.x == 0) part[chunk] = s;
+    }
+}
+
+// ... and on the fp32 value array beside the device CSR (k_spmv_stream's walk: the chunk's entries as 8-byte value and
+// column pairs, the products parked in LDS, every thread adds up its rows left to right)
+__global__ __launch_bounds__(BLOCK) void k_mx_spmv_csr(int n_rows, int n_chunks, const int *__restrict__ row_ptrs,
+                                                       const int *__restrict__ cols, const float *__restrict__ vals,
+                                                       const float *__restrict__ x, float *__restrict__ y,
+                                                       double *__restrict__ part, const MixedScalars *gate, int xgroup,
+                                                       const int *__restrict__ block_order)
+{
+    __shared__ __attribute__((aligned(16))) float prod[SPMV_TILE];
+    __shared__ double slot[N_WAVES];
+    if (mx_gated(gate)) return;
+    const int chunk = block_order ? block_order[blockIdx.x] : xcd_chunk(blockIdx.x, xgroup);
+    if (chunk < 0 || chunk >= n_chunks) return;
+    const int tid = threadIdx.x;
+    const int r0 = chunk * CHUNK_ROWS;
+    const int r1 = min(r0 + CHUNK_ROWS, n_rows);
+    const int nz0 = row_ptrs[r0];
+    const int nz1 = row_ptrs[r1];
+    const int row = r0 + tid * ROWS_PER_THREAD;
+    int rs[ROWS_PER_THREAD + 1];
+#pragma unroll
+    for (int j = 0; j <= ROWS_PER_THREAD; ++j) rs[j] = row_ptrs[min(row + j, r1)];
+    float acc[ROWS_PER_THREAD] = {0.0f, 0.0f};
+    constexpr int GROUPS = SPMV_TILE / (BLOCK * 2);
+    for (int t0 = nz0 & ~3; t0 < nz1; t0 += SPMV_TILE) {
+        float2 va[GROUPS];
+        int2 cc[GROUPS];
+#pragma unroll
+        for (int g = 0; g < GROUPS; ++g) {
+            const int e = t0 + (g * BLOCK + tid) * 2;
+            const int ec = e < nz1 ? e : t0;  // clamp: stay inside the (padded) arrays
+            va[g] = *reinterpret_cast<const float2 *>(vals + ec);
+            cc[g] = *reinterpret_cast<const int2 *>(cols + ec);
+        }
+#pragma unroll
+        for (int g = 0; g < GROUPS; ++g) {
+            float2 pr;
+            pr.x = va[g].x * x[cc[g].x];
+            pr.y = va[g].y * x[cc[g].y];
+            *reinterpret_cast<float2 *>(prod + (g * BLOCK + tid) * 2) = pr;
+        }
+        __syncthreads();
+        const int t1 = t0 + SPMV_TILE;
+#pragma unroll
+        for (int j = 0; j < ROWS_PER_THREAD; ++j) {
+            const int kb = max(rs[j], t0), ke = min(rs[j + 1], t1);
+            for (int k = kb; k < ke; ++k) acc[j] = acc[j] + prod[k - t0];
+        }
+        __syncthreads();
+    }
+    double d = 0.0;
+#pragma unroll
+    for (int j = 0; j < ROWS_PER_THREAD; ++j) {
+        if (row + j < r1) {
+            y[row + j] = acc[j];
+            if (part) d += (double)x[row + j] * (double)acc[j];
+        }
+    }
+    if (part) {
+        const double s = block_sum(d, slot);
+        if (tid == 0) part[chunk] = s;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// vector kernels of the inner solve
+// ------------------------------------------------------------------------------------------
+// O3 + start: r32 = fl32(r / S), z = r32 * inv_d32 (or r32 itself), u = 0; partials of rho = wide(r32, z), tau0 = wide1(r32)
+__global__ __launch_bounds__(BLOCK) void k_mx_start(int n, const double *__restrict__ r, const float *__restrict__ inv_d,
+                                                    float *__restrict__ r32, float *__restrict__ z, float *__restrict__ u,
+                                                    double *__restrict__ part_rho, double *__restrict__ part_tau,
+                                                    const MixedScalars *m)
+{
+    __shared__ double slot[2 * N_WAVES];
+    if (m->outer_stop) return;
+    const double S = m->S;
+    const int chunk = blockIdx.x;
+    const RowPair rp = my_rows(chunk, n);
+    const double2 rd = ld2(r, rp);
+    float2 rv, zv, zero;
+    rv.x = rp.n > 0 ? (float)(rd.x / S) : 0.0f;
+    rv.y = rp.n > 1 ? (float)(rd.y / S) : 0.0f;
+    zero.x = zero.y = 0.0f;
+    zv = rv;
+    if (inv_d) {
+        const float2 dv = ld2f(inv_d, rp);
+        zv.x = rv.x * dv.x;
+        zv.y = rv.y * dv.y;
+        st2f(z, rp, zv);
+    }
+    st2f(r32, rp, rv);
+    st2f(u, rp, zero);
+    double a = 0.0, b = 0.0;
+    if (rp.n > 0) {
+        a += (double)rv.x * (double)zv.x;
+        b += fabs((double)rv.x);
+    }
+    if (rp.n > 1) {
+        a += (double)rv.y * (double)zv.y;
+        b += fabs((double)rv.y);
+    }
+    block_sum2(a, b, slot);
+    if (threadIdx.x == 0) {
+        part_rho[chunk] = a;
+        part_tau[chunk] = b;
+    }
+}
+
+// step 1: p = z + fl32(rho / rho_prev) p, or p = z (first turn, rho_prev == 0)
+__global__ __launch_bounds__(BLOCK) void k_mx_step1(int n, float *__restrict__ p, const float *__restrict__ z,
+                                                    const MixedScalars *m)
+{
+    if (mx_gated(m)) return;
+    const int use_beta = m->use_beta;
+    const float b32 = m->b32;
+    const RowPair rp = my_rows(blockIdx.x, n);
+    float2 zv = ld2f(z, rp);
+    if (use_beta) {
+        const float2 pv = ld2f(p, rp);
+        const float t0 = b32 * pv.x, t1 = b32 * pv.y;
+        zv.x = zv.x + t0;
+        zv.y = zv.y + t1;
+    }
+    st2f(p, rp, zv);
+}
+
+// steps 4 and 5: u += a p, r -= a q, z = r * inv_d32; partials of rho = wide(r, z), tau = wide1(r)
+__global__ __launch_bounds__(BLOCK) void k_mx_step2(int n, float *__restrict__ u, float *__restrict__ r,
+                                                    const float *__restrict__ p, const float *__restrict__ q,
+                                                    const float *__restrict__ inv_d, float *__restrict__ z,
+                                                    double *__restrict__ part_rho, double *__restrict__ part_tau,
+                                                    const MixedScalars *m)
+{
+    __shared__ double slot[2 * N_WAVES];
+    if (mx_gated(m)) return;
+    const float a32 = m->a32;
+    const int chunk = blockIdx.x;
+    const RowPair rp = my_rows(chunk, n);
+    const float2 pv = ld2f(p, rp), qv = ld2f(q, rp);
+    float2 uv = ld2f(u, rp), rv = ld2f(r, rp);
+    const float up0 = a32 * pv.x, up1 = a32 * pv.y, rq0 = a32 * qv.x, rq1 = a32 * qv.y;
+    uv.x = uv.x + up0;
+    uv.y = uv.y + up1;
+    rv.x = rv.x - rq0;
+    rv.y = rv.y - rq1;
+    st2f(u, rp, uv);
+    st2f(r, rp, rv);
+    float2 zv = rv;
+    if (inv_d) {
+        const float2 dv = ld2f(inv_d, rp);
+        zv.x = rv.x * dv.x;
+        zv.y = rv.y * dv.y;
+        st2f(z, rp, zv);
+    }
+    double a = 0.0, b = 0.0;
+    if (rp.n > 0) {
+        a += (double)rv.x * (double)zv.x;
+        b += fabs((double)rv.x);
+    }
+    if (rp.n > 1) {
+        a += (double)rv.y * (double)zv.y;
+        b += fabs((double)rv.y);
+    }
+    block_sum2(a, b, slot);
+    if (threadIdx.x == 0) {
+        part_rho[chunk] = a;
+        part_tau[chunk] = b;
+    }
+}
+
+// O5: x += S * (double)u, product and sum rounded separately; not after a stop of the outer loop, not when the inner solve
+// ended on a non-finite scalar
+__global__ __launch_bounds__(BLOCK) void k_mx_add(int n, double *__restrict__ x, const float *__restrict__ u,
+                                                  const MixedScalars *m)
+{
+    if (m->outer_stop || m->inner_nonfinite) return;
+    const double S = m->S;
+    const RowPair rp = my_rows(blockIdx.x, n);
+    const float2 uv = ld2f(u, rp);
+    double2 xv = ld2(x, rp);
+    const double t0 = S * (double)uv.x, t1 = S * (double)uv.y;
+    xv.x = xv.x + t0;
+    xv.y = xv.y + t1;
+    st2(x, rp, xv);
+}
+
+// out[new_id[i]] = in[i] (scatter) | out[i] = in[new_id[i]] (gather): ogl_solver_spmv_f32 on a renumbered device copy
+__global__ __launch_bounds__(BLOCK) void k_mx_permute(int n, const int *__restrict__ new_id, const float *__restrict__ in,
+                                                      float *__restrict__ out, int gather)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    if (gather)
+        out[i] = in[new_id[i]];
+    else
+        out[new_id[i]] = in[i];
+}
+
+// ------------------------------------------------------------------------------------------
+// finalisers (one workgroup, the finaliser's tree): scalars in fp64, every quotient rounded once to binary32
+// ------------------------------------------------------------------------------------------
+enum MxPhase { MX_START = 0, MX_PI = 1, MX_RHO = 2 };
+template <int PHASE>
+__global__ __launch_bounds__(FIN_BLOCK) void k_mx_fin(MixedScalars *m, const double *part0, const double *part1, int n_part)
+{
+    __shared__ double slot[FIN_WAVES];
+    if (m->outer_stop || m->inner_stop) return;
+    const double *const parts[2] = {part0, part1};
+    double v[2];
+    if (PHASE == MX_PI)
+        reduce_partials<1>(parts, n_part, slot, v);
+    else
+        reduce_partials<2>(parts, n_part, slot, v);
+    if (threadIdx.x != 0) return;
+    if (PHASE == MX_START) {  // rho = wide(r, z), tau0 = wide1(r); L turns allowed
+        m->rho = v[0];
+        m->tau0 = v[1];
+        m->tau = v[1];
+        if (!finite_d(v[0]) || !finite_d(v[1])) {
+            m->inner_nonfinite = 1;
+            m->inner_stop = 1;
+        } else if (m->inner_cap < 1) {
+            m->inner_stop = 1;
+        }
+    } else if (PHASE == MX_PI) {  // pi = wide(p, q); a = fl32(rho / pi)
+        const double pi = v[0];
+        m->pi = pi;
+        if (pi == 0.0) {  // the turn is not counted
+            m->inner_stop = 1;
+        } else if (!finite_d(pi)) {
+            m->inner_turns = m->inner_turns + 1;
+            m->inner_nonfinite = 1;
+            m->inner_stop = 1;
+        } else {
+            m->a32 = (float)(m->rho / pi);
+        }
+    } else {  // rho_prev = rho, rho = wide(r, z), tau = wide1(r); the inner stop gate
+        const double rho_prev = m->rho, rho = v[0], tau = v[1];
+        const int j = m->inner_turns + 1;
+        m->prev_rho = rho_prev;
+        m->rho = rho;
+        m->tau = tau;
+        m->inner_turns = j;
+        if (!finite_d(rho) || !finite_d(tau)) {
+            m->inner_nonfinite = 1;
+            m->inner_stop = 1;
+        } else {
+            m->use_beta = rho_prev != 0.0 ? 1 : 0;
+            if (rho_prev != 0.0) m->b32 = (float)(rho / rho_prev);
+            if (tau <= m->theta * m->tau0 || j >= m->inner_cap) m->inner_stop = 1;
+        }
+    }
+}
+
+// O1 + O2: S = sum |r| (the partials of the residual), the check of outer step k, then this step's inner tolerance and
+// budget.  `s`: the double path's scalars -- its norm factor is read, its stop flag raised with the outer stop (the outer
+// kernels are the double path's own and gate on it).
+__global__ __launch_bounds__(FIN_BLOCK) void k_mx_head(MixedScalars *m, DevScalars *s, const double *part, int n_part,
+                                                       double *history)
+{
+    __shared__ double slot[FIN_WAVES];
+    if (m->outer_stop) return;
+    const double *const parts[2] = {part, nullptr};
+    double v[2];
+    reduce_partials<1>(parts, n_part, slot, v);
+    if (threadIdx.x != 0) return;
+    const double S = v[0], S_prev = m->S;
+    const int k = m->outer_steps, T = m->total_turns + m->inner_turns;
+    const int prev_turns = m->inner_turns;
+    const double nf = s->norm_factor;
+    m->total_turns = T;
+    m->S_prev = S_prev;
+    m->S = S;
+    m->norm_factor = nf;
+    int stop = 0, reason = 0;
+    if (m->bad_coef != INT_MAX || m->bad_invd != INT_MAX) {  // a value not representable in binary32: the solve fails
+        stop = 1;
+        reason = MIXED_STOP_INVALID;
+    }
+    CritVals c = load_criterion(m->crit);
+    c.frequency = 1;
+    const int n_evals = m->n_evals;
+    const Verdict vd = criterion_verdict(c, T, n_evals, m->init_res, nf, S, nullptr);
+    if (vd.evaluated) {
+        if (c.export_res && history) history[n_evals] = vd.res;
+        m->n_evals = vd.n_evals;
+        m->init_res = vd.init_res;
+        m->res = vd.res;
+    }
+    if (!stop && vd.stop) {
+        stop = 1;
+        const bool met = vd.res < c.tolerance || (c.rel_tol > 0 && vd.res < c.rel_tol * vd.init_res);
+        reason = met ? MIXED_STOP_CRITERION : MIXED_STOP_MAX_ITER;
+    }
+    if (!stop && k >= 1) {
+        if (prev_turns == 0) {
+            stop = 1;
+            reason = MIXED_STOP_BREAKDOWN;
+        } else if (S >= S_prev || !finite_d(S)) {
+            stop = 1;
+            reason = MIXED_STOP_NO_PROGRESS;
+        } else if (S == 0.0) {
+            stop = 1;
+            reason = MIXED_STOP_CRITERION;
+        }
+    }
+    m->inner_turns = 0;
+    if (stop) {
+        m->outer_stop = 1;
+        m->stop_reason = reason;
+        s->stop = 1;
+        return;
+    }
+    const double res = S / nf;
+    const double want_abs = c.tolerance, want_rel = c.rel_tol * vd.init_res;
+    const double nu = (want_abs > want_rel ? want_abs : want_rel) / res;
+    const double half_nu = 0.5 * nu, floor_tol = m->inner_rel_tol;
+    m->theta = floor_tol > half_nu ? floor_tol : half_nu;
+    const int left = c.max_iter - T;
+    m->inner_cap = m->inner_max_iter < left ? m->inner_max_iter : left;
+    m->outer_steps = k + 1;
+    m->inner_stop = 0;
+    m->inner_nonfinite = 0;
+    m->use_beta = 0;
+}
+
+__global__ void k_mx_reset(MixedScalars *m, DevCriterion crit, double inner_rel_tol, int inner_max_iter)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    MixedScalars z{};
+    z.crit = crit;
+    z.inner_rel_tol = inner_rel_tol;
+    z.inner_max_iter = inner_max_iter;
+    z.bad_coef = INT_MAX;
+    z.bad_invd = INT_MAX;
+    *m = z;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------
+void launch_mixed_refresh(hipStream_t st, int64_t n, const int32_t *map, const double *src, float *out, int32_t *bad)
+{
+    if (n <= 0) return;
+    const int64_t blocks = std::min<int64_t>((n + BLOCK - 1) / BLOCK, 8192);
+    hipLaunchKernelGGL(k_mx_refresh, dim3((unsigned)blocks), dim3(BLOCK), 0, st, (long)n, map, src, out, bad);
+}
+
+void launch_mixed_reset(hipStream_t st, MixedScalars *m, const DevCriterion &crit, double inner_rel_tol, int inner_max_iter)
+{
+    hipLaunchKernelGGL(k_mx_reset, dim3(1), dim3(64), 0, st, m, crit, inner_rel_tol, inner_max_iter);
+}
+
+void launch_mixed_spmv_sym(hipStream_t st, const DevSym &A, const float *planes, const float *x, float *y, double *part,
+                           const MixedScalars *gate)
+{
+    if (A.n_rows == 0) return;
+    const int nc = (int)n_chunks(A.n_rows);
+    const dim3 grid(A.block_order ? A.n_blocks : xcd_grid(nc)), block(BLOCK);
+    MxOffsets off;
+    for (int j = 0; j < SYM_MAX_OFFSETS; ++j) off.d[j] = A.d[j];
+    bool fast = A.nd >= 2 && A.d[1] == 1;
+    for (int j = 2; j < A.nd; ++j) fast = fast && (A.d[j] % 2 == 0);
+#define OGL_MX_SYM(ND)                                                                                                  \
+    do {                                                                                                                \
+        if (fast)                                                                                                       \
+            hipLaunchKernelGGL((k_mx_spmv_sym<ND, true>), grid, block, 0, st, A.n_rows, nc, off, A.mask, planes, x, y,   \
+                               part, gate, A.block_order);                                                              \
+        else                                                                                                            \
+            hipLaunchKernelGGL((k_mx_spmv_sym<ND, false>), grid, block, 0, st, A.n_rows, nc, off, A.mask, planes, x, y,  \
+                               part, gate, A.block_order);                                                              \
+    } while (0)
+    if (A.nd == 2)
+        OGL_MX_SYM(2);
+    else if (A.nd == 3)
+        OGL_MX_SYM(3);
+    else
+        OGL_MX_SYM(4);
+    static_assert(SYM_MAX_OFFSETS == 4, "instantiations above");
+#undef OGL_MX_SYM
+}
+
+void launch_mixed_spmv_csr(hipStream_t st, const DevCsr &A, const float *vals, const float *x, float *y, double *part,
+                           const MixedScalars *gate)
+{
+    if (A.n_rows == 0) return;
+    const int nc = (int)n_chunks(A.n_rows);
+    const int xg = A.xcd_group > 0 ? A.xcd_group : XCD_GROUP;
+    const dim3 grid(A.block_order ? A.n_blocks : xcd_grid(nc, xg)), block(BLOCK);
+    hipLaunchKernelGGL(k_mx_spmv_csr, grid, block, 0, st, A.n_rows, nc, A.row_ptrs, A.cols, vals, x, y, part, gate, xg,
+                       A.block_order);
+}
+
+void launch_mixed_head(hipStream_t st, MixedScalars *m, DevScalars *s, const double *part, int32_t n_part, double *history)
+{
+    hipLaunchKernelGGL(k_mx_head, dim3(1), dim3(FIN_BLOCK), 0, st, m, s, part, n_part, history);
+}
+
+void launch_mixed_start(hipStream_t st, int32_t n, const double *r, const float *inv_d, float *r32, float *z, float *u,
+                        double *part_rho, double *part_tau, MixedScalars *m)
+{
+    const int nc = (int)n_chunks(n);
+    if (nc == 0) return;
+    hipLaunchKernelGGL(k_mx_start, dim3(nc), dim3(BLOCK), 0, st, n, r, inv_d, r32, z, u, part_rho, part_tau, m);
+    hipLaunchKernelGGL((k_mx_fin<MX_START>), dim3(1), dim3(FIN_BLOCK), 0, st, m, part_rho, part_tau, nc);
+}
+
+void launch_mixed_step1(hipStream_t st, int32_t n, float *p, const float *z, const MixedScalars *m)
+{
+    const int nc = (int)n_chunks(n);
+    if (nc == 0) return;
+    hipLaunchKernelGGL(k_mx_step1, dim3(nc), dim3(BLOCK), 0, st, n, p, z, m);
+}
+
+void launch_mixed_fin_pi(hipStream_t st, MixedScalars *m, const double *part, int32_t n_part)
+{
+    hipLaunchKernelGGL((k_mx_fin<MX_PI>), dim3(1), dim3(FIN_BLOCK), 0, st, m, part, nullptr, n_part);
+}
+
+void launch_mixed_step2(hipStream_t st, int32_t n, float *u, float *r, const float *p, const float *q, const float *inv_d,
+                        float *z, double *part_rho, double *part_tau, MixedScalars *m)
+{
+    const int nc = (int)n_chunks(n);
+    if (nc == 0) return;
+    hipLaunchKernelGGL(k_mx_step2, dim3(nc), dim3(BLOCK), 0, st, n, u, r, p, q, inv_d, z, part_rho, part_tau, m);
+    hipLaunchKernelGGL((k_mx_fin<MX_RHO>), dim3(1), dim3(FIN_BLOCK), 0, st, m, part_rho, part_tau, nc);
+}
+
+void launch_mixed_add(hipStream_t st, int32_t n, double *x, const float *u, const MixedScalars *m)
+{
+    const int nc = (int)n_chunks(n);
+    if (nc == 0) return;
+    hipLaunchKernelGGL(k_mx_add, dim3(nc), dim3(BLOCK), 0, st, n, x, u, m);
+}
+
+void launch_mixed_permute(hipStream_t st, int32_t n, const int32_t *new_id, const float *in, float *out, bool gather)
+{
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_mx_permute, dim3(blocks_for(n)), dim3(BLOCK), 0, st, n, new_id, in, out, gather ? 1 : 0);
+}
+
+}  // namespace ogl

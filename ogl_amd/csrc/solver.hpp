@@ -305,6 +305,22 @@ struct PrecondData {
     }
 };
 
+// Mixed precision for GKOCG (solver_mixed.cpp): the fp32 vectors of the inner solve, the fp32
+// inverse diagonal, the scalars of both loops with their pinned poll slots, and a staging vector for ogl_solver_spmv_f32.
+// Allocated at the first mixed solve and kept.
+struct MixedPart {
+    DevBuf<float> u, r, z, p, q, inv_d, io;
+    DevBuf<MixedScalars> scal;
+    MixedScalars *h_scal = nullptr;  // pinned, 2 slots
+    void release()
+    {
+        for (DevBuf<float> *b : {&u, &r, &z, &p, &q, &inv_d, &io}) b->release();
+        scal.release();
+        ledger::pinned_free(h_scal);
+        h_scal = nullptr;
+    }
+};
+
 }  // namespace ogl
 
 struct ogl_solver;
@@ -377,6 +393,7 @@ struct ogl_solver {
     ogl::SymxDev symx_dev;
     ogl::SellDev sell_dev;
     ogl::Stream21Dev s21_dev;
+    ogl::Fp32Dev fp32_dev;  // the fp32 copy the mixed-precision inner solve runs on
     uint64_t vals_epoch = 0;  // bumped by every coefficient upload into d_vals
     void refresh_values(ogl::SpmvLayout l);
     void release_layout(ogl::SpmvLayout l);
@@ -550,6 +567,15 @@ struct ogl_solver {
     int run_cg(ogl_perf *perf);
     int run_bicgstab(ogl_perf *perf);
     int run_krylov(ogl_perf *perf);
+    // mixed precision (property mixedPrecision; solver_mixed.cpp): fp32 inner CG under an fp64 iterative refinement
+    ogl::MixedPart mixed;
+    int mixed_requested(bool *on);      // the keywords' validation and the refusals (OGL_ERR_INVALID / _UNSUPPORTED)
+    // buffers, the scalars reset for a solve, the fp32 copy of the matrix current for this values epoch
+    int mixed_storage(const ogl::DevCriterion &crit, double inner_rel_tol, int inner_max_iter);
+    int mixed_overflow(const ogl::MixedScalars &m);  // OGL_ERR_INVALID naming the row when a value overflowed binary32
+    void mixed_spmv(const float *x, float *y, double *part, const ogl::MixedScalars *gate);
+    int run_mixed(ogl_perf *perf);
+    int spmv_f32(const float *x, float *y);
     // run_krylov = plan -> prepare -> loop -> finish; one function per solver x turn shape (solver.cpp)
     struct KrylovRun;
     int krylov_plan(KrylovRun &k);

@@ -239,6 +239,10 @@ int ogl_solver::run_bicgstab(ogl_perf *perf) { return run_krylov(perf); }
 
 int ogl_solver::run_krylov(ogl_perf *perf)
 {
+    bool mixed_on = false;  // (property mixedPrecision: solver_mixed.cpp)
+    OGL_TRY(mixed_requested(&mixed_on));
+    if (mixed_on) return run_mixed(perf);
+    props["mixedPrecisionInUse"] = 0.0;
     KrylovRun k;
     OGL_TRY(krylov_plan(k));
     OGL_TRY(krylov_prepare(k));
@@ -1184,6 +1188,8 @@ int ogl_solver::apply_resident(ogl_perf *perf)
     ogl_perf local{};
     if (!perf) perf = &local;
     TraceRange trace("solve", field);
+    bool mixed_on = false;  // (refused before anything is generated for it)
+    OGL_TRY(mixed_requested(&mixed_on));
     {
         TraceRange trace_pc("init_preconditioner", field);
         OGL_TRY(init_preconditioner());

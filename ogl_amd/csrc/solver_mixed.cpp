@@ -1,0 +1,285 @@
+// solver_mixed.cpp -- mixed precision for GKOCG (property mixedPrecision; the contract: DESIGN.md section 7c): the Krylov
+// turns run in fp32 on an fp32 copy of the matrix, as the inner solver of an fp64 iterative refinement whose residual,
+// criterion, norm factor and x are the double path's own.  The host enqueues and polls as krylov_loop does: batches of
+// inner turns with the stop flags looked at one batch late, every kernel past a stop a no-op.
+// See solver.hpp, solver_internal.hpp, kernels_mixed.hip.
+#include "solver_internal.hpp"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <vector>
+
+using namespace ogl;
+
+namespace {
+
+const char *solver_name(int kind)
+{
+    return kind == OGL_SOLVER_CG ? "GKOCG" : kind == OGL_SOLVER_BICGSTAB ? "GKOBiCGStab" : "GKOGMRES";
+}
+
+int32_t *word_of(MixedScalars *m, size_t offset) { return reinterpret_cast<int32_t *>(reinterpret_cast<char *>(m) + offset); }
+
+}  // namespace
+
+// The keywords (properties of the same name) and where the mode applies: GKOCG, one rank, preconditioner none or BJ with
+// maxBlockSize 1.  Anything else with mixedPrecision set is refused, none silently.
+int ogl_solver::mixed_requested(bool *on)
+{
+    *on = prop("mixedPrecision", 0.0) != 0.0;
+    if (!*on) return OGL_OK;
+    const double inner_rel_tol = prop("innerRelTol", 1e-4), inner_max_iter = prop("innerMaxIter", 1000.0);
+    if (!(inner_rel_tol > 0.0 && inner_rel_tol < 1.0))
+        return fail(OGL_ERR_INVALID, "innerRelTol %g outside (0, 1)", inner_rel_tol);
+    if (!(inner_max_iter >= 1.0)) return fail(OGL_ERR_INVALID, "innerMaxIter %g below 1", inner_max_iter);
+    const PrecondKind kind = precond_kind_of(cfg);
+    const bool precond_ok = cfg.preconditioner == OGL_PRECOND_NONE || kind == PrecondKind::Jacobi;
+    const int n_ranks = reg->comm ? reg->comm->n_ranks : 1;
+    if (cfg.solver != OGL_SOLVER_CG || !precond_ok || n_ranks > 1)
+        return fail(OGL_ERR_UNSUPPORTED,
+                    "mixedPrecision runs GKOCG on one rank with preconditioner none or BJ with maxBlockSize 1: this is "
+                    "solver %s, preconditioner %s (maxBlockSize %d), %d rank(s)",
+                    solver_name(cfg.solver), cfg.preconditioner == OGL_PRECOND_NONE ? "none" : precond_name(kind),
+                    cfg.max_block_size, n_ranks);
+    return OGL_OK;
+}
+
+// The vectors and scalars of the mode, reset for a solve, and the fp32 copy of the matrix current for this coefficient
+// upload: the twin of the half storage's planes when the in-loop SpMV runs there, the value array beside the device
+// CSR on every other in-loop layout.
+int ogl_solver::mixed_storage(const DevCriterion &crit, double inner_rel_tol, int inner_max_iter)
+{
+    hipStream_t st = reg->stream;
+    const size_t nv = (size_t)pat.n_rows + 4;  // (a trailing pair access of the last odd row stays inside)
+    for (DevBuf<float> *b : {&mixed.u, &mixed.r, &mixed.z, &mixed.p, &mixed.q, &mixed.inv_d}) OGL_TRY(b->alloc(nv, st));
+    OGL_TRY(mixed.scal.alloc(1, st));
+    if (!mixed.h_scal)
+        OGL_HIP_CHECK(ledger::pinned_malloc(reinterpret_cast<void **>(&mixed.h_scal), 2 * sizeof(MixedScalars)));
+    launch_mixed_reset(st, mixed.scal.p, crit, inner_rel_tol, inner_max_iter);
+    const bool half = spmv_layout == SpmvLayout::Sym;
+    if (half) refresh_values(SpmvLayout::Sym);
+    OGL_TRY(fp32_dev.ensure(half, pat_id, half ? sym_dev.map.n : d_vals.n, st));
+    if (fp32_dev.epoch != vals_epoch || vals_epoch == 0) {
+        fp32_dev.refresh(half ? sym_dev.map.p : nullptr, d_vals.p, word_of(mixed.scal.p, offsetof(MixedScalars, bad_coef)), st);
+        fp32_dev.epoch = vals_epoch;
+    }
+    props["mixedInnerLayout"] = half ? 2.0 : 0.0;  // (spmvLayout's codes: 2 half storage, 0 the CSR arrays)
+    return OGL_OK;
+}
+
+void ogl_solver::mixed_spmv(const float *x, float *y, double *part, const MixedScalars *gate)
+{
+    if (fp32_dev.half)
+        launch_mixed_spmv_sym(reg->stream, sym(), fp32_dev.planes.p, x, y, part, gate);
+    else
+        launch_mixed_spmv_csr(reg->stream, csr(false), fp32_dev.vals.p, x, y, part, gate);
+}
+
+// A coefficient or an inverse diagonal that is finite in fp64 and not in binary32: the solve fails and names the row
+// (the caller's numbering).  The copy is marked stale, so that the next call converts -- and reports -- again.
+int ogl_solver::mixed_overflow(const MixedScalars &m)
+{
+    if (m.bad_coef == INT_MAX && m.bad_invd == INT_MAX) return OGL_OK;
+    fp32_dev.epoch = 0;
+    const bool coef = m.bad_coef != INT_MAX;
+    int64_t row = m.bad_invd;
+    if (coef && fp32_dev.half) {
+        const int64_t per_chunk = (int64_t)sym_dev.nd * CHUNK_ROWS;
+        row = (m.bad_coef / per_chunk) * CHUNK_ROWS + m.bad_coef % CHUNK_ROWS;
+    } else if (coef) {
+        std::vector<int32_t> rp((size_t)pat.n_rows + 1);
+        OGL_HIP_CHECK(hipMemcpy(rp.data(), d_row_ptrs.p, rp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        row = (int64_t)(std::upper_bound(rp.begin(), rp.end(), m.bad_coef) - rp.begin()) - 1;
+    }
+    row = std::max<int64_t>(0, std::min<int64_t>(row, (int64_t)pat.n_rows - 1));
+    if (pat.renumbered() && (size_t)row < pat.old_of.size()) row = pat.old_of[(size_t)row];
+    return fail(OGL_ERR_INVALID, "mixedPrecision: %s of row %lld is finite in double precision and not in single precision",
+                coef ? "a coefficient" : "the inverse diagonal", (long long)row);
+}
+
+int ogl_solver::run_mixed(ogl_perf *perf)
+{
+    hipStream_t st = reg->stream;
+    const int n = pat.n_rows, nc = (int)n_chunks(n);
+    DevScalars *s = d_scal.p;
+    const bool is_final = cfg.rel_tol == 0.0;
+    // the criterion as configured: every outer check evaluates (frequency 1), the adaptive policy is not consulted
+    DevCriterion crit{};
+    crit.tolerance = cfg.tolerance;
+    crit.rel_tol = cfg.rel_tol;
+    crit.min_iter = cfg.min_iter;
+    crit.max_iter = cfg.max_iter;
+    crit.frequency = 1;
+    crit.export_res = cfg.export_res;
+    const int inner_max_iter = (int)std::min(prop("innerMaxIter", 1000.0), 2147483647.0);
+    OGL_TRY(mixed_storage(crit, prop("innerRelTol", 1e-4), inner_max_iter));
+    MixedScalars *m = mixed.scal.p;
+    const float *inv_d = nullptr;
+    if (precond) {  // inv_d32 = fl32 of the inverse diagonal the double path would use for this solve
+        launch_mixed_refresh(st, n, nullptr, precond, mixed.inv_d.p, word_of(m, offsetof(MixedScalars, bad_invd)));
+        inv_d = mixed.inv_d.p;
+    }
+    float *z = inv_d ? mixed.z.p : mixed.r.p;  // without a preconditioner z is the residual itself
+    // (sized by what the keywords allow, as the double path's block: the same one solve after solve)
+    OGL_TRY(d_history.alloc((size_t)std::max(std::max(crit.max_iter, crit.min_iter) + 2,
+                                             crit.max_iter + std::max(1, cfg.norm_eval_limit) + 1) + 4, st));
+    if (cfg.export_res) OGL_HIP_CHECK(hipMemsetAsync(d_history.p, 0, d_history.n * sizeof(double), st));
+    for (int i = 0; i < 2; ++i)
+        if (!chk_ev[i]) OGL_HIP_CHECK(ev_create(&chk_ev[i]));
+
+    // O0: the double path's prologue -- norm factor, r = b - A x on the in-loop layout, the partials of sum |r|
+    const double t_start = now_ms();
+    launch_reset_scalars(st, s, crit);
+    launch_partials_sum(st, n, d_x.p, d_part0.p);
+    FinArgs fa{};
+    fa.part[0] = d_part0.p;
+    fa.n_part = nc;
+    fa.n_sums = 1;
+    fa.n_local = fa.n_global = (double)n;
+    OGL_TRY(finalize(FIN_MEAN, fa));
+    launch_fill_xbar(st, n, d_w.p, s);
+    OGL_TRY(dist_spmv(SPMV_PLAIN, d_w.p, nullptr, d_q.p, SpmvDots{}, nullptr));
+    OGL_TRY(dist_spmv(SPMV_RESIDUAL, d_x.p, d_b.p, d_r.p, SpmvDots{}, nullptr));
+    launch_partials_normfactor(st, n, d_b.p, d_q.p, d_r.p, d_part0.p);
+    fa = FinArgs{};
+    fa.part[0] = d_part0.p;
+    fa.n_part = nc;
+    fa.n_sums = 1;
+    OGL_TRY(finalize(FIN_NORMFACTOR, fa));
+    launch_partials_norm1(st, n, d_r.p, d_part2.p);
+
+    auto poll_record = [&](int slot) -> int {
+        OGL_HIP_CHECK(hipMemcpyAsync(&mixed.h_scal[slot], m, sizeof(MixedScalars), hipMemcpyDeviceToHost, st));
+        OGL_HIP_CHECK(hipEventRecord(poll_ev[slot], st));
+        return OGL_OK;
+    };
+    // one inner turn, five launches: step 1 | SpMV (pi partials) | a | steps 4, 5 (rho, tau partials) | rho, tau, the gate
+    auto enqueue_turns = [&](int count) {
+        for (int i = 0; i < count; ++i) {
+            launch_mixed_step1(st, n, mixed.p.p, z, m);
+            mixed_spmv(mixed.p.p, mixed.q.p, d_part2.p, m);
+            launch_mixed_fin_pi(st, m, d_part2.p, nc);
+            launch_mixed_step2(st, n, mixed.u.p, mixed.r.p, mixed.p.p, mixed.q.p, inv_d, mixed.z.p, d_part0.p, d_part1.p, m);
+        }
+    };
+    const int batch = 16;
+    int turns = 0, enqueued = 0;  // inner turns so far (the device's total_turns); turns put into the stream
+    MixedScalars fin{};
+    for (int k = 0;; ++k) {
+        // O1, O2 (one launch), O3 + the start of the inner solve
+        if (k == 0) OGL_HIP_CHECK(hipEventRecord(chk_ev[0], st));
+        launch_mixed_head(st, m, s, d_part2.p, nc, d_history.p);
+        if (k == 0) OGL_HIP_CHECK(hipEventRecord(chk_ev[1], st));
+        launch_mixed_start(st, n, d_r.p, inv_d, mixed.r.p, z, mixed.u.p, d_part0.p, d_part1.p, m);
+        // O4: the device's budget of this step is min(innerMaxIter, maxIter - T); the host knows T exactly, so it never
+        // enqueues past it, and it looks at the flags of batch j only after batch j + 1 is in the queue
+        const int cap = std::max(0, std::min(inner_max_iter, crit.max_iter - turns));
+        int enq = 0;
+        auto next_batch = [&]() {
+            const int count = std::min(batch, cap - enq);
+            enqueue_turns(count);
+            enq += count;
+            enqueued += count;
+        };
+        next_batch();
+        OGL_TRY(poll_record(0));
+        MixedScalars seen{};
+        for (int j = 0;; ++j) {
+            const bool more = enq < cap;
+            if (more) {
+                next_batch();
+                OGL_TRY(poll_record((j + 1) & 1));
+            }
+            OGL_HIP_CHECK(hipEventSynchronize(poll_ev[j & 1]));
+            seen = mixed.h_scal[j & 1];
+            if (seen.outer_stop || seen.inner_stop) break;
+            if (!more) return fail(OGL_ERR_STATE, "mixedPrecision: the inner solve did not stop within its budget");
+        }
+        if (seen.outer_stop) {
+            fin = seen;
+            break;
+        }
+        turns += seen.inner_turns;
+        // O5, O6: x += S u, r = b - A x with the prologue's kernel, the partials of sum |r| for the next check
+        launch_mixed_add(st, n, d_x.p, mixed.u.p, m);
+        OGL_TRY(dist_spmv(SPMV_RESIDUAL, d_x.p, d_b.p, d_r.p, SpmvDots{}, s));
+        launch_partials_norm1(st, n, d_r.p, d_part2.p);
+    }
+    OGL_HIP_CHECK(hipStreamSynchronize(st));
+    OGL_HIP_CHECK(hipGetLastError());
+    if (fin.stop_reason == MIXED_STOP_INVALID) OGL_TRY(mixed_overflow(fin));
+    const double t_solve = now_ms() - t_start;
+    history.clear();
+    if (cfg.export_res) {  // entry j: the j-th evaluated check
+        history.resize((size_t)fin.n_evals);
+        OGL_HIP_CHECK(hipMemcpy(history.data(), d_history.p, history.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    float chk_ms = 0.f;
+    OGL_HIP_CHECK(hipEventElapsedTime(&chk_ms, chk_ev[0], chk_ev[1]));
+    props["mixedPrecisionInUse"] = 1.0;
+    props["mixedOuterSteps"] = (double)fin.outer_steps;
+    props["mixedInnerTurns"] = (double)fin.total_turns;
+    props["mixedStopReason"] = (double)fin.stop_reason;
+    props["turnsEnqueued"] = (double)enqueued;
+    perf->initial_residual = fin.init_res;
+    perf->final_residual = fin.res;
+    perf->n_iterations = fin.total_turns + 1;  // (maxIter keeps its meaning as a cap on turns)
+    perf->n_norm_evals = fin.n_evals;
+    perf->norm_factor = fin.norm_factor;
+    perf->t_solve_ms = t_solve;
+    perf->spmv_avg_ms = 0;
+    perf->spmv_launches = 0;
+    props[is_final ? "prevSolveIters_final" : "prevSolveIters"] = perf->n_iterations;
+    const double res_norm_time = std::max(1e-3, (double)chk_ms * 1e3);
+    perf->t_res_norm_us = res_norm_time;
+    perf->n_global_rows = (double)n;
+    props["_prev_solve"] = std::floor(t_solve * 1e3 / std::max(perf->n_iterations, 1) / res_norm_time);
+    return OGL_OK;
+}
+
+// y = A32 x through the inner SpMV of the layout in use, both vectors in the caller's order
+int ogl_solver::spmv_f32(const float *x, float *y)
+{
+    hipStream_t st = reg->stream;
+    const int n = pat.n_rows;
+    OGL_TRY(mixed_storage(DevCriterion{}, 1e-4, 1));
+    const size_t bytes = (size_t)n * sizeof(float);
+    if (pat.renumbered()) {
+        OGL_TRY(mixed.io.alloc((size_t)n + 4, st));
+        OGL_TRY(reg->stager.h2d(mixed.io.p, x, bytes, st));
+        launch_mixed_permute(st, n, d_new_id.p, mixed.io.p, mixed.p.p, /*gather=*/false);
+    } else {
+        OGL_TRY(reg->stager.h2d(mixed.p.p, x, bytes, st));
+    }
+    mixed_spmv(mixed.p.p, mixed.q.p, nullptr, nullptr);
+    // property mixedTimedSpmvs > 0 (measurements only): that many inner SpMVs with the pi partials, as a turn runs them,
+    // timed with HIP events -> mixedSpmvUs
+    if (const int timed = (int)prop("mixedTimedSpmvs", 0.0); timed > 0) {
+        EventPair ev;
+        OGL_HIP_CHECK(ev_create(&ev[0]));
+        OGL_HIP_CHECK(ev_create(&ev[1]));
+        OGL_HIP_CHECK(hipMemcpyAsync(mixed.r.p, mixed.p.p, bytes, hipMemcpyDeviceToDevice, st));
+        mixed_spmv(mixed.r.p, mixed.z.p, d_part2.p, nullptr);  // warm-up
+        OGL_HIP_CHECK(hipEventRecord(ev[0], st));
+        for (int i = 0; i < timed; ++i)  // (alternating inputs: no launch reads what the last one wrote)
+            mixed_spmv((i & 1) ? mixed.r.p : mixed.p.p, mixed.z.p, d_part2.p, nullptr);
+        OGL_HIP_CHECK(hipEventRecord(ev[1], st));
+        OGL_HIP_CHECK(hipEventSynchronize(ev[1]));
+        float ms = 0.f;
+        OGL_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        props["mixedSpmvUs"] = 1e3 * (double)ms / timed;
+    }
+    MixedScalars got;
+    OGL_HIP_CHECK(hipMemcpyAsync(&mixed.h_scal[0], mixed.scal.p, sizeof(MixedScalars), hipMemcpyDeviceToHost, st));
+    if (pat.renumbered()) {
+        launch_mixed_permute(st, n, d_new_id.p, mixed.q.p, mixed.io.p, /*gather=*/true);
+        OGL_TRY(reg->stager.d2h(y, mixed.io.p, bytes, st));
+    } else {
+        OGL_TRY(reg->stager.d2h(y, mixed.q.p, bytes, st));
+    }
+    OGL_HIP_CHECK(hipStreamSynchronize(st));
+    OGL_HIP_CHECK(hipGetLastError());
+    got = mixed.h_scal[0];
+    return mixed_overflow(got);
+}

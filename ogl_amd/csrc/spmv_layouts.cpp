@@ -444,4 +444,29 @@ void Stream21Dev::view(DevCsr &A) const
     A.far_col21 = far_col.p;
 }
 
+// ---- fp32 copy for the mixed-precision mode ----
+int Fp32Dev::ensure(bool half_storage, uint64_t pattern, size_t count, hipStream_t st)
+{
+    DevBuf<float> &b = half_storage ? planes : vals;
+    if (half != half_storage || pat_id != pattern || b.n != count) epoch = 0;
+    half = half_storage;
+    pat_id = pattern;
+    (half_storage ? vals : planes).release();
+    return b.alloc(count, st);
+}
+
+void Fp32Dev::refresh(const int32_t *map, const double *csr_vals, int32_t *bad, hipStream_t st)
+{
+    DevBuf<float> &b = half ? planes : vals;
+    // (the planes carry two slots of padding behind the map's last entry, as SymDev::refresh knows)
+    launch_mixed_refresh(st, half ? (int64_t)b.n - 2 : (int64_t)b.n, map, csr_vals, b.p, bad);
+}
+
+void Fp32Dev::release()
+{
+    planes.release();
+    vals.release();
+    epoch = 0;
+}
+
 }  // namespace ogl

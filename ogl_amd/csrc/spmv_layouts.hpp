@@ -124,4 +124,21 @@ struct Stream21Dev {
     void view(DevCsr &A) const;  // the packed-column fields of the CSR-stream view
 };
 
+// The fp32 copy of the matrix that the inner solve of the mixed-precision mode runs on: an fp32
+// twin of the half storage's planes when that is the in-loop layout -- it shares SymDev's mask, map and order -- and an
+// fp32 value array beside the device CSR (sharing its row pointers and columns) for every other in-loop layout.
+// Allocated at the first mixed solve and kept; refreshed from the CSR values under the values epoch by one kernel that
+// also reports the first value that overflows binary32.
+struct Fp32Dev {
+    DevBuf<float> planes, vals;
+    bool half = false;     // which of the two is in use
+    uint64_t pat_id = 0;   // the pattern the buffers were sized for
+    uint64_t epoch = 0;    // 0: stale
+    int ensure(bool half_storage, uint64_t pattern, size_t count, hipStream_t st);
+    // map: SymDev::map (half storage) or nullptr (CSR values); bad: device word that receives the overflowing position
+    void refresh(const int32_t *map, const double *csr_vals, int32_t *bad, hipStream_t st);
+    const float *values() const { return half ? planes.p : vals.p; }
+    void release();
+};
+
 }  // namespace ogl
