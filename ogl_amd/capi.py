@@ -22,6 +22,8 @@ PRECOND_MULTIGRID = 7
 # keywords of the Multigrid sub-dictionary (Preconditioner.H:297-317): they travel as properties; cycle as a number
 MG_KEYWORDS = ("maxLevels", "minCoarseRows", "coarseSolverIters", "cycle", "zeroGuess")
 MG_CYCLE = {"v": 0, "w": 1, "f": 2}
+# keyword orthoMethod of GKOGMRES: it travels as a property, as a number
+ORTHO_METHOD = {"mgs": 0, "cgs": 1, "cgs2": 2}
 FORMAT_COO, FORMAT_CSR, FORMAT_ELL = 0, 1, 2
 RENUMBER_OFF, RENUMBER_ON, RENUMBER_AUTO = 0, 1, 2
 IFACE_PROCESSOR, IFACE_CYCLIC = 0, 1
@@ -376,6 +378,11 @@ class Solver:
             self.set_property("innerRelTol", float(inner_rel_tol))
         if inner_max_iter is not None:
             self.set_property("innerMaxIter", float(inner_max_iter))
+        return self
+
+    def set_ortho_method(self, word):
+        """The keyword orthoMethod ('mgs' | 'cgs' | 'cgs2': GKOGMRES' Gram-Schmidt step) for the next solves."""
+        self.set_property("orthoMethod", float(ORTHO_METHOD[word]))
         return self
 
     def apply_preconditioner(self, r):

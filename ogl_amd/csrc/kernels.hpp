@@ -560,6 +560,17 @@ void launch_gmres_scale(hipStream_t st, int32_t n, double *out, const double *in
 void launch_gmres_mgs(hipStream_t st, int32_t n, double *w, const double *vprev,
                       const double *hprev, const double *vdot, double *part,
                       const DevScalars *gate);
+// classical Gram-Schmidt in block form (kernels_gmres.hip; orthoMethod cgs | cgs2).  V: the basis,
+// vector j at V + j * ld; k = it + 1 vectors take part; a partial array holds row j at part + j * n_chunks(n).
+// multidot: the partials of w . V_j, j < k.  fin_h (one workgroup per j, k_finalize's tree): h[j] = sum of row j, and
+// h_col[j] = h[j] (add: h_col[j] + h[j]).  block_update: w -= sum_j h[j] V_j, j ascending; then the partials of w . w into
+// part_norm, or (part_dots != nullptr) those of w . V_j on the new w into part_dots.
+void launch_gmres_multidot(hipStream_t st, int32_t n, const double *w, const double *V, int64_t ld, int32_t k, double *part,
+                           const DevScalars *gate);
+void launch_gmres_fin_h(hipStream_t st, int32_t n, const DevScalars *gate, const double *part, int32_t k, double *h,
+                        double *h_col, bool add);
+void launch_gmres_block_update(hipStream_t st, int32_t n, double *w, const double *V, int64_t ld, int32_t k, const double *h,
+                               double *part_norm, double *part_dots, const DevScalars *gate);
 // t_i = sum_{j < it} V_j[i] * y[j] ; with `before` != nullptr the sum is stored there, otherwise
 // x_i += t_i * inv_diag_i (inv_diag == nullptr: x_i += t_i)
 void launch_gmres_update_x(hipStream_t st, int32_t n, const double *V, int64_t ld, const double *y,

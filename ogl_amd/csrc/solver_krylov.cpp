@@ -193,6 +193,7 @@ struct ogl_solver::KrylovRun {
     // turn shapes (see plan)
     bool fused = false, fused2 = false, merged = false, merged_halo = false, bicg_fold = false, gmres_fold = false;
     int m = 0;        // Krylov dimension of GKOGMRES
+    int ortho = 0;    // GKOGMRES: 0 modified Gram-Schmidt, 1 | 2 classical Gram-Schmidt in block form, one | two rounds
     int64_t ldv = 0;  // leading dimension of the Krylov bases
     double n_global = 0.0;
     size_t n_halo = 0;
@@ -236,6 +237,24 @@ struct ogl_solver::KrylovRun {
 
 int ogl_solver::run_cg(ogl_perf *perf) { return run_krylov(perf); }
 int ogl_solver::run_bicgstab(ogl_perf *perf) { return run_krylov(perf); }
+
+// Property orthoMethod: how GKOGMRES orthogonalises the new Krylov vector.  GKOCG and GKOBiCGStab
+// have no such step and ignore the keyword.  The block form takes all sums of a round through one finaliser launch of its
+// own, which has no all-reduce: with several ranks it is refused, not run on modified Gram-Schmidt in silence.
+int ogl_solver::ortho_requested(int *method)
+{
+    *method = 0;
+    if (cfg.solver != OGL_SOLVER_GMRES) return OGL_OK;
+    const double v = prop("orthoMethod", 0.0);
+    if (v != 0.0 && v != 1.0 && v != 2.0)
+        return fail(OGL_ERR_INVALID, "orthoMethod %g is none of 0 (mgs), 1 (cgs), 2 (cgs2)", v);
+    const int n_ranks = reg->comm ? reg->comm->n_ranks : 1;
+    if (v != 0.0 && n_ranks > 1)
+        return fail(OGL_ERR_UNSUPPORTED, "orthoMethod %s runs GKOGMRES on one rank: this registry has %d ranks",
+                    v == 1.0 ? "cgs" : "cgs2", n_ranks);
+    *method = (int)v;
+    return OGL_OK;
+}
 
 int ogl_solver::run_krylov(ogl_perf *perf)
 {
@@ -291,7 +310,15 @@ int ogl_solver::krylov_plan(KrylovRun &k)
     // link's kernel (k_gmres_mgs_fold: one launch per link instead of two)
     // (larger systems: with the leader finalisation on request only, property gmresLead -- a Gram-Schmidt link moves 16 N
     //  bytes, and the wait for the leaders costs it what the finaliser launch did: 216^3 GMRES(30) 1068 against 1047 us per turn)
-    k.gmres_fold = gmres && (small || (lead_any && prop("gmresLead", 0.0) != 0.0)) && prop("gmresFold", 1.0) != 0.0;
+    OGL_TRY(ortho_requested(&k.ortho));  // (the block forms of Gram-Schmidt have no links to fold a finaliser into)
+    props["orthoMethodInUse"] = (double)k.ortho;
+    k.gmres_fold = gmres && !k.ortho && (small || (lead_any && prop("gmresLead", 0.0) != 0.0)) && prop("gmresFold", 1.0) != 0.0;
+    // launches of a single-rank turn, averaged over a full cycle: the SpMV's one, the scaling's one and the Gram-Schmidt step
+    // with the column's finaliser -- it + 3 folded links or 2 it + 4 launches at column `it`, 4 | 6 in block form (the
+    // preconditioner's own launches, where it has any, are not counted)
+    if (gmres)
+        props["gmresLaunchesPerTurn"] =
+            2.0 + (k.ortho ? 2.0 + 2.0 * k.ortho : k.gmres_fold ? 0.5 * (k.m - 1) + 3.0 : (double)(k.m - 1) + 4.0);
     k.slot_s[0] = s;
     k.slot_s[1] = k.s2;
     props["fusedFinalizersInUse"] = ((fused || k.bicg_fold || k.gmres_fold) && small) ? 1.0 : 0.0;
@@ -421,6 +448,10 @@ int ogl_solver::krylov_prepare(KrylovRun &k)
         OGL_TRY(d_gm.alloc(gmres_state_len(m), st));
         OGL_HIP_CHECK(hipMemsetAsync(d_gm.p, 0, gmres_state_len(m) * sizeof(double), st));
         if (generic) OGL_TRY(d_z.alloc((size_t)n + 2, st));
+        if (k.ortho) {
+            OGL_TRY(d_gs_part.alloc((size_t)(m + 1) * (size_t)nc, st));
+            OGL_TRY(d_gs_h.alloc((size_t)m + 1, st));
+        }
     } else if (generic) {
         OGL_TRY(d_z.alloc((size_t)n + 2, st));
     }
@@ -591,7 +622,22 @@ int ogl_solver::turn_gmres(KrylovRun &k, int enq, int pe)
     // finish_arnoldi (modified Gram-Schmidt): H(k,it) = nx.V_k ; nx -= H(k,it) V_k
     fg.turn = it;
     fg.n_sums = 1;
-    if (k.gmres_fold) {
+    if (k.ortho) {
+        // classical Gram-Schmidt in block form: every dot product of a round in one pass over the basis, every correction
+        // in a second one; cgs2 runs a second round on the updated vector, whose dot products come out of the first
+        // round's update pass, and H(j, it) is the sum of the two coefficients
+        const int nv = it + 1;
+        launch_gmres_multidot(st, n, nx, d_V.p, ldv, nv, d_gs_part.p, s);
+        launch_gmres_fin_h(st, n, s, d_gs_part.p, nv, d_gs_h.p, k.gm_h(0, it), false);
+        if (k.ortho == 2) {
+            launch_gmres_block_update(st, n, nx, d_V.p, ldv, nv, d_gs_h.p, nullptr, d_gs_part.p, s);
+            launch_gmres_fin_h(st, n, s, d_gs_part.p, nv, d_gs_h.p, k.gm_h(0, it), true);
+        }
+        launch_gmres_block_update(st, n, nx, d_V.p, ldv, nv, d_gs_h.p, d_part0.p, nullptr, s);
+        fg.check_after = 1;
+        OGL_TRY(finalize(FIN_GMRES_COL, fg));  // ||nx||, Givens, residual-norm recurrence, the next turn's check
+        fg.check_after = 0;
+    } else if (k.gmres_fold) {
         double *pin = d_part1.p, *pout = d_part0.p;  // (a link reads the partials of the one before it)
         for (int j = 0; j <= it; ++j) {
             launch_gmres_mgs_fold(st, n, nx, j > 0 ? d_V.p + (size_t)(j - 1) * ldv : nullptr,
@@ -619,6 +665,43 @@ int ogl_solver::turn_gmres(KrylovRun &k, int enq, int pe)
         fg.check_after = 0;
     }
     if (!k.gmres_scale_late()) launch_gmres_scale(st, n, nx, nx, k.beta_ptr, s);
+    return OGL_OK;
+}
+
+// Property orthoTimedLaunches > 0 (measurements only; after a solve on orthoMethod cgs | cgs2, on its buffers): that many
+// launches of every kernel of the block form at columns it = 0, 15 and 29 (as far as krylovDim goes), timed with HIP
+// events -> orthoMultidotUs_<it>, orthoFinHUs_<it>, orthoUpdateUs_<it> (with the w . w partials), orthoUpdateDotsUs_<it>
+// (with cgs2's second-round partials).  The coefficients are zeroed first: the update leaves the basis as it is.
+int ogl_solver::time_ortho_kernels(KrylovRun &k)
+{
+    const int timed = (int)prop("orthoTimedLaunches", 0.0);
+    if (timed <= 0 || !k.ortho) return OGL_OK;
+    hipStream_t st = k.st;
+    EventPair ev;
+    OGL_HIP_CHECK(ev_create(&ev[0]));
+    OGL_HIP_CHECK(ev_create(&ev[1]));
+    OGL_HIP_CHECK(hipMemsetAsync(d_gs_h.p, 0, d_gs_h.n * sizeof(double), st));
+    for (const int it : {0, 15, 29}) {
+        if (it >= k.m) break;
+        const int nv = it + 1;
+        double *w = d_V.p + (size_t)nv * k.ldv, *col = k.gm_h(0, it);
+        const char *names[4] = {"orthoMultidotUs_", "orthoFinHUs_", "orthoUpdateUs_", "orthoUpdateDotsUs_"};
+        for (int which = 0; which < 4; ++which) {
+            for (int i = -1; i < timed; ++i) {  // (i == -1: warm-up)
+                if (i == 0) OGL_HIP_CHECK(hipEventRecord(ev[0], st));
+                if (which == 0) launch_gmres_multidot(st, k.n, w, d_V.p, k.ldv, nv, d_gs_part.p, nullptr);
+                if (which == 1) launch_gmres_fin_h(st, k.n, nullptr, d_gs_part.p, nv, d_gs_h.p, col, false);
+                if (which == 2) launch_gmres_block_update(st, k.n, w, d_V.p, k.ldv, nv, d_gs_h.p, d_part0.p, nullptr, nullptr);
+                if (which == 3) launch_gmres_block_update(st, k.n, w, d_V.p, k.ldv, nv, d_gs_h.p, nullptr, d_gs_part.p, nullptr);
+            }
+            OGL_HIP_CHECK(hipEventRecord(ev[1], st));
+            if (which == 1) OGL_HIP_CHECK(hipMemsetAsync(d_gs_h.p, 0, d_gs_h.n * sizeof(double), st));
+            OGL_HIP_CHECK(hipEventSynchronize(ev[1]));
+            float ms = 0.f;
+            OGL_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            props[names[which] + std::to_string(it)] = 1e3 * (double)ms / timed;
+        }
+    }
     return OGL_OK;
 }
 
@@ -1121,6 +1204,7 @@ int ogl_solver::krylov_finish(KrylovRun &k, ogl_perf *perf)
         OGL_HIP_CHECK(hipGetLastError());
     }
     const double t_solve = now_ms() - k.t_start;
+    OGL_TRY(time_ortho_kernels(k));
     history.clear();
     if (cfg.export_res) {
         history.resize(fin.iter);
@@ -1190,6 +1274,8 @@ int ogl_solver::apply_resident(ogl_perf *perf)
     TraceRange trace("solve", field);
     bool mixed_on = false;  // (refused before anything is generated for it)
     OGL_TRY(mixed_requested(&mixed_on));
+    int ortho = 0;
+    OGL_TRY(ortho_requested(&ortho));
     {
         TraceRange trace_pc("init_preconditioner", field);
         OGL_TRY(init_preconditioner());
