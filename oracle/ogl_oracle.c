@@ -1021,6 +1021,10 @@ void orc_csr_transpose(orc_label n, const orc_label *rowptr, const orc_label *co
 }
 
 void orc_precond_apply(orc_label n, const orc_precond *P, const orc_scalar *r, orc_scalar *z) {
+    if (P && P->kind == ORC_PRECOND_CALLBACK) {
+        P->apply(P->user, r, z, n);
+        return;
+    }
     if (P && P->kind == ORC_PRECOND_ISAI_GENERAL) {
         orc_spmv(n, P->w_rowptr, P->w_cols, P->w_vals, r, z);
         return;
@@ -1056,7 +1060,7 @@ void orc_precond_apply(orc_label n, const orc_precond *P, const orc_scalar *r, o
 orc_label orc_cg(const orc_dist_matrix *A, const orc_scalar *b, orc_scalar *x,
                  const orc_scalar *inv_diag, const orc_criterion *crit,
                  orc_criterion_state *st) {
-    orc_precond P = {inv_diag ? ORC_PRECOND_SCALAR : ORC_PRECOND_NONE, inv_diag, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    orc_precond P = {inv_diag ? ORC_PRECOND_SCALAR : ORC_PRECOND_NONE, inv_diag, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     return orc_cg_p(A, b, x, &P, crit, st);
 }
 
@@ -1107,7 +1111,7 @@ orc_label orc_cg_p(const orc_dist_matrix *A, const orc_scalar *b, orc_scalar *x,
 orc_label orc_bicgstab(const orc_dist_matrix *A, const orc_scalar *b, orc_scalar *x,
                        const orc_scalar *inv_diag, const orc_criterion *crit,
                        orc_criterion_state *st) {
-    orc_precond P = {inv_diag ? ORC_PRECOND_SCALAR : ORC_PRECOND_NONE, inv_diag, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    orc_precond P = {inv_diag ? ORC_PRECOND_SCALAR : ORC_PRECOND_NONE, inv_diag, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     return orc_bicgstab_p(A, b, x, &P, crit, st);
 }
 

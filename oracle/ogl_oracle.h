@@ -239,7 +239,8 @@ void orc_jacobi_generate_blocks(orc_label n, const orc_label *rowptr, const orc_
                                 const orc_label *block_ptrs, orc_label stride, orc_scalar *blocks);
 
 enum { ORC_PRECOND_NONE = 0, ORC_PRECOND_SCALAR = 1, ORC_PRECOND_BLOCK = 2,
-       ORC_PRECOND_ISAI_SPD = 3, ORC_PRECOND_ISAI_GENERAL = 4 };
+       ORC_PRECOND_ISAI_SPD = 3, ORC_PRECOND_ISAI_GENERAL = 4, ORC_PRECOND_CALLBACK = 5 };
+typedef void (*orc_precond_fn)(void *user, const orc_scalar *r, orc_scalar *z, orc_label n);
 typedef struct {
     int kind;
     const orc_scalar *inv_diag;   /* SCALAR */
@@ -256,6 +257,11 @@ typedef struct {
      * blocks are those of the caller's numbering (Preconditioner.H:91-105 generates on the matrix OpenFOAM hands
      * over); block_rows[r0 + i] = row of the block's i-th member in the system at hand.  NULL: r0 + i itself. */
     const orc_label *block_rows;
+    /* CALLBACK: z = M^-1 r is whatever apply(user, r, z, n) writes -- a preconditioner the C loops cannot apply
+     * themselves (the tests' NumPy references of IC / ILU / IRILU / Multigrid).  Last, so that the positional
+     * initialisers of the kinds above stay valid. */
+    orc_precond_fn apply;
+    void *user;
 } orc_precond;
 
 /* ISAI with sparsityPower 1 ([UPSTREAM] gko::preconditioner::Isai).  spd != 0: W has the pattern

@@ -368,11 +368,15 @@ def jacobi_generate_scalar(rowptr, cols, vals):
     return out
 
 
+PRECOND_FN = C.CFUNCTYPE(None, C.c_void_p, _SP, _SP, C.c_int32)
+
+
 class _CPrecond(C.Structure):
     _fields_ = [("kind", C.c_int), ("inv_diag", _SP), ("n_blocks", C.c_int32),
                 ("block_ptrs", _LP), ("blocks", _SP), ("stride", C.c_int32),
                 ("w_rowptr", _LP), ("w_cols", _LP), ("w_vals", _SP),
-                ("wt_rowptr", _LP), ("wt_cols", _LP), ("wt_vals", _SP), ("block_rows", _LP)]
+                ("wt_rowptr", _LP), ("wt_cols", _LP), ("wt_vals", _SP), ("block_rows", _LP),
+                ("apply", PRECOND_FN), ("user", C.c_void_p)]
 
 
 class Precond:
@@ -451,6 +455,22 @@ class Precond:
         z = np.zeros_like(r)
         lib().orc_precond_apply(C.c_int32(r.size), C.byref(self.c), pr, z.ctypes.data_as(_SP))
         return z
+
+
+class CallbackPrecond(Precond):
+    """ORC_PRECOND_CALLBACK: z = fn(r), a Python callable taking and returning one float64 entry per row, as the
+    preconditioner of the oracle's loops (cg / bicgstab / gmres take it wherever they take a Precond)."""
+
+    def __init__(self, fn):
+        self.fn = fn
+
+        def _apply(_user, r, z, n):
+            out = np.ctypeslib.as_array(z, shape=(max(1, n),))[:n]
+            out[:] = np.nan                     # (an exception cannot cross the C loop: it would leave NaN behind, not stale z)
+            out[:] = self.fn(np.ctypeslib.as_array(r, shape=(max(1, n),))[:n].copy())
+
+        self._cb = PRECOND_FN(_apply)           # the C side holds a bare pointer: keep the thunk alive here
+        self.c = _CPrecond(5, None, 0, None, None, 0, None, None, None, None, None, None, None, self._cb, None)
 
 
 class DistMatrix:

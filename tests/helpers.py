@@ -23,16 +23,24 @@ def oracle_matrix(oracle, case, **kw):
 
 
 class blocked:
-    """Run the oracle's reductions in the device's fixed tree (bit-exact comparisons)."""
+    """Run the oracle's reductions in the device's fixed tree (bit-exact comparisons).  Blocks nest: an inner block
+    (a reference that enters one itself, called back from inside a solve under an outer one) sets its own chunk size
+    and hands the outer block's mode back when it exits; only the outermost exit returns to the sequential sum."""
+    _stack = []
 
     def __init__(self, oracle, chunk_rows):
         self.oracle, self.chunk_rows = oracle, chunk_rows
 
     def __enter__(self):
+        blocked._stack.append(self.chunk_rows)
         self.oracle.set_reduction(self.oracle.REDUCE_BLOCKED, self.chunk_rows)
 
     def __exit__(self, *a):
-        self.oracle.set_reduction(self.oracle.REDUCE_SEQUENTIAL)
+        blocked._stack.pop()
+        if blocked._stack:
+            self.oracle.set_reduction(self.oracle.REDUCE_BLOCKED, blocked._stack[-1])
+        else:
+            self.oracle.set_reduction(self.oracle.REDUCE_SEQUENTIAL)
 
 
 def rel_dev(a, b):
