@@ -494,7 +494,23 @@ void launch_cg_step2r1x(hipStream_t st, int32_t n, double *r, const double *q, c
 struct HeldQ {
     int32_t on = 0;     // 1: the turns without an event pair run the one-launch kernel
     int32_t n_pos = 0;  // positions of the launch order (DevSym::n_blocks, or xcd_grid(chunks) without a band order)
+    // Phase S draws (property heldQStaticSlots): slot i < static_slots of workgroup w holds position w + i grid, the
+    // positions from static_slots * grid on form eight queues (position p: queue p % 8) that the first `drawers`
+    // workgroups draw from, workgroup w from queue w % 8.  static_slots == HQ_STATIC: every slot static, no counter
+    // touched.  heads: 2 sets of 8 counters, one 128-byte line each; launch j draws from set `parity` and zeroes the
+    // other -- parity counts the held-q LAUNCHES of the solve (turn_cg_held_q).
+    int32_t static_slots = 0;
+    int32_t drawers = 0;
+    unsigned *heads = nullptr;
+    int32_t parity = 0;
 };
+// The held-q kernel's own register slots: HQ_R + HZ_L = 22 slots per workgroup at the occupancy and LDS of 11 + 9.  The
+// two slots more are headroom for the draw to balance with, not capacity: the gates stay at grid * HQ_STATIC positions.
+constexpr int HQ_R = 13, HQ_STATIC = HZ_R + HZ_L;
+// heldQStaticSlots where the property is not set.  Measured at 216^3 (profiles/r14_held_q_draw.txt): 4 .. 14 run level,
+// 2.4 % above the static map; 16, 0 and 18 gain less or nothing
+constexpr int HQ_STATIC_DEFAULT = 12;
+constexpr int HQ_HEAD_STRIDE = 32, HQ_HEAD_WORDS = 2 * N_XCD * HQ_HEAD_STRIDE;  // (unsigned words: 128 bytes per counter)
 int held_q_positions(const DevSym &A);
 // occupancy (workgroups per CU) and static LDS bytes of the held-q instantiations: the minimum / the maximum over them
 int held_q_occupancy(int *per_cu, size_t *lds_bytes);

@@ -466,7 +466,8 @@ __global__ __launch_bounds__(BLOCK) void k_cg_turn_sym_big(int n_rows, int n_chu
 //   holes, or xcd_chunk): with G a multiple of 8 a chunk's far neighbours sit on its own XCD, as in the stand-alone SpMV.
 //   Any other G computes the same bits but sends them to other L2s; the host turns the kernel on by default only where
 //   G % 8 == 0 (plan_held_z).
-//   The same map in all three phases; holes and positions past the end own nothing.
+//   The same map in all three phases; holes and positions past the end own nothing.  That is the STATIC map; by default
+//   only a workgroup's first slots follow it and the others are drawn (below, at HeldQSrc), from HQ_R + L = 22 slots.
 //   phase S: sym_rows on p; the chunk's partial of p.q goes out as a tagged word (6 words per chunk: beta | rho | sum|r'|),
 //     tag `seq`.  Sixteen workgroups poll those partials in the finaliser's order (lead_wave_sums_tagged: the bits of
 //     lead_leaders<1> over the stand-alone SpMV's partials) and publish where the body's first wait looks.
@@ -474,22 +475,52 @@ __global__ __launch_bounds__(BLOCK) void k_cg_turn_sym_big(int n_rows, int n_chu
 //     only after every workgroup has finished S, and nobody passes the first wait before.
 // A stopped solve returns before any poll; every spin is bounded by lead.timeout_ticks and ends the solve with comm_error.
 // ------------------------------------------------------------------------------------------
+// The draw (HeldQ, kernels.hpp; S = static_slots < HQ_STATIC): a static map cannot level workgroups whose rates differ, so
+// only slot i < S of workgroup w holds position w + i G; the positions from S G on form eight queues -- position p is in
+// queue p % 8, in launch order -- and workgroup w < drawers takes the next of queue w % 8 for each further slot: one
+// returning atomic add of thread 0 on the queue's head, asked for one slot AHEAD, in front of the loads of the slot at
+// work, and read by the workgroup behind the barrier block_sum has anyway (a draw costs a trip to memory: it must not
+// stand in front of a slot's loads).  w % 8 is the XCD the workgroup runs on -- the assumption xcd_chunk makes, for speed
+// only.  A drawn slot's position stays in LDS (drawn[]): the same map in all three phases.
+//   Every position is computed, by exactly one workgroup: a ticket below the queue's length belongs to whoever drew it,
+//   and a workgroup asks only while it has a free slot, so it computes what it draws.  A workgroup stops asking when its
+//   R + L slots are full or its ticket is past the queue's end.  If one of the queue's workgroups stopped for the second
+//   reason, every ticket below the length was drawn before; if all of them stopped for the first, they drew
+//   drawers_of_the_queue * (R + L - S) tickets, and the host admits the draw only where that is >= the queue's length
+//   (plan_held_z; else the static map runs).  Nobody waits for anybody's draw: phase S ends as it did.
+//   The heads: two sets of eight, picked by the parity of the solve's held-q launches.  Workgroup 0 zeroes the OTHER set,
+//   whose last users left at the kernel boundary before this launch and whose next come after this launch's end.  Zeroing
+//   the set in use inside the launch that uses it would be wrong at any point: a workgroup that owns nothing polls for
+//   nothing it must wait for and may still draw after workgroup 0 has passed both waits.
 // the held-q turn's slots: positions of the SpMV's launch order with their holes; q of a chunk is in its slot; 6 tagged
 // words per chunk (beta | rho | sum|r'|)
+// DRAW false: the static map alone, and nothing of the draw in the code
+template <bool DRAW>
 struct HeldQSrc {
     static constexpr bool Q_HELD = true;
     static constexpr int STRIDE = 6, WORD = 2;
     int G, n_pos, n_partials;
     const int *__restrict__ block_order;
-    __device__ __forceinline__ int chunk_of(int i) const  // -1: a hole of the order or a position past its end
+    int S;             // slots below S are static
+    const int *drawn;  // LDS: the position of slot i >= S, -1 where it drew none
+    __device__ __forceinline__ int chunk_at(int pos) const  // -1: a hole of the order, a position past its end, none
     {
-        const int pos = blockIdx.x + i * G;
-        if (pos >= n_pos) return -1;
+        if (pos < 0 || pos >= n_pos) return -1;
         const int c = block_order ? block_order[pos] : xcd_chunk(pos);
         return c < n_partials ? c : -1;
     }
+    __device__ __forceinline__ int chunk_of(int i) const
+    {
+        if constexpr (!DRAW) return chunk_at((int)blockIdx.x + i * G);
+        return chunk_at(i < S ? (int)blockIdx.x + i * G : __builtin_amdgcn_readfirstlane(drawn[i]));
+    }
+    __device__ __forceinline__ int chunk_of_rolled(int i) const  // (resident_cg_turn.hpp, turn_chunk_rolled)
+    {
+        if constexpr (!DRAW) return chunk_at((int)blockIdx.x + i * G);
+        return chunk_at(i < S ? (int)blockIdx.x + i * G : drawn[i]);
+    }
 };
-template <int R, int L, int B, int K, int ND, bool FAST>
+template <int R, int L, int B, int K, int ND, bool FAST, bool DRAW>
 __global__ __launch_bounds__(BLOCK, B) void k_cg_turn_held_q(int n, int n_chunks, int n_pos, SymOffsets off,
                                                              const uint8_t *__restrict__ mask,
                                                              const double *__restrict__ planes,
@@ -497,22 +528,51 @@ __global__ __launch_bounds__(BLOCK, B) void k_cg_turn_held_q(int n, int n_chunks
                                                              const double *__restrict__ inv_diag, double *p, double *p_out,
                                                              double *__restrict__ x, DevScalars *s,
                                                              unsigned long long *tagged, double *history, LeadBox lead,
-                                                             const double *p_pend, int ring_phase, int early_slots)
+                                                             const double *p_pend, int ring_phase, int early_slots,
+                                                             int static_slots, int drawers, unsigned *heads, int parity)
 {
     __shared__ double zl[L > 0 ? L * CHUNK_ROWS : 1];
     __shared__ TurnLds lds;
+    __shared__ int drawn[DRAW ? R + L : 1];
+    using Src = HeldQSrc<DRAW>;
     const TurnScalars ts = turn_prelude<K>(s, ring_phase);
     const TurnArgs a{n, r, inv_diag, p, p_out, x, s, tagged, history, lead, p_pend, early_slots};
-    const HeldQSrc src{(int)gridDim.x, n_pos, n_chunks, block_order};
     const int G = gridDim.x, w = blockIdx.x;
+    const int S = DRAW ? static_slots : R + L;
+    const Src src{G, n_pos, n_chunks, block_order, S, drawn};
     if (ts.stopped) return;  // (every workgroup sees the same flag: nobody polls, nobody writes)
+    unsigned *const head = heads + (size_t)(parity * N_XCD + w % N_XCD) * HQ_HEAD_STRIDE;
+    const int q0 = S * G + ((w % N_XCD) - (S * G) % N_XCD + N_XCD) % N_XCD;  // the queue's first position
+    auto ask = [&]() { return __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto position = [&](unsigned ticket) {
+        const long long pos = q0 + (long long)N_XCD * ticket;
+        return pos < n_pos ? (int)pos : -1;
+    };
+    bool more = DRAW && w < drawers;  // (workgroup-uniform) the queue has not ended for this workgroup
+    if constexpr (DRAW) {
+        if (threadIdx.x < R + L) drawn[threadIdx.x] = -1;
+        if (w == 0 && threadIdx.x < N_XCD) heads[(size_t)((parity ^ 1) * N_XCD + threadIdx.x) * HQ_HEAD_STRIDE] = 0u;
+        if (more && S == 0 && threadIdx.x == 0) drawn[0] = position(ask());  // (the one draw nothing can hide)
+        __syncthreads();
+        if (more && S == 0) more = __builtin_amdgcn_readfirstlane(drawn[0]) >= 0;
+    }
     // phase S: q = A p of every slot's chunk, kept; the partials of p.q
     TurnSlots<R, L> z;
     z.zl = zl;
 #pragma unroll
     for (int i = 0; i < R + L; ++i) {
+        const bool ahead = DRAW && more && i + 1 >= S && i + 1 < R + L;  // (workgroup-uniform) slot i + 1 draws
+        unsigned ticket = 0;
+        if (ahead && threadIdx.x == 0) ticket = ask();
         const int chunk = src.chunk_of(i);
-        if (chunk < 0) continue;  // (workgroup-uniform; no break: the loop must unroll, see TurnSlots)
+        if (chunk < 0) {  // (workgroup-uniform; no break: the loop must unroll, see TurnSlots)
+            if (ahead) {  // (a hole of the order: no block_sum to stand behind)
+                if (threadIdx.x == 0) drawn[i + 1] = position(ticket);
+                __syncthreads();
+                more = __builtin_amdgcn_readfirstlane(drawn[i + 1]) >= 0;
+            }
+            continue;
+        }
         const RowPair rp = my_rows(chunk, n);
         double2 xd;
         double2 vq = sym_rows<SPMV_PLAIN, ND, FAST, true>(chunk, rp, n, off, mask, planes, p, nullptr, xd);
@@ -522,14 +582,16 @@ __global__ __launch_bounds__(BLOCK, B) void k_cg_turn_held_q(int n, int n_chunks
         double d = 0.0;
         if (rp.n > 0) d += xd.x * vq.x;
         if (rp.n > 1) d += xd.y * vq.y;
+        if (ahead && threadIdx.x == 0) drawn[i + 1] = position(ticket);
         const double sd = block_sum(d, lds.slot);
-        if (threadIdx.x == 0) put_tagged(tagged + HeldQSrc::STRIDE * (size_t)chunk, ts.seq, sd);
+        if (ahead) more = __builtin_amdgcn_readfirstlane(drawn[i + 1]) >= 0;
+        if (threadIdx.x == 0) put_tagged(tagged + Src::STRIDE * (size_t)chunk, ts.seq, sd);
     }
     // beta: sixteen workgroups -- behind the 2 x 16 of the later sums where the grid has them -- are the finaliser's wavefronts
     const int lead0 = G >= 3 * FIN_WAVES ? 2 * FIN_WAVES : 0;
     if (w >= lead0 && w < lead0 + FIN_WAVES)
-        lead_wave_sums_tagged(lead, ts.seq, tagged, HeldQSrc::STRIDE, n_chunks, w - lead0, 0);
-    TurnFront<HeldQSrc::Q_HELD> f;
+        lead_wave_sums_tagged(lead, ts.seq, tagged, Src::STRIDE, n_chunks, w - lead0, 0);
+    TurnFront<Src::Q_HELD> f;
     turn_ask_first(src, a, f);
     double beta;
     if (!turn_await_beta(a, ts, lds, beta)) return;
@@ -667,7 +729,8 @@ void launch_cg_turn_sym_big(hipStream_t st, const DevSym &A, const double *p_in,
 }
 
 // The held-q turn: ND as launch_spmv_sym has them, FAST both, the streaming loads only, p in place or two buffers
-#define OGL_HELD_Q(K, ND, FAST) k_cg_turn_held_q<HZ_R, HZ_L, HZ_B, K, ND, FAST>
+// -- and each of them twice: the static map on the held-z turn's 11 + 9 slots, the draw on 13 + 9
+#define OGL_HELD_Q(K, ND, FAST, DRAW) k_cg_turn_held_q<DRAW ? HQ_R : HZ_R, HZ_L, HZ_B, K, ND, FAST, DRAW>
 #define OGL_HELD_Q_EACH(DO) \
     DO(0, 2, false) DO(0, 2, true) DO(0, 3, false) DO(0, 3, true) DO(0, 4, false) DO(0, 4, true) \
     DO(2, 2, false) DO(2, 2, true) DO(2, 3, false) DO(2, 3, true) DO(2, 4, false) DO(2, 4, true)
@@ -680,18 +743,20 @@ int held_q_occupancy(int *per_cu, size_t *lds_bytes)
 {
     *per_cu = HZ_B;
     *lds_bytes = 0;
-#define OGL_HELD_Q_ASK(K, ND, FAST)                                                                                  \
-    {                                                                                                                \
-        int o = 0;                                                                                                   \
-        hipFuncAttributes fa;                                                                                        \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, OGL_HELD_Q(K, ND, FAST), BLOCK, 0) != hipSuccess ||     \
-            hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(OGL_HELD_Q(K, ND, FAST))) != hipSuccess)        \
-            return 1;                                                                                                \
-        *per_cu = std::min(*per_cu, o);                                                                              \
-        *lds_bytes = std::max(*lds_bytes, (size_t)fa.sharedSizeBytes);                                               \
+#define OGL_HELD_Q_ASK_ONE(K, ND, FAST, DRAW)                                                                            \
+    {                                                                                                                    \
+        int o = 0;                                                                                                       \
+        hipFuncAttributes fa;                                                                                            \
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, OGL_HELD_Q(K, ND, FAST, DRAW), BLOCK, 0) != hipSuccess ||   \
+            hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(OGL_HELD_Q(K, ND, FAST, DRAW))) != hipSuccess)      \
+            return 1;                                                                                                    \
+        *per_cu = std::min(*per_cu, o);                                                                                  \
+        *lds_bytes = std::max(*lds_bytes, (size_t)fa.sharedSizeBytes);                                                   \
     }
+#define OGL_HELD_Q_ASK(K, ND, FAST) OGL_HELD_Q_ASK_ONE(K, ND, FAST, false) OGL_HELD_Q_ASK_ONE(K, ND, FAST, true)
     OGL_HELD_Q_EACH(OGL_HELD_Q_ASK)
 #undef OGL_HELD_Q_ASK
+#undef OGL_HELD_Q_ASK_ONE
     return 0;
 }
 
@@ -705,9 +770,17 @@ void launch_cg_turn_held_q(hipStream_t st, const DevSym &A, double *r, const dou
     bool fast;
     const SymOffsets off = sym_offsets(A, &fast);
 #define OGL_HELD_Q_K(K, ND, FAST)                                                                                        \
-    hipLaunchKernelGGL((OGL_HELD_Q(K, ND, FAST)), grid, block, 0, st, A.n_rows, nc, hq.n_pos, off, A.mask, A.planes,     \
+    do {                                                                                                                 \
+        if (hq.static_slots < HQ_STATIC)                                                                                 \
+            OGL_HELD_Q_KD(K, ND, FAST, true);                                                                            \
+        else                                                                                                             \
+            OGL_HELD_Q_KD(K, ND, FAST, false);                                                                           \
+    } while (0)
+#define OGL_HELD_Q_KD(K, ND, FAST, DRAW)                                                                                 \
+    hipLaunchKernelGGL((OGL_HELD_Q(K, ND, FAST, DRAW)), grid, block, 0, st, A.n_rows, nc, hq.n_pos, off, A.mask, A.planes,     \
                        A.block_order, r, inv_diag, p, K == 2 ? p_out : p, x, s, hz.tagged, history, lead,                \
-                       K == 2 ? (const double *)ring.b[1] : nullptr, K == 2 ? ring.phase : 0, hz.early_slots)
+                       K == 2 ? (const double *)ring.b[1] : nullptr, K == 2 ? ring.phase : 0, hz.early_slots,            \
+                       hq.static_slots, hq.drawers, hq.heads, hq.parity)
 #define OGL_HELD_Q_ND(K, ND)              \
     do {                                  \
         if (fast)                         \
@@ -731,6 +804,7 @@ void launch_cg_turn_held_q(hipStream_t st, const DevSym &A, double *r, const dou
         OGL_HELD_Q_RING(4);
 #undef OGL_HELD_Q_RING
 #undef OGL_HELD_Q_ND
+#undef OGL_HELD_Q_KD
 #undef OGL_HELD_Q_K
 }
 #undef OGL_HELD_Q_EACH

@@ -65,8 +65,11 @@ OGL_VIEW_FIELDS(LeadBox, 24);
 inline void visit(KeyHasher &h, const LeadBox &a) { h(a.box), h(a.timeout_ticks), h(a.early_loads); }
 OGL_VIEW_FIELDS(HeldZ, 16);
 inline void visit(KeyHasher &h, const HeldZ &a) { h(a.tagged), h(a.grid), h(a.early_slots); }
-OGL_VIEW_FIELDS(HeldQ, 8);
-inline void visit(KeyHasher &h, const HeldQ &a) { h(a.on), h(a.n_pos); }
+OGL_VIEW_FIELDS(HeldQ, 32);
+inline void visit(KeyHasher &h, const HeldQ &a)
+{
+    h(a.on), h(a.n_pos), h(a.static_slots), h(a.drawers), h(a.heads), h(a.parity);
+}
 
 #undef OGL_VIEW_FIELDS
 

@@ -107,6 +107,20 @@ struct TurnSlots {
     }
 };
 
+// chunk_of where the slot is a run-time number (the early-x loop): a Src whose chunk_of is bound to unrolled loops --
+// the held-q turn's reads a drawn slot's position through a convergent operation, which a rolled loop with a run-time
+// bound cannot be unrolled around -- has chunk_of_rolled beside it
+template <class Src>
+__device__ __forceinline__ auto turn_chunk_rolled(const Src &src, int i, int) -> decltype(src.chunk_of_rolled(i))
+{
+    return src.chunk_of_rolled(i);
+}
+template <class Src>
+__device__ __forceinline__ int turn_chunk_rolled(const Src &src, int i, long)
+{
+    return src.chunk_of(i);
+}
+
 // the rows of a slot's chunk (a slot that owns nothing: no rows, no loads)
 __device__ __forceinline__ RowPair turn_rows(int chunk, int n)
 {
@@ -243,7 +257,7 @@ __device__ __forceinline__ void turn_phase_h(const Src &src, const TurnArgs &a, 
     const int n_early = ts.defers ? 0 : min(a.early_slots, R + L);
 #pragma unroll 2
     for (int i = 0; i < n_early; ++i) {
-        const int chunk = src.chunk_of(i);
+        const int chunk = turn_chunk_rolled(src, i, 0);
         if (chunk < 0) continue;
         const RowPair rp = my_rows(chunk, a.n);
         update_x(rp, ld2(a.p, rp), K);

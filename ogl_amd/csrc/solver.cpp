@@ -248,6 +248,7 @@ ogl_solver::~ogl_solver()
     ledger::pinned_free(h_scal);
     ledger::dev_free(lead_box);
     ledger::dev_free(held_z_box);
+    ledger::dev_free(held_q_heads);
     mixed.release();
     for (auto &e : poll_ev)
         if (e) ev_destroy(e);

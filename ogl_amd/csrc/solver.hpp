@@ -523,6 +523,7 @@ struct ogl_solver {
     unsigned long long *held_z_box = nullptr;
     size_t held_z_words = 0;
     int held_z_census = 0, held_z_census_grid = 0;
+    unsigned *held_q_heads = nullptr;  // the queue heads phase S of the held-q turn draws from (HQ_HEAD_WORDS words)
     hipEvent_t chk_ev[2] = {nullptr, nullptr};  // brackets one evaluated criterion check per solve (time_for_res_norm_eval)
     bool x_resident = false, b_resident = false;
     ogl::PrecondData own_precond;              // regenerated-for-this-solve preconditioner

@@ -814,6 +814,7 @@ int ogl_solver::turn_cg_held_q(KrylovRun &k, int enq, int pe)
     }
     launch_cg_turn_held_q(st, sym(), d_r.p, precond, p_new, k.p_of_turn(enq + 2), d_x.p, k.s2, d_history.p, k.lead,
                           k.ring_of_turn(enq + 1), k.hz, k.hq);
+    if (k.hq.static_slots < HQ_STATIC) k.hq.parity ^= 1;  // (the next LAUNCH draws from the set this one has zeroed)
     return OGL_OK;
 }
 
@@ -825,6 +826,8 @@ int ogl_solver::plan_held_z(KrylovRun &k)
     k.hz = HeldZ{};
     k.hq = HeldQ{};
     props["heldQInUse"] = 0.0;
+    props["heldQStaticSlotsInUse"] = 0.0;
+    props["heldQSlotsPerGroup"] = 0.0;
     props["heldZInUse"] = 0.0;
     props["heldZGridInUse"] = 0.0;  // (the workgroups the turn launches: whether heldZGrid was honoured or clipped by the device)
     if (!(k.lead.box != nullptr && k.fused && !k.fused2 && !k.generic && !k.multi && (k.ring.k == 0 || k.ring.k == 2)))
@@ -894,8 +897,41 @@ int ogl_solver::plan_held_z(KrylovRun &k)
     if (held_q) {
         k.hq.on = 1;
         k.hq.n_pos = n_pos;
+        k.hq.static_slots = HQ_STATIC;
+        k.hq.drawers = grid;
         props["heldQInUse"] = 1.0;
+        // Phase S draws the positions behind the first heldQStaticSlots slots from eight queues (k_cg_turn_held_q).
+        // heldQIdleGroups m (a test's knob: only with no static slot, m a multiple of 8): the last m workgroups own
+        // nothing, so the others fill the slots past HQ_STATIC.  The draw is complete only where, queue by queue, the
+        // drawing workgroups' free slots hold the queue; anything else runs the static map.
+        const int slots = HQ_R + HZ_L;
+        const int S = std::max(0, std::min(HQ_STATIC, (int)prop("heldQStaticSlots", (double)HQ_STATIC_DEFAULT)));
+        const int idle = (int)prop("heldQIdleGroups", 0.0);
+        const int drawers = (S == 0 && idle > 0 && idle % N_XCD == 0 && idle < grid) ? grid - idle : grid;
+        bool fits = (long long)S * grid < n_pos;  // (else there is nothing to draw)
+        for (int q = 0; fits && q < N_XCD; ++q) {
+            auto members = [q](long long lo, long long hi) {  // numbers in [lo, hi) that are q modulo 8
+                auto below = [q](long long v) { return v <= q ? 0 : (v - q + N_XCD - 1) / N_XCD; };
+                return hi > lo ? below(hi) - below(lo) : 0;
+            };
+            fits = members(0, drawers) * (slots - S) >= members((long long)S * grid, n_pos);
+        }
+        if (fits) {
+            if (!held_q_heads) {
+                void *h = nullptr;
+                OGL_HIP_CHECK(ledger::dev_malloc(&h, HQ_HEAD_WORDS * sizeof(unsigned)));
+                held_q_heads = static_cast<unsigned *>(h);
+            }
+            // (both sets: the parity restarts with the solve)
+            OGL_HIP_CHECK(hipMemsetAsync(held_q_heads, 0, HQ_HEAD_WORDS * sizeof(unsigned), st));
+            k.hq.static_slots = S;
+            k.hq.drawers = drawers;
+            k.hq.heads = held_q_heads;
+        }
     }
+    props["heldQStaticSlotsInUse"] = (double)k.hq.static_slots;
+    // (the static map runs the kernel on the held-z turn's 11 + 9 slots, the draw the one on 13 + 9)
+    props["heldQSlotsPerGroup"] = !k.hq.on ? 0.0 : (double)((k.hq.static_slots < HQ_STATIC ? HQ_R : HZ_R) + HZ_L);
     return OGL_OK;
 }
 

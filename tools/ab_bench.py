@@ -5,6 +5,9 @@ the in-loop SpMV time and the turn rate of every run.  Development tool.
 
   python tools/ab_bench.py tools/bin/libogl_amd_2c97ef6.so [rounds] [bench.py flags ...]
 
+OGL_AB_IN_TREE_PROP="KEY=v1,v2,..." runs the in-tree library once per value in every round, with --prop KEY=v (the other
+library never sees the property: it may not know it).
+
 Every run is a child process with a time limit of its own (OGL_AB_TIMEOUT_S, 300 s by default).  The first run that
 fails -- a non-zero exit, a time-out, no result line -- ends the whole A/B with exit status 1: nothing more is started on
 a device that a run may have left in a bad state.
@@ -22,10 +25,16 @@ limit = float(os.environ.get("OGL_AB_TIMEOUT_S", "300"))
 runner = ("import sys, runpy; sys.path.insert(0, %r); from ogl_amd import capi; capi.LIB_PATH = sys.argv[1]; "
           "sys.argv = ['bench.py'] + sys.argv[2:]; runpy.run_path(%r, run_name='__main__')"
           % (ROOT, os.path.join(ROOT, "bench.py")))
-libs = [("in-tree", os.path.join(ROOT, "ogl_amd", "lib", "libogl_amd.so")), (os.path.basename(other), other)]
+in_tree = os.path.join(ROOT, "ogl_amd", "lib", "libogl_amd.so")
+libs = [("in-tree", in_tree, [])]
+if os.environ.get("OGL_AB_IN_TREE_PROP"):
+    key, values = os.environ["OGL_AB_IN_TREE_PROP"].split("=")
+    libs = [("in-tree %s=%s" % (key, v), in_tree, ["--prop", "%s=%s" % (key, v)]) for v in values.split(",")]
+libs.append((os.path.basename(other), other, []))
 for r in range(rounds):
-    for name, lib in libs:
-        cmd = [sys.executable, "-c", runner, lib, "--steps", "3", "--warmup", "1", "--cpu-iters", "0", "--no-general-legs", *flags]
+    for name, lib, extra in libs:
+        cmd = [sys.executable, "-c", runner, lib, "--steps", "3", "--warmup", "1", "--cpu-iters", "0", "--no-general-legs", *flags,
+               *extra]
         try:
             p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=limit)
         except subprocess.TimeoutExpired:
