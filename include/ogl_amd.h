@@ -64,7 +64,9 @@ typedef enum {
     OGL_PRECOND_IRILU = 6, /* Preconditioner.H:147-178  the ILU factors, 5 Richardson sweeps each    */
     /* Preconditioner.H:259-341  aggregation AMG (Pgm + Multigrid), one V-cycle per apply.  Its keywords travel as
      * properties: maxLevels (9), minCoarseRows (10), coarseSolverIters (4), cycle (0 = v; 1 = w and 2 = f are refused),
-     * zeroGuess (1; 0 is refused). */
+     * zeroGuess (1; 0 is refused), aggregation (0 = pgm: ties to the larger column; 1 = hashed: ties to the larger edge
+     * hash) and aggregatePasses (1; 1 ... 4 pairwise coarsenings per kept level); any other value of the last two is
+     * OGL_ERR_INVALID.  Read-only after a solve: mgLevels, mgRows<l>, mgNnz<l>, mgPasses<l>, mgOperatorComplexity. */
     OGL_PRECOND_MULTIGRID = 7
 } ogl_precond_kind;
 

@@ -20,8 +20,10 @@ PRECOND_NONE, PRECOND_BJ, PRECOND_ISAI, PRECOND_GISAI = 0, 1, 2, 3
 PRECOND_IC, PRECOND_ILU, PRECOND_IRILU = 4, 5, 6
 PRECOND_MULTIGRID = 7
 # keywords of the Multigrid sub-dictionary (Preconditioner.H:297-317): they travel as properties; cycle as a number
-MG_KEYWORDS = ("maxLevels", "minCoarseRows", "coarseSolverIters", "cycle", "zeroGuess")
+MG_KEYWORDS = ("maxLevels", "minCoarseRows", "coarseSolverIters", "cycle", "zeroGuess", "aggregation", "aggregatePasses")
 MG_CYCLE = {"v": 0, "w": 1, "f": 2}
+MG_AGGREGATION = {"pgm": 0, "hashed": 1}
+_MG_WORDS = {"cycle": MG_CYCLE, "aggregation": MG_AGGREGATION}
 # keyword orthoMethod of GKOGMRES: it travels as a property, as a number
 ORTHO_METHOD = {"mgs": 0, "cgs": 1, "cgs2": 2}
 FORMAT_COO, FORMAT_CSR, FORMAT_ELL = 0, 1, 2
@@ -393,11 +395,12 @@ class Solver:
         return z
 
     def set_multigrid(self, **kw):
-        """The Multigrid keywords (MG_KEYWORDS; cycle as 'v' | 'w' | 'f', zeroGuess as a bool) for the next solves."""
+        """The Multigrid keywords (MG_KEYWORDS; cycle as 'v' | 'w' | 'f', aggregation as 'pgm' | 'hashed' -- either also as
+        its number --, zeroGuess as a bool) for the next solves."""
         for k, v in kw.items():
             if k not in MG_KEYWORDS:
                 raise KeyError(k)
-            self.set_property(k, float(MG_CYCLE[v] if k == "cycle" else v))
+            self.set_property(k, float(_MG_WORDS[k][v] if isinstance(v, str) else v))
         return self
 
     def mg_level(self, level):

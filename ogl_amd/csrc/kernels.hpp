@@ -347,6 +347,7 @@ struct MgCsr {  // one matrix of the hierarchy: columns ascending per row
 };
 constexpr double MG_OMEGA = 0.9;  // the smoother's relaxation factor
 constexpr int MG_ROUNDS = 15;     // matching rounds per coarsening
+constexpr int MG_MAX_PASSES = 4;  // keyword aggregatePasses: pairwise coarsenings per kept level
 struct MgScalars {                // the coarsest level's CG
     double rho, prev_rho, beta;
 };
@@ -367,10 +368,14 @@ struct MgTail {
     MgTailLevel lev[MG_TAIL_MAX_LEVELS];
 };
 void launch_mg_tail(hipStream_t st, const MgTail &T, const double *b, double *x, const DevScalars *gate);
-// generation: diag[i] = A(i, i), inv_d[i] = 1 / A(i, i)
+// generation: diag[i] = A(i, i), inv_d[i] = 1 / A(i, i) (inv_d nullptr: not wanted)
 void launch_mg_diag(hipStream_t st, const MgCsr &A, double *diag, double *inv_d);
-// s[i] = strongest unaggregated (want 0) / aggregated (want 1) neighbour of the unaggregated row i (-1 none, -2 row aggregated)
-void launch_mg_strongest(hipStream_t st, const MgCsr &A, const double *diag, const int32_t *agg, int want, int32_t *s);
+// s[i] = strongest unaggregated (want 0) / aggregated (want 1) neighbour of the unaggregated row i (-1 none, -2 row aggregated);
+// hashed: equal strengths go to the larger edge hash before the larger column (aggregation hashed)
+void launch_mg_strongest(hipStream_t st, const MgCsr &A, const double *diag, const int32_t *agg, int want, bool hashed,
+                         int32_t *s);
+// comp[i] = cidx[comp[i]]: the aggregate map of a kept level composed from its passes
+void launch_mg_compose(hipStream_t st, int32_t n, const int32_t *cidx, int32_t *comp);
 // mutual pairs become aggregates; *left += rows still unaggregated
 void launch_mg_match(hipStream_t st, int32_t n, const int32_t *s, int32_t *agg, int32_t *left);
 void launch_mg_join(hipStream_t st, int32_t n, const int32_t *s, int32_t *agg);

@@ -59,11 +59,26 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_diag(MgCsr A, double *__restric
     if (i >= A.n) return;
     const double d = entry_at(A, i, i);
     diag[i] = d;
-    inv_d[i] = 1.0 / d;
+    if (inv_d) inv_d[i] = 1.0 / d;  // (nullptr: a pass between two kept levels needs the strengths' diagonal only)
+}
+
+// aggregation hashed: the tie-breaker of an edge, symmetric in the pair ("hashed ties")
+__device__ __forceinline__ uint32_t mg_edge_hash(int i, int j)
+{
+    const uint32_t a = (uint32_t)(i < j ? i : j), b = (uint32_t)(i < j ? j : i);
+    uint32_t h = (a * 0x9E3779B1u) ^ (b * 0x85EBCA6Bu + 0xC2B2AE35u);
+    h ^= h >> 16;
+    h *= 0x7feb352du;
+    h ^= h >> 15;
+    h *= 0x846ca68bu;
+    h ^= h >> 16;
+    return h;
 }
 
 // s[i] = the neighbour of the unaggregated row i with the largest strength among the unaggregated (want == 0) or the
-// aggregated (want == 1) ones, ties to the larger column; -1: none; -2: row i is aggregated already
+// aggregated (want == 1) ones, ties to the larger column -- HASHED: to the larger mg_edge_hash(i, j) first; -1: none; -2: row i
+// is aggregated already
+template <bool HASHED>
 __global__ __launch_bounds__(MG_BLOCK) void k_mg_strongest(MgCsr A, const double *__restrict__ diag,
                                                            const int32_t *__restrict__ agg, int want,
                                                            int32_t *__restrict__ s)
@@ -76,6 +91,7 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_strongest(MgCsr A, const double
     }
     const double di = fabs(diag[i]);
     double best = -1.0;
+    uint32_t bh = 0;
     int bj = -1;
     const int end = A.row_ptrs[i + 1];
     for (int k = A.row_ptrs[i]; k < end;) {
@@ -87,12 +103,26 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_strongest(MgCsr A, const double
         const double w = 0.5 * (fabs(a) + fabs(entry_at(A, j, i)));
         const double dj = fabs(diag[j]);
         const double st = w / (di > dj ? di : dj);
-        if (st >= best) {
+        if (HASHED) {  // (columns ascend: among equal strengths and hashes the later one is the larger column)
+            const uint32_t h = mg_edge_hash(i, j);
+            if (st > best || (st == best && h >= bh)) {
+                best = st;
+                bh = h;
+                bj = j;
+            }
+        } else if (st >= best) {
             best = st;
             bj = j;
         }
     }
     s[i] = bj;
+}
+
+// the map of several passes composed: comp (fine row -> row of the pass's matrix) becomes fine row -> the pass's coarse row
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_compose(int n, const int32_t *__restrict__ cidx, int32_t *__restrict__ comp)
+{
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i < n) comp[i] = cidx[comp[i]];
 }
 
 // mutual pairs become aggregates rooted at the smaller row; *left += rows still unaggregated
@@ -457,10 +487,15 @@ __global__ __launch_bounds__(BLOCK) void k_mg_tail(MgTail T, const double *b_in,
     } while (0)
 
 void launch_mg_diag(hipStream_t st, const MgCsr &A, double *diag, double *inv_d) { MG_LAUNCH(k_mg_diag, A.n, A, diag, inv_d); }
-void launch_mg_strongest(hipStream_t st, const MgCsr &A, const double *diag, const int32_t *agg, int want, int32_t *s)
+void launch_mg_strongest(hipStream_t st, const MgCsr &A, const double *diag, const int32_t *agg, int want, bool hashed,
+                         int32_t *s)
 {
-    MG_LAUNCH(k_mg_strongest, A.n, A, diag, agg, want, s);
+    if (hashed)
+        MG_LAUNCH(k_mg_strongest<true>, A.n, A, diag, agg, want, s);
+    else
+        MG_LAUNCH(k_mg_strongest<false>, A.n, A, diag, agg, want, s);
 }
+void launch_mg_compose(hipStream_t st, int32_t n, const int32_t *cidx, int32_t *comp) { MG_LAUNCH(k_mg_compose, n, n, cidx, comp); }
 void launch_mg_match(hipStream_t st, int32_t n, const int32_t *s, int32_t *agg, int32_t *left)
 {
     MG_LAUNCH(k_mg_match, n, n, s, agg, left);

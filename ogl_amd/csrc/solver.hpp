@@ -23,6 +23,7 @@ namespace ogl {
 // it keeps no copy of it, only 1 / diagonal, the aggregates and the vectors.
 struct MgLevel {
     int32_t n = 0, nnz = 0, n_coarse = 0;      // n_coarse: rows of the next level (0: this is the coarsest)
+    int passes = 0;                            // pairwise coarsenings that made the next level (aggregatePasses; 0: coarsest)
     // levels >= 1; level 0 only on a renumbered device copy (own: the system matrix in the CALLER's numbering, in which
     // the hierarchy lives -- the products then run on it instead of the in-loop layout)
     bool own = true;
@@ -214,13 +215,18 @@ struct MultigridPart {
     DevBuf<int32_t> s, flag, incl, cidx, rows, sorted, left;
     DevBuf<unsigned long long> keys, keys_sorted;
     DevBuf<uint8_t> temp;
+    // aggregatePasses > 1: the matrices between two kept levels (one read, one written) and a pass's own aggregation
+    DevBuf<int32_t> pass_row_ptrs[2], pass_cols[2], pass_agg;
+    DevBuf<double> pass_vals[2];
     void release()
     {
         levels.clear();
         n_levels = 0;
         scal.release();
-        for (DevBuf<int32_t> *b : {&map0, &s, &flag, &incl, &cidx, &rows, &sorted, &left}) b->release();
-        for (DevBuf<double> *b : {&in, &out, &diag, &vals_sorted}) b->release();
+        for (DevBuf<int32_t> *b : {&map0, &s, &flag, &incl, &cidx, &rows, &sorted, &left, &pass_agg, &pass_row_ptrs[0],
+                                   &pass_row_ptrs[1], &pass_cols[0], &pass_cols[1]})
+            b->release();
+        for (DevBuf<double> *b : {&in, &out, &diag, &vals_sorted, &pass_vals[0], &pass_vals[1]}) b->release();
         keys.release();
         keys_sorted.release();
         temp.release();

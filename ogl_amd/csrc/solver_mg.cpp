@@ -41,6 +41,11 @@ int ogl_solver::check_multigrid_keywords()
     if (prop("coarseSolverIters", 4.0) < 0.0)
         return fail(OGL_ERR_INVALID, "preconditioner Multigrid: coarseSolverIters %d is negative",
                     (int)prop("coarseSolverIters", 4.0));
+    const double aggregation = prop("aggregation", 0.0), passes = prop("aggregatePasses", 1.0);
+    if (aggregation != 0.0 && aggregation != 1.0)
+        return fail(OGL_ERR_INVALID, "preconditioner Multigrid: aggregation %g is neither 0 (pgm) nor 1 (hashed)", aggregation);
+    if (!(passes >= 1.0 && passes <= (double)MG_MAX_PASSES) || passes != (double)(int)passes)
+        return fail(OGL_ERR_INVALID, "preconditioner Multigrid: aggregatePasses %g outside [1, %d]", passes, MG_MAX_PASSES);
     return OGL_OK;
 }
 
@@ -49,6 +54,8 @@ int ogl_solver::generate_multigrid(PrecondData &P)
     hipStream_t st = reg->stream;
     const int max_levels = (int)prop("maxLevels", 9.0);
     const int32_t min_coarse = (int32_t)prop("minCoarseRows", 10.0);
+    const bool hashed = prop("aggregation", 0.0) == 1.0;
+    const int max_passes = (int)prop("aggregatePasses", 1.0);
     MultigridPart &M = P.mg;
     M.cg_iters = (int)prop("coarseSolverIters", 4.0);
     OGL_TRY(grow(M.scal, 1, st));
@@ -117,57 +124,109 @@ int ogl_solver::generate_multigrid(PrecondData &P)
         OGL_TRY(grow(L.inv_d, (size_t)n + 2, st));
         OGL_TRY(grow(M.diag, (size_t)n, st));
         for (DevBuf<double> *v : {&L.xa, &L.xb, &L.t}) OGL_TRY(grow(*v, (size_t)n + 2, st));
+        L.passes = 0;
         launch_mg_diag(st, cur, M.diag.p, L.inv_d.p);
         if (l >= max_levels || n <= min_coarse || n < 2) break;
-        // ---- aggregation: up to MG_ROUNDS matching rounds, then the leftovers ----
+        // (every work buffer at the size of the level's first pass: the later passes' matrices are smaller)
         OGL_TRY(grow(L.agg, (size_t)n, st));
         for (DevBuf<int32_t> *v : {&M.s, &M.flag, &M.incl, &M.cidx, &M.rows, &M.sorted, &L.agg_rows})
             OGL_TRY(grow(*v, (size_t)std::max(n, m), st));
-        OGL_HIP_CHECK(hipMemsetAsync(L.agg.p, 0xff, (size_t)n * sizeof(int32_t), st));
-        int32_t prev_left = n;
-        for (int round = 0; round < MG_ROUNDS; ++round) {
-            OGL_HIP_CHECK(hipMemsetAsync(M.left.p, 0, sizeof(int32_t), st));
-            launch_mg_strongest(st, cur, M.diag.p, L.agg.p, 0, M.s.p);
-            launch_mg_match(st, n, M.s.p, L.agg.p, M.left.p);
-            int32_t left = 0;
-            OGL_TRY(read_i32(M.left.p, &left, st));
-            if (left == 0 || left == prev_left || (double)left < 0.05 * (double)n) break;
-            prev_left = left;
-        }
-        launch_mg_strongest(st, cur, M.diag.p, L.agg.p, 1, M.s.p);
-        launch_mg_join(st, n, M.s.p, L.agg.p);
-        // ---- numbering: roots in ascending order ----
         const size_t temp_bytes = mg_temp_bytes(n, m);
         OGL_TRY(grow(M.temp, temp_bytes, st));
-        launch_mg_root_flag(st, n, L.agg.p, M.flag.p);
-        OGL_HIP_CHECK(mg_inclusive_sum(st, M.temp.p, temp_bytes, M.flag.p, M.incl.p, n));
-        int32_t nc = 0;
-        OGL_TRY(read_i32(M.incl.p + (n - 1), &nc, st));
-        if (nc >= n) break;  // (a coarsening that does not shrink is dropped and ends the hierarchy)
-        launch_mg_coarse_index(st, n, L.agg.p, M.incl.p, M.cidx.p, M.rows.p);
-        OGL_HIP_CHECK(hipMemcpyAsync(L.agg.p, M.cidx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        // ---- the members of every coarse row, ascending ----
-        OGL_TRY(grow(L.agg_ptr, (size_t)nc + 1, st));
-        OGL_HIP_CHECK(mg_sort_rows(st, M.temp.p, temp_bytes, M.cidx.p, M.sorted.p, M.rows.p, L.agg_rows.p, n));
-        launch_mg_member_ptr(st, n, nc, M.sorted.p, L.agg_ptr.p);
-        // ---- A_c: stable sort of the entries by (agg(i), agg(j)), one entry per run, summed in sorted order ----
         OGL_TRY(grow(M.keys, (size_t)m, st));
         OGL_TRY(grow(M.keys_sorted, (size_t)m, st));
         OGL_TRY(grow(M.vals_sorted, (size_t)m, st));
-        launch_mg_keys(st, cur, L.agg.p, M.keys.p);
-        OGL_HIP_CHECK(mg_sort_entries(st, M.temp.p, temp_bytes, M.keys.p, M.keys_sorted.p, cur.vals,
-                                      M.vals_sorted.p, m));
-        launch_mg_head_flag(st, m, M.keys_sorted.p, M.flag.p);
-        OGL_HIP_CHECK(mg_inclusive_sum(st, M.temp.p, temp_bytes, M.flag.p, M.incl.p, m));
-        int32_t mc = 0;
-        OGL_TRY(read_i32(M.incl.p + (m - 1), &mc, st));
         if (M.levels.size() < (size_t)l + 2) M.levels.emplace_back(new MgLevel);
         MgLevel &C = *M.levels[(size_t)l + 1];
-        OGL_TRY(grow(C.row_ptrs, (size_t)nc + 1, st));
-        OGL_TRY(grow(C.cols, (size_t)mc, st));
-        OGL_TRY(grow(C.vals, (size_t)mc, st));
+        // ---- up to aggregatePasses pairwise coarsenings, each of the matrix the one before it made; L.agg: their
+        //      composition ----
+        MgCsr pa = cur;         // the matrix of this pass
+        bool in_place = false;  // pa is C's own arrays already
+        for (int pass = 0; pass < max_passes; ++pass) {
+            const int32_t pn = pa.n, pm = pa.nnz;
+            if (pass > 0) {
+                OGL_TRY(grow(M.pass_agg, (size_t)pn, st));
+                launch_mg_diag(st, pa, M.diag.p, nullptr);
+            }
+            int32_t *const agg = pass == 0 ? L.agg.p : M.pass_agg.p;
+            // ---- aggregation: up to MG_ROUNDS matching rounds, then the leftovers ----
+            OGL_HIP_CHECK(hipMemsetAsync(agg, 0xff, (size_t)pn * sizeof(int32_t), st));
+            int32_t prev_left = pn;
+            for (int round = 0; round < MG_ROUNDS; ++round) {
+                OGL_HIP_CHECK(hipMemsetAsync(M.left.p, 0, sizeof(int32_t), st));
+                launch_mg_strongest(st, pa, M.diag.p, agg, 0, hashed, M.s.p);
+                launch_mg_match(st, pn, M.s.p, agg, M.left.p);
+                int32_t left = 0;
+                OGL_TRY(read_i32(M.left.p, &left, st));
+                if (left == 0 || left == prev_left || (double)left < 0.05 * (double)pn) break;
+                prev_left = left;
+            }
+            launch_mg_strongest(st, pa, M.diag.p, agg, 1, hashed, M.s.p);
+            launch_mg_join(st, pn, M.s.p, agg);
+            // ---- numbering: roots in ascending order ----
+            launch_mg_root_flag(st, pn, agg, M.flag.p);
+            OGL_HIP_CHECK(mg_inclusive_sum(st, M.temp.p, temp_bytes, M.flag.p, M.incl.p, pn));
+            int32_t nc = 0;
+            OGL_TRY(read_i32(M.incl.p + (pn - 1), &nc, st));
+            if (nc >= pn) break;  // (a pass that does not shrink is dropped and ends the level's passes)
+            launch_mg_coarse_index(st, pn, agg, M.incl.p, M.cidx.p, M.rows.p);
+            if (pass == 0)
+                OGL_HIP_CHECK(hipMemcpyAsync(L.agg.p, M.cidx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+            else
+                launch_mg_compose(st, n, M.cidx.p, L.agg.p);
+            // ---- A_c: stable sort of the entries by (agg(i), agg(j)), one entry per run, summed in sorted order ----
+            launch_mg_keys(st, pa, M.cidx.p, M.keys.p);
+            OGL_HIP_CHECK(mg_sort_entries(st, M.temp.p, temp_bytes, M.keys.p, M.keys_sorted.p, pa.vals, M.vals_sorted.p, pm));
+            launch_mg_head_flag(st, pm, M.keys_sorted.p, M.flag.p);
+            OGL_HIP_CHECK(mg_inclusive_sum(st, M.temp.p, temp_bytes, M.flag.p, M.incl.p, pm));
+            int32_t mc = 0;
+            OGL_TRY(read_i32(M.incl.p + (pm - 1), &mc, st));
+            // (the level's last pass writes the kept level's own arrays; one that may be followed by another, scratch)
+            in_place = pass + 1 == max_passes || nc <= min_coarse || nc < 2;
+            MgCsr out;
+            out.n = nc;
+            out.nnz = mc;
+            if (in_place) {
+                OGL_TRY(grow(C.row_ptrs, (size_t)nc + 1, st));
+                OGL_TRY(grow(C.cols, (size_t)mc, st));
+                OGL_TRY(grow(C.vals, (size_t)mc, st));
+                launch_mg_compact(st, pm, nc, M.keys_sorted.p, M.vals_sorted.p, M.incl.p, C.row_ptrs.p, C.cols.p, C.vals.p);
+                out.row_ptrs = C.row_ptrs.p;
+                out.cols = C.cols.p;
+                out.vals = C.vals.p;
+            } else {
+                DevBuf<int32_t> &rp = M.pass_row_ptrs[pass & 1], &cc = M.pass_cols[pass & 1];
+                DevBuf<double> &vv = M.pass_vals[pass & 1];
+                OGL_TRY(grow(rp, (size_t)nc + 1, st));
+                OGL_TRY(grow(cc, (size_t)mc, st));
+                OGL_TRY(grow(vv, (size_t)mc, st));
+                launch_mg_compact(st, pm, nc, M.keys_sorted.p, M.vals_sorted.p, M.incl.p, rp.p, cc.p, vv.p);
+                out.row_ptrs = rp.p;
+                out.cols = cc.p;
+                out.vals = vv.p;
+            }
+            pa = out;
+            ++L.passes;
+            if (in_place) break;
+        }
+        if (L.passes == 0) break;  // (the first pass did not shrink: the hierarchy ends here)
+        const int32_t nc = pa.n, mc = pa.nnz;
+        if (!in_place) {  // (a later pass was dropped: the kept matrix is the scratch one of the pass before it)
+            OGL_TRY(grow(C.row_ptrs, (size_t)nc + 1, st));
+            OGL_TRY(grow(C.cols, (size_t)mc, st));
+            OGL_TRY(grow(C.vals, (size_t)mc, st));
+            OGL_HIP_CHECK(hipMemcpyAsync(C.row_ptrs.p, pa.row_ptrs, ((size_t)nc + 1) * sizeof(int32_t),
+                                         hipMemcpyDeviceToDevice, st));
+            if (mc > 0) {
+                OGL_HIP_CHECK(hipMemcpyAsync(C.cols.p, pa.cols, (size_t)mc * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+                OGL_HIP_CHECK(hipMemcpyAsync(C.vals.p, pa.vals, (size_t)mc * sizeof(double), hipMemcpyDeviceToDevice, st));
+            }
+        }
+        // ---- the members of every coarse row, ascending (rows[i] = i: k_mg_coarse_index of the first pass) ----
+        OGL_TRY(grow(L.agg_ptr, (size_t)nc + 1, st));
+        OGL_HIP_CHECK(mg_sort_rows(st, M.temp.p, temp_bytes, L.agg.p, M.sorted.p, M.rows.p, L.agg_rows.p, n));
+        launch_mg_member_ptr(st, n, nc, M.sorted.p, L.agg_ptr.p);
         OGL_TRY(grow(C.b, (size_t)nc + 2, st));
-        launch_mg_compact(st, m, nc, M.keys_sorted.p, M.vals_sorted.p, M.incl.p, C.row_ptrs.p, C.cols.p, C.vals.p);
         L.n_coarse = nc;
         C.n = nc;
         C.nnz = mc;
@@ -185,6 +244,8 @@ int ogl_solver::generate_multigrid(PrecondData &P)
         props["mgRows" + std::to_string(k)] = (double)M.levels[(size_t)k]->n;
         props["mgNnz" + std::to_string(k)] = (double)M.levels[(size_t)k]->nnz;
         total += (double)M.levels[(size_t)k]->nnz;
+        // (passes that made level k + 1; read-only)
+        if (k + 1 < M.n_levels) props["mgPasses" + std::to_string(k)] = (double)M.levels[(size_t)k]->passes;
     }
     props["mgOperatorComplexity"] = M.levels[0]->nnz > 0 ? total / (double)M.levels[0]->nnz : 1.0;
     return OGL_OK;
