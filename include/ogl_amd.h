@@ -65,8 +65,11 @@ typedef enum {
     /* Preconditioner.H:259-341  aggregation AMG (Pgm + Multigrid), one V-cycle per apply.  Its keywords travel as
      * properties: maxLevels (9), minCoarseRows (10), coarseSolverIters (4), cycle (0 = v; 1 = w and 2 = f are refused),
      * zeroGuess (1; 0 is refused), aggregation (0 = pgm: ties to the larger column; 1 = hashed: ties to the larger edge
-     * hash) and aggregatePasses (1; 1 ... 4 pairwise coarsenings per kept level); any other value of the last two is
-     * OGL_ERR_INVALID.  Read-only after a solve: mgLevels, mgRows<l>, mgNnz<l>, mgPasses<l>, mgOperatorComplexity. */
+     * hash), aggregatePasses (1; 1 ... 4 pairwise coarsenings per kept level) and coarseVisits (1; 1 ... 3 visits of
+     * every level below the fine one per visit of its parent, the coarsest excepted: 2 is a W-type cycle); any other value
+     * of the last three is OGL_ERR_INVALID, and a hierarchy on which coarseVisits makes more than 4096 level visits per
+     * apply fails the solve with OGL_ERR_UNSUPPORTED.  Read-only after a solve: mgLevels, mgRows<l>, mgNnz<l>, mgPasses<l>,
+     * mgVisits<l>, mgOperatorComplexity. */
     OGL_PRECOND_MULTIGRID = 7
 } ogl_precond_kind;
 

@@ -20,7 +20,8 @@ PRECOND_NONE, PRECOND_BJ, PRECOND_ISAI, PRECOND_GISAI = 0, 1, 2, 3
 PRECOND_IC, PRECOND_ILU, PRECOND_IRILU = 4, 5, 6
 PRECOND_MULTIGRID = 7
 # keywords of the Multigrid sub-dictionary (Preconditioner.H:297-317): they travel as properties; cycle as a number
-MG_KEYWORDS = ("maxLevels", "minCoarseRows", "coarseSolverIters", "cycle", "zeroGuess", "aggregation", "aggregatePasses")
+MG_KEYWORDS = ("maxLevels", "minCoarseRows", "coarseSolverIters", "cycle", "zeroGuess", "aggregation", "aggregatePasses",
+               "coarseVisits")
 MG_CYCLE = {"v": 0, "w": 1, "f": 2}
 MG_AGGREGATION = {"pgm": 0, "hashed": 1}
 _MG_WORDS = {"cycle": MG_CYCLE, "aggregation": MG_AGGREGATION}

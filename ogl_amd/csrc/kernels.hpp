@@ -353,7 +353,10 @@ struct MgScalars {                // the coarsest level's CG
 };
 // the tail of the hierarchy as ONE single-workgroup kernel: levels first .. last of the V-cycle (the last one is the
 // coarsest), walked down, solved and walked up with barriers between the phases.  b: right-hand side of the first of
-// them, x: its answer; the levels' own vectors hold everything in between.
+// them, x: its answer; the levels' own vectors hold everything in between.  coarse_visits (keyword coarseVisits, 1 .. 3):
+// every level below the first, the coarsest excepted, is visited that often per visit of its parent -- the first visit from
+// nothing, the others continued from the answer before with the same right-hand side.  The first level has one visit per
+// launch; continued != 0: that visit starts from what x holds (the launcher's own revisit of it) instead of from nothing.
 struct MgTailLevel {
     int32_t n = 0, n_coarse = 0;
     const int32_t *row_ptrs = nullptr, *cols = nullptr, *agg = nullptr, *agg_ptr = nullptr, *agg_rows = nullptr;
@@ -363,8 +366,10 @@ struct MgTailLevel {
 constexpr int MG_TAIL_MAX_LEVELS = 16;
 constexpr int MG_TAIL_DEFAULT_ROWS = 512;  // property mgTailRows
 constexpr int MG_TAIL_MAX_ROWS = 1024 * 512;  // (the finaliser's tree inside the workgroup: one partial per virtual thread)
+constexpr int MG_MAX_COARSE_VISITS = 3;     // keyword coarseVisits (k_mg_tail counts a level's visits in two bits)
+constexpr int MG_MAX_VISITS_PER_APPLY = 4096;  // level visits of one apply, summed over the levels: beyond it the solve is refused
 struct MgTail {
-    int32_t count = 0, cg_iters = 0;
+    int32_t count = 0, cg_iters = 0, coarse_visits = 1, continued = 0;
     MgTailLevel lev[MG_TAIL_MAX_LEVELS];
 };
 void launch_mg_tail(hipStream_t st, const MgTail &T, const double *b, double *x, const DevScalars *gate);

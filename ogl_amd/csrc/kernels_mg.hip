@@ -416,63 +416,91 @@ __device__ __forceinline__ double tail_dot(int n, const double *a, const double 
     return out[0];
 }
 
+// The recursion of the cycle ("coarse visits") walked iteratively: `l` is the level being visited,
+// `seen` holds, two bits per level, how many visits level l has had under the present visit of its parent (coarse_visits
+// <= 3).  Both are the same in every thread, so every barrier is reached by the whole workgroup.  The first of the tail's
+// levels is visited once per launch -- from nothing, or continued from the x_out of the launch before (T.continued); the
+// levels below it coarse_visits times per visit of their parent, the coarsest once.
 __global__ __launch_bounds__(BLOCK) void k_mg_tail(MgTail T, const double *b_in, double *x_out, const DevScalars *gate)
 {
     __shared__ double lds[2 * FIN_WAVES];
     MG_GATE();
     const int last = T.count - 1;
-    for (int l = 0; l < last; ++l) {  // ---- down ----
-        const MgTailLevel &L = T.lev[l];
-        const double *b = l == 0 ? b_in : L.b;
-        for (int i = threadIdx.x; i < L.n; i += BLOCK) L.xa[i] = MG_OMEGA * (b[i] * L.inv_d[i]);
-        __syncthreads();
-        tail_sweep(L, b, L.xa, nullptr, L.xb);
-        double *bc = T.lev[l + 1].b;
-        for (int I = threadIdx.x; I < L.n_coarse; I += BLOCK) {
-            double acc = 0.0;
-            for (int m = L.agg_ptr[I]; m < L.agg_ptr[I + 1]; ++m) {
-                const int i = L.agg_rows[m];
-                acc += b[i] - tail_row_product(L, i, L.xb, nullptr);
+    uint32_t seen = 0;
+    int l = 0;
+    bool continued = T.continued != 0;
+    for (;;) {
+        if (l < last) {  // ---- down: the 2 pre-sweeps, residual and restriction of one visit of level l ----
+            const MgTailLevel &L = T.lev[l];
+            const double *b = l == 0 ? b_in : L.b;
+            if (continued) {
+                tail_sweep(L, b, l == 0 ? x_out : L.xb, nullptr, L.xa);
+            } else {
+                for (int i = threadIdx.x; i < L.n; i += BLOCK) L.xa[i] = MG_OMEGA * (b[i] * L.inv_d[i]);
+                __syncthreads();
             }
-            bc[I] = acc;
-        }
-        __syncthreads();
-    }
-    {  // ---- the coarsest solver ----
-        const MgTailLevel &L = T.lev[last];
-        const double *b = last == 0 ? b_in : L.b;
-        double *x = last == 0 ? x_out : L.xb;
-        for (int i = threadIdx.x; i < L.n; i += BLOCK) {
-            L.r[i] = b[i];
-            x[i] = 0.0;
-            L.p[i] = 0.0;
-        }
-        __syncthreads();
-        double rho = 0.0;
-        for (int it = 0; it < T.cg_iters; ++it) {
-            const double prev = it == 0 ? 1.0 : rho;
-            rho = tail_dot(L.n, L.r, L.r, L.part, lds);
-            const double tmp = (prev == 0.0) ? 0.0 : rho / prev;
-            for (int i = threadIdx.x; i < L.n; i += BLOCK) L.p[i] = L.r[i] + tmp * L.p[i];
-            __syncthreads();
-            for (int i = threadIdx.x; i < L.n; i += BLOCK) L.t[i] = tail_row_product(L, i, L.p, nullptr);
-            __syncthreads();
-            const double beta = tail_dot(L.n, L.p, L.t, L.part, lds);
-            if (beta != 0.0) {
-                const double t = rho / beta;
-                for (int i = threadIdx.x; i < L.n; i += BLOCK) {
-                    x[i] += t * L.p[i];
-                    L.r[i] -= t * L.t[i];
+            tail_sweep(L, b, L.xa, nullptr, L.xb);
+            double *bc = T.lev[l + 1].b;
+            for (int I = threadIdx.x; I < L.n_coarse; I += BLOCK) {
+                double acc = 0.0;
+                for (int m = L.agg_ptr[I]; m < L.agg_ptr[I + 1]; ++m) {
+                    const int i = L.agg_rows[m];
+                    acc += b[i] - tail_row_product(L, i, L.xb, nullptr);
                 }
+                bc[I] = acc;
             }
             __syncthreads();
+            ++l;  // (the first visit of the level below: from nothing)
+            seen = (seen & ~(3u << (2 * l))) | (1u << (2 * l));
+            continued = false;
+            continue;
         }
-    }
-    for (int l = last - 1; l >= 0; --l) {  // ---- up ----
-        const MgTailLevel &L = T.lev[l];
-        const double *b = l == 0 ? b_in : L.b;
-        tail_sweep(L, b, L.xb, T.lev[l + 1].xb, L.xa);
-        tail_sweep(L, b, L.xa, nullptr, l == 0 ? x_out : L.xb);
+        {  // ---- the coarsest solver ----
+            const MgTailLevel &L = T.lev[last];
+            const double *b = last == 0 ? b_in : L.b;
+            double *x = last == 0 ? x_out : L.xb;
+            for (int i = threadIdx.x; i < L.n; i += BLOCK) {
+                L.r[i] = b[i];
+                x[i] = 0.0;
+                L.p[i] = 0.0;
+            }
+            __syncthreads();
+            double rho = 0.0;
+            for (int it = 0; it < T.cg_iters; ++it) {
+                const double prev = it == 0 ? 1.0 : rho;
+                rho = tail_dot(L.n, L.r, L.r, L.part, lds);
+                const double tmp = (prev == 0.0) ? 0.0 : rho / prev;
+                for (int i = threadIdx.x; i < L.n; i += BLOCK) L.p[i] = L.r[i] + tmp * L.p[i];
+                __syncthreads();
+                for (int i = threadIdx.x; i < L.n; i += BLOCK) L.t[i] = tail_row_product(L, i, L.p, nullptr);
+                __syncthreads();
+                const double beta = tail_dot(L.n, L.p, L.t, L.part, lds);
+                if (beta != 0.0) {
+                    const double t = rho / beta;
+                    for (int i = threadIdx.x; i < L.n; i += BLOCK) {
+                        x[i] += t * L.p[i];
+                        L.r[i] -= t * L.t[i];
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        // ---- up: correction and 2 post-sweeps, level by level, until a level is due another visit ----
+        for (;;) {
+            if (l == 0) return;
+            --l;
+            const MgTailLevel &L = T.lev[l];
+            const double *b = l == 0 ? b_in : L.b;
+            tail_sweep(L, b, L.xb, T.lev[l + 1].xb, L.xa);
+            tail_sweep(L, b, L.xa, nullptr, l == 0 ? x_out : L.xb);
+            if (l == 0) return;
+            const uint32_t had = (seen >> (2 * l)) & 3u;
+            if ((int)had < T.coarse_visits) {  // (same b, continued from the level's xb)
+                seen += 1u << (2 * l);
+                continued = true;
+                break;
+            }
+        }
     }
 }
 

@@ -500,7 +500,9 @@ struct ogl_solver {
     // Multigrid: generation of the hierarchy (per-round and per-level sizes are the only host round trips) and one V-cycle
     int generate_multigrid(ogl::PrecondData &P);
     void apply_multigrid(const double *in, double *out, const ogl::DevScalars *gate, double *dot_part);
-    void mg_cycle(int level, const double *b, double *x, const ogl::DevScalars *gate, int &launches);
+    void mg_cycle(int level, const double *b, double *x, const ogl::DevScalars *gate, int &launches, bool continued);
+    int prepare_multigrid_apply();
+    int mg_coarse_visits = 1;  // keyword coarseVisits as this solver's applies use it (prepare_multigrid_apply)
     // A x of a level (0: the system matrix on the in-loop layout, local part only)
     void mg_product(int level, const double *x, double *y, const ogl::DevScalars *gate);
     int check_multigrid_keywords();

@@ -1,6 +1,7 @@
 // solver_mg.cpp -- preconditioner Multigrid (Preconditioner.H:259-341): generation of the aggregation hierarchy on the
-// device, one V-cycle as the apply, and the entry points that hand the hierarchy out.  Kernels: kernels_mg.hip; the
-// contract: DESIGN.md section 7b.
+// device, one V-cycle as the apply (coarseVisits > 1: every coarse level but the coarsest visited that often per visit of
+// its parent), and the entry points that hand the hierarchy out.  Kernels: kernels_mg.hip; the contract: DESIGN.md
+// section 7b.
 #include "solver_internal.hpp"
 
 #include <algorithm>
@@ -46,6 +47,32 @@ int ogl_solver::check_multigrid_keywords()
         return fail(OGL_ERR_INVALID, "preconditioner Multigrid: aggregation %g is neither 0 (pgm) nor 1 (hashed)", aggregation);
     if (!(passes >= 1.0 && passes <= (double)MG_MAX_PASSES) || passes != (double)(int)passes)
         return fail(OGL_ERR_INVALID, "preconditioner Multigrid: aggregatePasses %g outside [1, %d]", passes, MG_MAX_PASSES);
+    const double visits = prop("coarseVisits", 1.0);
+    if (!(visits >= 1.0 && visits <= (double)MG_MAX_COARSE_VISITS) || visits != (double)(int)visits)
+        return fail(OGL_ERR_INVALID, "preconditioner Multigrid: coarseVisits %g outside [1, %d]", visits, MG_MAX_COARSE_VISITS);
+    return OGL_OK;
+}
+
+// This solver's side of an apply of the hierarchy (its own or a stored one): coarseVisits, and how often one apply then
+// visits every level -- level 0 once, every level below it coarseVisits times per visit of its parent, the coarsest as
+// often as its parent.  A hierarchy too deep for that many visits is refused here, before any apply.
+int ogl_solver::prepare_multigrid_apply()
+{
+    const MultigridPart &M = precond_data->mg;
+    mg_coarse_visits = (int)prop("coarseVisits", 1.0);
+    props["coarseVisits"] = (double)mg_coarse_visits;
+    std::vector<double> visits((size_t)M.n_levels, 1.0);
+    double total = 0.0;
+    for (int l = 0; l < M.n_levels; ++l) {
+        if (l > 0) visits[(size_t)l] = visits[(size_t)l - 1] * (l + 1 < M.n_levels ? (double)mg_coarse_visits : 1.0);
+        total += visits[(size_t)l];
+    }
+    if (total > (double)MG_MAX_VISITS_PER_APPLY)
+        return fail(OGL_ERR_UNSUPPORTED,
+                    "preconditioner Multigrid: coarseVisits %d on %d levels makes %.0f level visits per apply (at most %d): "
+                    "raise aggregatePasses for a shallower hierarchy, or lower coarseVisits or maxLevels",
+                    mg_coarse_visits, M.n_levels, total, MG_MAX_VISITS_PER_APPLY);
+    for (int l = 0; l < M.n_levels; ++l) props["mgVisits" + std::to_string(l)] = visits[(size_t)l];
     return OGL_OK;
 }
 
@@ -259,8 +286,10 @@ void ogl_solver::mg_product(int level, const double *x, double *y, const DevScal
         launch_mg_csr_spmv(reg->stream, precond_data->mg.levels[(size_t)level]->view(), x, y, gate);
 }
 
-// x = the V-cycle's answer to A_level x = b, from x = 0; x is none of the level's own vectors' aliases the cycle reads
-void ogl_solver::mg_cycle(int level, const double *b, double *x, const DevScalars *gate, int &launches)
+// One visit of `level`: x = the cycle's answer to A_level x = b -- from x = 0, or (continued; never level 0 or the coarsest)
+// from the answer of the visit before, which x then holds.  x is the level's own xb for every level but 0, so a continued
+// visit reads it before the visit's last sweep writes it.  The level's b is not written by its own visits.
+void ogl_solver::mg_cycle(int level, const double *b, double *x, const DevScalars *gate, int &launches, bool continued)
 {
     hipStream_t st = reg->stream;
     const MultigridPart &M = precond_data->mg;
@@ -271,6 +300,8 @@ void ogl_solver::mg_cycle(int level, const double *b, double *x, const DevScalar
         MgTail T;
         T.count = M.n_levels - level;
         T.cg_iters = M.cg_iters;
+        T.coarse_visits = mg_coarse_visits;
+        T.continued = continued ? 1 : 0;
         for (int k = 0; k < T.count; ++k) {
             const MgLevel &S = *M.levels[(size_t)(level + k)];
             MgTailLevel &D = T.lev[k];
@@ -322,8 +353,11 @@ void ogl_solver::mg_cycle(int level, const double *b, double *x, const DevScalar
     }
     const MgLevel &C = *M.levels[(size_t)level + 1];
     const MgCsr A = L.view();
-    // 2 pre-sweeps (the first from x = 0: no product), residual and restriction
-    launch_mg_jacobi0(st, n, b, L.inv_d.p, L.xa.p, gate);
+    // 2 pre-sweeps (the first from x = 0: no product; of a continued visit: a full sweep from x), residual and restriction
+    if (continued)
+        launch_mg_csr_sweep(st, A, L.inv_d.p, b, x, nullptr, nullptr, L.xa.p, gate);
+    else
+        launch_mg_jacobi0(st, n, b, L.inv_d.p, L.xa.p, gate);
     const bool layout = !L.own;  // (level 0 in the caller's numbering: products on the in-loop layout, sweeps behind them)
     if (layout) {
         mg_product(0, L.xa.p, L.t.p, gate);
@@ -336,8 +370,11 @@ void ogl_solver::mg_cycle(int level, const double *b, double *x, const DevScalar
         launch_mg_restrict(st, C.n, L.agg_ptr.p, L.agg_rows.p, A, b, L.xb.p, nullptr, C.b.p, gate);
         launches += 3;
     }
-    // the coarse correction lands in the coarse level's xb (its last post-sweep writes there; the coarsest CG too)
-    mg_cycle(level + 1, C.b.p, C.xb.p, gate, launches);
+    // the coarse correction lands in the coarse level's xb (its last post-sweep writes there; the coarsest CG too); the
+    // visits after the first continue from there with the same C.b
+    mg_cycle(level + 1, C.b.p, C.xb.p, gate, launches, false);
+    if (level + 2 < M.n_levels)
+        for (int visit = 1; visit < mg_coarse_visits; ++visit) mg_cycle(level + 1, C.b.p, C.xb.p, gate, launches, true);
     // correction and 2 post-sweeps
     if (layout) {
         launch_mg_prolong(st, n, L.xb.p, C.xb.p, L.agg.p, L.xa.p, gate);
@@ -369,11 +406,11 @@ void ogl_solver::apply_multigrid(const double *in, double *out, const DevScalars
     props["mgTailRows"] = tail_rows;
     if (pat.renumbered()) {  // (the vectors carried into the caller's order and back, as apply_factor does)
         launch_factor_gather_perm(reg->stream, pat.n_rows, d_new_id.p, in, M.in.p, gate);
-        mg_cycle(0, M.in.p, M.out.p, gate, launches);
+        mg_cycle(0, M.in.p, M.out.p, gate, launches, false);
         launch_factor_scatter_perm(reg->stream, pat.n_rows, d_new_id.p, M.out.p, out, gate);
         launches += 2;
     } else {
-        mg_cycle(0, in, out, gate, launches);
+        mg_cycle(0, in, out, gate, launches, false);
     }
     props["mgLaunchesPerApply"] = (double)launches;  // (without the fused dot of a Krylov turn)
     if (dot_part) launch_partials_dot(reg->stream, pat.n_rows, in, out, dot_part, gate);

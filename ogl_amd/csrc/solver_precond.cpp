@@ -393,8 +393,9 @@ int ogl_solver::prepare_apply()
     const size_t n = (size_t)pat.n_rows + 2;
     switch (P.kind) {
     case PrecondKind::None:
-    case PrecondKind::Gisai:
-    case PrecondKind::Multigrid: break;  // (Multigrid's vectors in the caller's order belong to the hierarchy)
+    case PrecondKind::Gisai: break;
+    // (Multigrid's vectors in the caller's order belong to the hierarchy; coarseVisits and its guard are this solver's)
+    case PrecondKind::Multigrid: OGL_TRY(prepare_multigrid_apply()); break;
     case PrecondKind::Jacobi: precond = P.bj.values.p; break;
     case PrecondKind::Isai: OGL_TRY(d_isai_tmp.alloc(n, st)); break;  // W r before W^T
     case PrecondKind::BlockJacobi:
