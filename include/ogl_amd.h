@@ -68,8 +68,10 @@ typedef enum {
      * hash), aggregatePasses (1; 1 ... 4 pairwise coarsenings per kept level) and coarseVisits (1; 1 ... 3 visits of
      * every level below the fine one per visit of its parent, the coarsest excepted: 2 is a W-type cycle); any other value
      * of the last three is OGL_ERR_INVALID, and a hierarchy on which coarseVisits makes more than 4096 level visits per
-     * apply fails the solve with OGL_ERR_UNSUPPORTED.  Read-only after a solve: mgLevels, mgRows<l>, mgNnz<l>, mgPasses<l>,
-     * mgVisits<l>, mgOperatorComplexity. */
+     * apply fails the solve with OGL_ERR_UNSUPPORTED.  cyclePrecision (0 = double; 1 = single: the cycle on binary32
+     * operands, the hierarchy still generated and handed out in fp64; any other value is OGL_ERR_INVALID, and so is a
+     * coefficient or inverse diagonal of a level that is finite in fp64 and not in binary32).  Read-only after a solve:
+     * mgLevels, mgRows<l>, mgNnz<l>, mgPasses<l>, mgVisits<l>, mgOperatorComplexity, mgCyclePrecisionInUse (0 | 1). */
     OGL_PRECOND_MULTIGRID = 7
 } ogl_precond_kind;
 

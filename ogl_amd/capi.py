@@ -21,10 +21,11 @@ PRECOND_IC, PRECOND_ILU, PRECOND_IRILU = 4, 5, 6
 PRECOND_MULTIGRID = 7
 # keywords of the Multigrid sub-dictionary (Preconditioner.H:297-317): they travel as properties; cycle as a number
 MG_KEYWORDS = ("maxLevels", "minCoarseRows", "coarseSolverIters", "cycle", "zeroGuess", "aggregation", "aggregatePasses",
-               "coarseVisits")
+               "coarseVisits", "cyclePrecision")
 MG_CYCLE = {"v": 0, "w": 1, "f": 2}
 MG_AGGREGATION = {"pgm": 0, "hashed": 1}
-_MG_WORDS = {"cycle": MG_CYCLE, "aggregation": MG_AGGREGATION}
+MG_CYCLE_PRECISION = {"double": 0, "single": 1}
+_MG_WORDS = {"cycle": MG_CYCLE, "aggregation": MG_AGGREGATION, "cyclePrecision": MG_CYCLE_PRECISION}
 # keyword orthoMethod of GKOGMRES: it travels as a property, as a number
 ORTHO_METHOD = {"mgs": 0, "cgs": 1, "cgs2": 2}
 FORMAT_COO, FORMAT_CSR, FORMAT_ELL = 0, 1, 2
@@ -396,8 +397,8 @@ class Solver:
         return z
 
     def set_multigrid(self, **kw):
-        """The Multigrid keywords (MG_KEYWORDS; cycle as 'v' | 'w' | 'f', aggregation as 'pgm' | 'hashed' -- either also as
-        its number --, zeroGuess as a bool) for the next solves."""
+        """The Multigrid keywords (MG_KEYWORDS; cycle as 'v' | 'w' | 'f', aggregation as 'pgm' | 'hashed', cyclePrecision as
+        'double' | 'single' -- each also as its number --, zeroGuess as a bool) for the next solves."""
         for k, v in kw.items():
             if k not in MG_KEYWORDS:
                 raise KeyError(k)

@@ -340,11 +340,14 @@ void launch_factor_scatter_perm(hipStream_t st, int32_t n, const int32_t *new_id
 
 // Multigrid (kernels_mg.hip; Preconditioner.H:259-341): an aggregation hierarchy generated on the device and the kernels
 // of its V-cycle.  The contract is spelled out in DESIGN.md section 7b.
-struct MgCsr {  // one matrix of the hierarchy: columns ascending per row
+template <class T>
+struct MgCsrOf {  // one matrix of the hierarchy: columns ascending per row
     int32_t n = 0, nnz = 0;
     const int32_t *row_ptrs = nullptr, *cols = nullptr;
-    const double *vals = nullptr;
+    const T *vals = nullptr;
 };
+using MgCsr = MgCsrOf<double>;
+using MgCsr32 = MgCsrOf<float>;  // keyword cyclePrecision single: the binary32 twin of a level, on the same index arrays
 constexpr double MG_OMEGA = 0.9;  // the smoother's relaxation factor
 constexpr int MG_ROUNDS = 15;     // matching rounds per coarsening
 constexpr int MG_MAX_PASSES = 4;  // keyword aggregatePasses: pairwise coarsenings per kept level
@@ -357,22 +360,29 @@ struct MgScalars {                // the coarsest level's CG
 // every level below the first, the coarsest excepted, is visited that often per visit of its parent -- the first visit from
 // nothing, the others continued from the answer before with the same right-hand side.  The first level has one visit per
 // launch; continued != 0: that visit starts from what x holds (the launcher's own revisit of it) instead of from nothing.
-struct MgTailLevel {
+template <class T>
+struct MgTailLevelOf {
     int32_t n = 0, n_coarse = 0;
     const int32_t *row_ptrs = nullptr, *cols = nullptr, *agg = nullptr, *agg_ptr = nullptr, *agg_rows = nullptr;
-    const double *vals = nullptr, *inv_d = nullptr;
-    double *b = nullptr, *xa = nullptr, *xb = nullptr, *t = nullptr, *r = nullptr, *p = nullptr, *part = nullptr;
+    const T *vals = nullptr, *inv_d = nullptr;
+    T *b = nullptr, *xa = nullptr, *xb = nullptr, *t = nullptr, *r = nullptr, *p = nullptr;
+    double *part = nullptr;  // (the partials of the coarsest CG's sums are doubles in either precision)
 };
+using MgTailLevel = MgTailLevelOf<double>;
 constexpr int MG_TAIL_MAX_LEVELS = 16;
 constexpr int MG_TAIL_DEFAULT_ROWS = 512;  // property mgTailRows
 constexpr int MG_TAIL_MAX_ROWS = 1024 * 512;  // (the finaliser's tree inside the workgroup: one partial per virtual thread)
 constexpr int MG_MAX_COARSE_VISITS = 3;     // keyword coarseVisits (k_mg_tail counts a level's visits in two bits)
 constexpr int MG_MAX_VISITS_PER_APPLY = 4096;  // level visits of one apply, summed over the levels: beyond it the solve is refused
-struct MgTail {
+template <class T>
+struct MgTailOf {
     int32_t count = 0, cg_iters = 0, coarse_visits = 1, continued = 0;
-    MgTailLevel lev[MG_TAIL_MAX_LEVELS];
+    MgTailLevelOf<T> lev[MG_TAIL_MAX_LEVELS];
 };
+using MgTail = MgTailOf<double>;
+using MgTail32 = MgTailOf<float>;
 void launch_mg_tail(hipStream_t st, const MgTail &T, const double *b, double *x, const DevScalars *gate);
+void launch_mg_tail(hipStream_t st, const MgTail32 &T, const float *b, float *x, const DevScalars *gate);
 // generation: diag[i] = A(i, i), inv_d[i] = 1 / A(i, i) (inv_d nullptr: not wanted)
 void launch_mg_diag(hipStream_t st, const MgCsr &A, double *diag, double *inv_d);
 // s[i] = strongest unaggregated (want 0) / aggregated (want 1) neighbour of the unaggregated row i (-1 none, -2 row aggregated);
@@ -418,6 +428,34 @@ void launch_mg_cg_fin(hipStream_t st, const double *part, int32_t n_part, int wh
 void launch_mg_cg_step1(hipStream_t st, int32_t n, double *p, const double *r, const MgScalars *s, const DevScalars *gate);
 void launch_mg_cg_step2(hipStream_t st, int32_t n, double *x, double *r, const double *p, const double *q,
                         const MgScalars *s, const DevScalars *gate);
+// --- keyword cyclePrecision single ("the cycle in single precision"): the same kernels on binary32
+// operands with binary32 operations; the scalars of the coarsest CG stay doubles, formed from wide sums (products of the
+// float64 casts in the loop's tree) and rounded once where a vector kernel takes them ---
+constexpr int32_t MG_NONE_BAD = 0x7f7f7f7f;  // an overflow word nothing has lowered (set by a byte fill)
+// the twin of one level: vals32 = fl32(A.vals) (nullptr: the level keeps no matrix of its own), inv_d32 = fl32(inv_d);
+// *bad = the smallest row with a value that is finite in fp64 and not in binary32
+void launch_mg_twin(hipStream_t st, const MgCsr &A, const double *inv_d, float *vals32, float *inv_d32, int32_t *bad);
+// level 0's first pre-sweep from the fp64 residual: b = fl32(r), x = omega32 (b inv_d)
+void launch_mg_jacobi0_in(hipStream_t st, int32_t n, const double *r, const float *inv_d, float *b, float *x,
+                          const DevScalars *gate);
+void launch_mg_jacobi0(hipStream_t st, int32_t n, const float *b, const float *inv_d, float *x, const DevScalars *gate);
+void launch_mg_prolong(hipStream_t st, int32_t n, const float *x, const float *xc, const int32_t *agg, float *x_out,
+                       const DevScalars *gate);
+// x_out64 != nullptr: the sweep's result is written there as doubles (level 0's last post-sweep) instead of x_out
+void launch_mg_csr_sweep(hipStream_t st, const MgCsr32 &A, const float *inv_d, const float *b, const float *x,
+                         const float *xc, const int32_t *agg, float *x_out, double *x_out64, const DevScalars *gate);
+void launch_mg_csr_spmv(hipStream_t st, const MgCsr32 &A, const float *x, float *y, const DevScalars *gate);
+// res != nullptr: bc[I] = sum of res_i (the residuals another kernel has formed); else of b_i - (A x)_i
+void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsr32 &A,
+                        const float *b, const float *x, const float *res, float *bc, const DevScalars *gate);
+// b64 != nullptr: r = fl32(b64) (a hierarchy of one level: the CG runs on the fp64 residual's rounding)
+void launch_mg_cg_init(hipStream_t st, int32_t n, const float *b, const double *b64, float *r, float *x, float *p,
+                       const DevScalars *gate);
+void launch_mg_wide_dot(hipStream_t st, int32_t n, const float *a, const float *b, double *part, const DevScalars *gate);
+void launch_mg_cg_step1(hipStream_t st, int32_t n, float *p, const float *r, const MgScalars *s, const DevScalars *gate);
+void launch_mg_cg_step2(hipStream_t st, int32_t n, float *x, float *r, const float *p, const float *q,
+                        const MgScalars *s, const DevScalars *gate);
+void launch_mg_widen(hipStream_t st, int32_t n, const float *x, double *out, const DevScalars *gate);
 
 // renumbering (keyword `renumber`): host vectors arrive in the caller's cell order
 //   scatter: out[new_id[i]] = in[i]   (b, x on upload)      gather: out[i] = in[new_id[i]]   (x on copy-back)
@@ -749,6 +787,19 @@ void launch_mixed_refresh(hipStream_t st, int64_t n, const int32_t *map, const d
 void launch_mixed_reset(hipStream_t st, MixedScalars *m, const DevCriterion &crit, double inner_rel_tol, int inner_max_iter);
 // y = A32 x on the fp32 twin of the half storage's planes / on the fp32 value array beside the device CSR; every row from
 // 0.0f in ascending column order.  part != nullptr: the per-chunk partials of sum (double)x_i (double)y_i
+// Multigrid's cycle in single precision runs its fine level on the same products with an epilogue in place of the pi
+// partials (MgEpi; gated by the Krylov loop's stop flag instead of the mixed mode's):
+//   MX_EPI_PLAIN y = A x | _SWEEP out = x + omega32 ((b - A x) inv_d) | _RESIDUAL out = b - A x | _SWEEP64 the sweep, written
+//   as doubles to out64
+enum MxEpilogue { MX_EPI_PI = 0, MX_EPI_PLAIN, MX_EPI_SWEEP, MX_EPI_RESIDUAL, MX_EPI_SWEEP64 };
+struct MgEpi {
+    const float *b = nullptr, *inv_d = nullptr;
+    float *out = nullptr;
+    double *out64 = nullptr;
+    const DevScalars *gate = nullptr;
+};
+void launch_mg_fine_sym(hipStream_t st, const DevSym &A, const float *planes, MxEpilogue epi, const float *x, const MgEpi &e);
+void launch_mg_fine_csr(hipStream_t st, const DevCsr &A, const float *vals, MxEpilogue epi, const float *x, const MgEpi &e);
 void launch_mixed_spmv_sym(hipStream_t st, const DevSym &A, const float *planes, const float *x, float *y, double *part,
                            const MixedScalars *gate);
 void launch_mixed_spmv_csr(hipStream_t st, const DevCsr &A, const float *vals, const float *x, float *y, double *part,

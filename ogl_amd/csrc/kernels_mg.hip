@@ -1,7 +1,8 @@
 // kernels_mg.hip -- the Multigrid preconditioner (Preconditioner.H:259-341): generation of an aggregation hierarchy on
 // the device and the kernels of one V-cycle.  The contract is this build's restatement of
-// [UPSTREAM] Ginkgo's Pgm(deterministic) + Multigrid; everything is fp64, products and sums round separately, and no
-// kernel uses an atomic on a value: the result does not depend on scheduling.
+// [UPSTREAM] Ginkgo's Pgm(deterministic) + Multigrid; products and sums round separately, and no kernel uses an atomic on a value:
+// the result does not depend on scheduling.  Generation is fp64; the apply's kernels take their operand type as a template
+// argument (double, or float for keyword cyclePrecision single).
 //
 // A repeated column of a row (cyclic patches) counts as ONE entry whose value is the sum of the repeats in stored order
 // (run_sum); the coarse matrices have one entry per column.
@@ -223,13 +224,63 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_compact(int m, int nc, const un
 #define MG_GATE() \
     if (gate && gate->stop) return
 
+// The apply's kernels take their operand type T from the caller: double (the contract of section 7b as it always was), or
+// float for `cyclePrecision single` -- the same operations in the same order on binary32 operands, every product and
+// every sum rounded once to T; omega is 0.9 rounded to T.  The coarsest CG's scalars are doubles in either case.
+
 // first pre-sweep, from x = 0
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_jacobi0(int n, const double *__restrict__ b, const double *__restrict__ inv_d,
-                                                         double *__restrict__ x, const DevScalars *gate)
+template <class T>
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_jacobi0(int n, const T *__restrict__ b, const T *__restrict__ inv_d,
+                                                         T *__restrict__ x, const DevScalars *gate)
 {
     MG_GATE();
     const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
-    if (i < n) x[i] = MG_OMEGA * (b[i] * inv_d[i]);
+    if (i < n) x[i] = (T)MG_OMEGA * (b[i] * inv_d[i]);
+}
+
+// ... of level 0 in single precision: b = fl32(r) is formed (and kept) on the way
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_jacobi0_in(int n, const double *__restrict__ r,
+                                                            const float *__restrict__ inv_d, float *__restrict__ b,
+                                                            float *__restrict__ x, const DevScalars *gate)
+{
+    MG_GATE();
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float bi = (float)r[i];
+    b[i] = bi;
+    x[i] = (float)MG_OMEGA * (bi * inv_d[i]);
+}
+
+// z = (double) x
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_widen(int n, const float *__restrict__ x, double *__restrict__ out,
+                                                       const DevScalars *gate)
+{
+    MG_GATE();
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i < n) out[i] = (double)x[i];
+}
+
+// the binary32 twin of a level: values and 1 / d rounded from the stored doubles; *bad = the smallest row that holds a
+// value finite in fp64 and not in binary32
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_twin(MgCsr A, const double *__restrict__ inv_d, float *__restrict__ vals32,
+                                                      float *__restrict__ inv_d32, int32_t *bad)
+{
+    const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (i >= A.n) return;
+    bool over = false;
+    const double d = inv_d[i];
+    const float fd = (float)d;
+    inv_d32[i] = fd;
+    over = fabs(d) <= 1.7976931348623157e308 && !(fabsf(fd) <= 3.402823466e38f);
+    if (vals32) {
+        for (int k = A.row_ptrs[i]; k < A.row_ptrs[i + 1]; ++k) {
+            const double v = A.vals[k];
+            const float f = (float)v;
+            vals32[k] = f;
+            over = over || (fabs(v) <= 1.7976931348623157e308 && !(fabsf(f) <= 3.402823466e38f));
+        }
+    }
+    if (over) atomicMin(bad, i);
 }
 
 // the sweep behind a product ax = A x that another kernel has formed
@@ -242,8 +293,9 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_sweep_epi(int n, const double *
     if (i < n) x_out[i] = x[i] + MG_OMEGA * ((b[i] - ax[i]) * inv_d[i]);
 }
 
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_prolong(int n, const double *__restrict__ x, const double *__restrict__ xc,
-                                                         const int32_t *__restrict__ agg, double *__restrict__ x_out,
+template <class T>
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_prolong(int n, const T *__restrict__ x, const T *__restrict__ xc,
+                                                         const int32_t *__restrict__ agg, T *__restrict__ x_out,
                                                          const DevScalars *gate)
 {
     MG_GATE();
@@ -251,58 +303,66 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_prolong(int n, const double *__
     if (i < n) x_out[i] = x[i] + xc[agg[i]];
 }
 
-// one sweep on a CSR level, x_out != x; xc != nullptr: the sweep reads t_j = x_j + xc[agg[j]] (the prolongation folded in)
-template <bool PROLONG>
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_csr_sweep(MgCsr A, const double *__restrict__ inv_d,
-                                                           const double *__restrict__ b, const double *__restrict__ x,
-                                                           const double *__restrict__ xc, const int32_t *__restrict__ agg,
-                                                           double *__restrict__ x_out, const DevScalars *gate)
+// one sweep on a CSR level, x_out != x; xc != nullptr: the sweep reads t_j = x_j + xc[agg[j]] (the prolongation folded in);
+// TO: the type the result is stored as (double: level 0's last post-sweep of the single-precision cycle writes z)
+template <class T, class TO, bool PROLONG>
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_csr_sweep(MgCsrOf<T> A, const T *__restrict__ inv_d,
+                                                           const T *__restrict__ b, const T *__restrict__ x,
+                                                           const T *__restrict__ xc, const int32_t *__restrict__ agg,
+                                                           TO *__restrict__ x_out, const DevScalars *gate)
 {
     MG_GATE();
     const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
     if (i >= A.n) return;
-    double s = 0.0;
+    T s = 0;
     for (int k = A.row_ptrs[i]; k < A.row_ptrs[i + 1]; ++k) {
         const int j = A.cols[k];
-        double t = x[j];
+        T t = x[j];
         if (PROLONG) t = t + xc[agg[j]];
         s += A.vals[k] * t;
     }
-    double ti = x[i];
+    T ti = x[i];
     if (PROLONG) ti = ti + xc[agg[i]];
-    x_out[i] = ti + MG_OMEGA * ((b[i] - s) * inv_d[i]);
+    x_out[i] = (TO)(ti + (T)MG_OMEGA * ((b[i] - s) * inv_d[i]));
 }
 
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_csr_spmv(MgCsr A, const double *__restrict__ x, double *__restrict__ y,
+template <class T>
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_csr_spmv(MgCsrOf<T> A, const T *__restrict__ x, T *__restrict__ y,
                                                           const DevScalars *gate)
 {
     MG_GATE();
     const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
     if (i >= A.n) return;
-    double s = 0.0;
+    T s = 0;
     for (int k = A.row_ptrs[i]; k < A.row_ptrs[i + 1]; ++k) s += A.vals[k] * x[A.cols[k]];
     y[i] = s;
 }
 
-// b_c[I] = sum over the members i of I, ascending, of r_i = b_i - (A x)_i; AX: the products come from `ax`
-template <bool AX>
+// b_c[I] = sum over the members i of I, ascending, of r_i = b_i - (A x)_i; FROM: MG_FROM_AX the products come from `ax`,
+// MG_FROM_RES the residuals themselves do
+enum { MG_FROM_A = 0, MG_FROM_AX = 1, MG_FROM_RES = 2 };
+template <class T, int FROM>
 __global__ __launch_bounds__(MG_BLOCK) void k_mg_restrict(int nc, const int32_t *__restrict__ agg_ptr,
-                                                          const int32_t *__restrict__ agg_rows, MgCsr A,
-                                                          const double *__restrict__ b, const double *__restrict__ x,
-                                                          const double *__restrict__ ax, double *__restrict__ bc,
+                                                          const int32_t *__restrict__ agg_rows, MgCsrOf<T> A,
+                                                          const T *__restrict__ b, const T *__restrict__ x,
+                                                          const T *__restrict__ ax, T *__restrict__ bc,
                                                           const DevScalars *gate)
 {
     MG_GATE();
     const int I = blockIdx.x * MG_BLOCK + threadIdx.x;
     if (I >= nc) return;
-    double acc = 0.0;
+    T acc = 0;
     for (int m = agg_ptr[I]; m < agg_ptr[I + 1]; ++m) {
         const int i = agg_rows[m];
-        double s;
-        if (AX) {
+        if (FROM == MG_FROM_RES) {
+            acc += ax[i];
+            continue;
+        }
+        T s;
+        if (FROM == MG_FROM_AX) {
             s = ax[i];
         } else {
-            s = 0.0;
+            s = 0;
             for (int k = A.row_ptrs[i]; k < A.row_ptrs[i + 1]; ++k) s += A.vals[k] * x[A.cols[k]];
         }
         acc += b[i] - s;
@@ -310,17 +370,33 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_restrict(int nc, const int32_t 
     bc[I] = acc;
 }
 
-// coarsest level: unpreconditioned CG from x = 0 ([UPSTREAM] cg::initialize / step_1 / step_2, guards as k_cg_step1 / 2)
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_cg_init(int n, const double *__restrict__ b, double *__restrict__ r,
-                                                         double *__restrict__ x, double *__restrict__ p,
-                                                         const DevScalars *gate)
+// coarsest level: unpreconditioned CG from x = 0 ([UPSTREAM] cg::initialize / step_1 / step_2, guards as k_cg_step1 / 2);
+// TB: the type b arrives in (double under T = float: a hierarchy of one level, r = fl32(b))
+template <class T, class TB>
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_cg_init(int n, const TB *__restrict__ b, T *__restrict__ r,
+                                                         T *__restrict__ x, T *__restrict__ p, const DevScalars *gate)
 {
     MG_GATE();
     const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
     if (i >= n) return;
-    r[i] = b[i];
-    x[i] = 0.0;
-    p[i] = 0.0;
+    r[i] = (T)b[i];
+    x[i] = 0;
+    p[i] = 0;
+}
+
+// the per-chunk partials of wide(a, b) = sum (double) a_i (double) b_i, as k_partials forms those of a dot product
+__global__ __launch_bounds__(BLOCK) void k_mg_wide_dot(int n, const float *__restrict__ a, const float *__restrict__ b,
+                                                       double *__restrict__ part, const DevScalars *gate)
+{
+    __shared__ double slot[N_WAVES];
+    MG_GATE();
+    const int chunk = blockIdx.x;
+    const RowPair r = my_rows(chunk, n);
+    double d = 0.0;
+    if (r.n > 0) d += (double)a[r.row] * (double)b[r.row];
+    if (r.n > 1) d += (double)a[r.row + 1] * (double)b[r.row + 1];
+    const double s = block_sum(d, slot);
+    if (threadIdx.x == 0) part[chunk] = s;
 }
 
 // the finaliser's tree over the chunk partials; what == 0: prev_rho <- rho (1 before the first), rho <- sum; 1: beta <- sum
@@ -341,19 +417,22 @@ __global__ __launch_bounds__(FIN_BLOCK) void k_mg_cg_fin(const double *part, int
     }
 }
 
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_cg_step1(int n, double *__restrict__ p, const double *__restrict__ r,
+// (the quotients are formed in fp64 and rounded once to T)
+template <class T>
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_cg_step1(int n, T *__restrict__ p, const T *__restrict__ r,
                                                           const MgScalars *s, const DevScalars *gate)
 {
     MG_GATE();
     const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
     if (i >= n) return;
     const double prev = s->prev_rho;
-    const double tmp = (prev == 0.0) ? 0.0 : s->rho / prev;
+    const T tmp = (T)((prev == 0.0) ? 0.0 : s->rho / prev);
     p[i] = r[i] + tmp * p[i];
 }
 
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_cg_step2(int n, double *__restrict__ x, double *__restrict__ r,
-                                                          const double *__restrict__ p, const double *__restrict__ q,
+template <class T>
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_cg_step2(int n, T *__restrict__ x, T *__restrict__ r,
+                                                          const T *__restrict__ p, const T *__restrict__ q,
                                                           const MgScalars *s, const DevScalars *gate)
 {
     MG_GATE();
@@ -361,7 +440,7 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_cg_step2(int n, double *__restr
     if (i >= n) return;
     const double beta = s->beta;
     if (beta == 0.0) return;
-    const double t = s->rho / beta;
+    const T t = (T)(s->rho / beta);
     x[i] += t * p[i];
     r[i] -= t * q[i];
 }
@@ -371,12 +450,13 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_cg_step2(int n, double *__restr
 // barrier between phases instead of a launch (those levels are bound by the dispatch latency of dependent launches, not by
 // bytes).  The same operations in the same order as the kernels above, hence the same bits.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ double tail_row_product(const MgTailLevel &L, int i, const double *x, const double *xc)
+template <class T>
+__device__ __forceinline__ T tail_row_product(const MgTailLevelOf<T> &L, int i, const T *x, const T *xc)
 {
-    double s = 0.0;
+    T s = 0;
     for (int k = L.row_ptrs[i]; k < L.row_ptrs[i + 1]; ++k) {
         const int j = L.cols[k];
-        double t = x[j];
+        T t = x[j];
         if (xc) t = t + xc[L.agg[j]];
         s += L.vals[k] * t;
     }
@@ -384,25 +464,36 @@ __device__ __forceinline__ double tail_row_product(const MgTailLevel &L, int i, 
 }
 
 // x_out = t + omega ((b - A t) inv_d), t = x (+ xc[agg]); x_out != x
-__device__ __forceinline__ void tail_sweep(const MgTailLevel &L, const double *b, const double *x, const double *xc,
-                                           double *x_out)
+template <class T>
+__device__ __forceinline__ void tail_sweep(const MgTailLevelOf<T> &L, const T *b, const T *x, const T *xc, T *x_out)
 {
     for (int i = threadIdx.x; i < L.n; i += BLOCK) {
-        const double s = tail_row_product(L, i, x, xc);
-        double ti = x[i];
+        const T s = tail_row_product(L, i, x, xc);
+        T ti = x[i];
         if (xc) ti = ti + xc[L.agg[i]];
-        x_out[i] = ti + MG_OMEGA * ((b[i] - s) * L.inv_d[i]);
+        x_out[i] = ti + (T)MG_OMEGA * ((b[i] - s) * L.inv_d[i]);
     }
     __syncthreads();
 }
 
-// a . b in the loop's tree: per-chunk partials as k_partials forms them, then the finaliser's tree (<= FIN_BLOCK chunks)
-__device__ __forceinline__ double tail_dot(int n, const double *a, const double *b, double *part, double *lds)
+__device__ __forceinline__ double2 tail_pair(const double *p, const RowPair &r) { return ld2(p, r); }
+__device__ __forceinline__ double2 tail_pair(const float *p, const RowPair &r)
+{
+    double2 v;
+    v.x = r.n > 0 ? (double)p[r.row] : 0.0;
+    v.y = r.n > 1 ? (double)p[r.row + 1] : 0.0;
+    return v;
+}
+
+// a . b (T = float: wide(a, b)) in the loop's tree: per-chunk partials as k_partials forms them, then the finaliser's tree
+// (<= FIN_BLOCK chunks)
+template <class T>
+__device__ __forceinline__ double tail_dot(int n, const T *a, const T *b, double *part, double *lds)
 {
     const int nc = (n + CHUNK_ROWS - 1) / CHUNK_ROWS;
     for (int c = 0; c < nc; ++c) {
         const RowPair r = my_rows(c, n);
-        const double2 va = ld2(a, r), vb = ld2(b, r);
+        const double2 va = tail_pair(a, r), vb = tail_pair(b, r);
         double d = 0.0;
         if (r.n > 0) d += va.x * vb.x;
         if (r.n > 1) d += va.y * vb.y;
@@ -421,31 +512,32 @@ __device__ __forceinline__ double tail_dot(int n, const double *a, const double 
 // <= 3).  Both are the same in every thread, so every barrier is reached by the whole workgroup.  The first of the tail's
 // levels is visited once per launch -- from nothing, or continued from the x_out of the launch before (T.continued); the
 // levels below it coarse_visits times per visit of their parent, the coarsest once.
-__global__ __launch_bounds__(BLOCK) void k_mg_tail(MgTail T, const double *b_in, double *x_out, const DevScalars *gate)
+template <class T>
+__global__ __launch_bounds__(BLOCK) void k_mg_tail(MgTailOf<T> Tl, const T *b_in, T *x_out, const DevScalars *gate)
 {
     __shared__ double lds[2 * FIN_WAVES];
     MG_GATE();
-    const int last = T.count - 1;
+    const int last = Tl.count - 1;
     uint32_t seen = 0;
     int l = 0;
-    bool continued = T.continued != 0;
+    bool continued = Tl.continued != 0;
     for (;;) {
         if (l < last) {  // ---- down: the 2 pre-sweeps, residual and restriction of one visit of level l ----
-            const MgTailLevel &L = T.lev[l];
-            const double *b = l == 0 ? b_in : L.b;
+            const MgTailLevelOf<T> &L = Tl.lev[l];
+            const T *b = l == 0 ? b_in : L.b;
             if (continued) {
-                tail_sweep(L, b, l == 0 ? x_out : L.xb, nullptr, L.xa);
+                tail_sweep<T>(L, b, l == 0 ? x_out : L.xb, nullptr, L.xa);
             } else {
-                for (int i = threadIdx.x; i < L.n; i += BLOCK) L.xa[i] = MG_OMEGA * (b[i] * L.inv_d[i]);
+                for (int i = threadIdx.x; i < L.n; i += BLOCK) L.xa[i] = (T)MG_OMEGA * (b[i] * L.inv_d[i]);
                 __syncthreads();
             }
-            tail_sweep(L, b, L.xa, nullptr, L.xb);
-            double *bc = T.lev[l + 1].b;
+            tail_sweep<T>(L, b, L.xa, nullptr, L.xb);
+            T *bc = Tl.lev[l + 1].b;
             for (int I = threadIdx.x; I < L.n_coarse; I += BLOCK) {
-                double acc = 0.0;
+                T acc = 0;
                 for (int m = L.agg_ptr[I]; m < L.agg_ptr[I + 1]; ++m) {
                     const int i = L.agg_rows[m];
-                    acc += b[i] - tail_row_product(L, i, L.xb, nullptr);
+                    acc += b[i] - tail_row_product<T>(L, i, L.xb, nullptr);
                 }
                 bc[I] = acc;
             }
@@ -456,27 +548,27 @@ __global__ __launch_bounds__(BLOCK) void k_mg_tail(MgTail T, const double *b_in,
             continue;
         }
         {  // ---- the coarsest solver ----
-            const MgTailLevel &L = T.lev[last];
-            const double *b = last == 0 ? b_in : L.b;
-            double *x = last == 0 ? x_out : L.xb;
+            const MgTailLevelOf<T> &L = Tl.lev[last];
+            const T *b = last == 0 ? b_in : L.b;
+            T *x = last == 0 ? x_out : L.xb;
             for (int i = threadIdx.x; i < L.n; i += BLOCK) {
                 L.r[i] = b[i];
-                x[i] = 0.0;
-                L.p[i] = 0.0;
+                x[i] = 0;
+                L.p[i] = 0;
             }
             __syncthreads();
             double rho = 0.0;
-            for (int it = 0; it < T.cg_iters; ++it) {
+            for (int it = 0; it < Tl.cg_iters; ++it) {
                 const double prev = it == 0 ? 1.0 : rho;
-                rho = tail_dot(L.n, L.r, L.r, L.part, lds);
-                const double tmp = (prev == 0.0) ? 0.0 : rho / prev;
+                rho = tail_dot<T>(L.n, L.r, L.r, L.part, lds);
+                const T tmp = (T)((prev == 0.0) ? 0.0 : rho / prev);
                 for (int i = threadIdx.x; i < L.n; i += BLOCK) L.p[i] = L.r[i] + tmp * L.p[i];
                 __syncthreads();
-                for (int i = threadIdx.x; i < L.n; i += BLOCK) L.t[i] = tail_row_product(L, i, L.p, nullptr);
+                for (int i = threadIdx.x; i < L.n; i += BLOCK) L.t[i] = tail_row_product<T>(L, i, L.p, nullptr);
                 __syncthreads();
-                const double beta = tail_dot(L.n, L.p, L.t, L.part, lds);
+                const double beta = tail_dot<T>(L.n, L.p, L.t, L.part, lds);
                 if (beta != 0.0) {
-                    const double t = rho / beta;
+                    const T t = (T)(rho / beta);
                     for (int i = threadIdx.x; i < L.n; i += BLOCK) {
                         x[i] += t * L.p[i];
                         L.r[i] -= t * L.t[i];
@@ -489,13 +581,13 @@ __global__ __launch_bounds__(BLOCK) void k_mg_tail(MgTail T, const double *b_in,
         for (;;) {
             if (l == 0) return;
             --l;
-            const MgTailLevel &L = T.lev[l];
-            const double *b = l == 0 ? b_in : L.b;
-            tail_sweep(L, b, L.xb, T.lev[l + 1].xb, L.xa);
-            tail_sweep(L, b, L.xa, nullptr, l == 0 ? x_out : L.xb);
+            const MgTailLevelOf<T> &L = Tl.lev[l];
+            const T *b = l == 0 ? b_in : L.b;
+            tail_sweep<T>(L, b, L.xb, Tl.lev[l + 1].xb, L.xa);
+            tail_sweep<T>(L, b, L.xa, nullptr, l == 0 ? x_out : L.xb);
             if (l == 0) return;
             const uint32_t had = (seen >> (2 * l)) & 3u;
-            if ((int)had < T.coarse_visits) {  // (same b, continued from the level's xb)
+            if ((int)had < Tl.coarse_visits) {  // (same b, continued from the level's xb)
                 seen += 1u << (2 * l);
                 continued = true;
                 break;
@@ -582,7 +674,7 @@ hipError_t mg_sort_entries(hipStream_t st, void *temp, size_t temp_bytes, const 
 
 void launch_mg_jacobi0(hipStream_t st, int32_t n, const double *b, const double *inv_d, double *x, const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_jacobi0, n, n, b, inv_d, x, gate);
+    MG_LAUNCH(k_mg_jacobi0<double>, n, n, b, inv_d, x, gate);
 }
 void launch_mg_sweep_epi(hipStream_t st, int32_t n, const double *b, const double *ax, const double *inv_d, const double *x,
                          double *x_out, const DevScalars *gate)
@@ -592,31 +684,31 @@ void launch_mg_sweep_epi(hipStream_t st, int32_t n, const double *b, const doubl
 void launch_mg_prolong(hipStream_t st, int32_t n, const double *x, const double *xc, const int32_t *agg, double *x_out,
                        const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_prolong, n, n, x, xc, agg, x_out, gate);
+    MG_LAUNCH(k_mg_prolong<double>, n, n, x, xc, agg, x_out, gate);
 }
 void launch_mg_csr_sweep(hipStream_t st, const MgCsr &A, const double *inv_d, const double *b, const double *x,
                          const double *xc, const int32_t *agg, double *x_out, const DevScalars *gate)
 {
     if (xc)
-        MG_LAUNCH(k_mg_csr_sweep<true>, A.n, A, inv_d, b, x, xc, agg, x_out, gate);
+        MG_LAUNCH((k_mg_csr_sweep<double, double, true>), A.n, A, inv_d, b, x, xc, agg, x_out, gate);
     else
-        MG_LAUNCH(k_mg_csr_sweep<false>, A.n, A, inv_d, b, x, xc, agg, x_out, gate);
+        MG_LAUNCH((k_mg_csr_sweep<double, double, false>), A.n, A, inv_d, b, x, xc, agg, x_out, gate);
 }
 void launch_mg_csr_spmv(hipStream_t st, const MgCsr &A, const double *x, double *y, const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_csr_spmv, A.n, A, x, y, gate);
+    MG_LAUNCH(k_mg_csr_spmv<double>, A.n, A, x, y, gate);
 }
 void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsr &A,
                         const double *b, const double *x, const double *ax, double *bc, const DevScalars *gate)
 {
     if (ax)
-        MG_LAUNCH(k_mg_restrict<true>, nc, nc, agg_ptr, agg_rows, A, b, x, ax, bc, gate);
+        MG_LAUNCH((k_mg_restrict<double, MG_FROM_AX>), nc, nc, agg_ptr, agg_rows, A, b, x, ax, bc, gate);
     else
-        MG_LAUNCH(k_mg_restrict<false>, nc, nc, agg_ptr, agg_rows, A, b, x, ax, bc, gate);
+        MG_LAUNCH((k_mg_restrict<double, MG_FROM_A>), nc, nc, agg_ptr, agg_rows, A, b, x, ax, bc, gate);
 }
 void launch_mg_cg_init(hipStream_t st, int32_t n, const double *b, double *r, double *x, double *p, const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_cg_init, n, n, b, r, x, p, gate);
+    MG_LAUNCH((k_mg_cg_init<double, double>), n, n, b, r, x, p, gate);
 }
 void launch_mg_cg_fin(hipStream_t st, const double *part, int32_t n_part, int what, int first, MgScalars *s,
                       const DevScalars *gate)
@@ -625,17 +717,92 @@ void launch_mg_cg_fin(hipStream_t st, const double *part, int32_t n_part, int wh
 }
 void launch_mg_cg_step1(hipStream_t st, int32_t n, double *p, const double *r, const MgScalars *s, const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_cg_step1, n, n, p, r, s, gate);
+    MG_LAUNCH(k_mg_cg_step1<double>, n, n, p, r, s, gate);
 }
 void launch_mg_cg_step2(hipStream_t st, int32_t n, double *x, double *r, const double *p, const double *q,
                         const MgScalars *s, const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_cg_step2, n, n, x, r, p, q, s, gate);
+    MG_LAUNCH(k_mg_cg_step2<double>, n, n, x, r, p, q, s, gate);
 }
 
 void launch_mg_tail(hipStream_t st, const MgTail &T, const double *b, double *x, const DevScalars *gate)
 {
-    hipLaunchKernelGGL(k_mg_tail, dim3(1), dim3(BLOCK), 0, st, T, b, x, gate);
+    hipLaunchKernelGGL(k_mg_tail<double>, dim3(1), dim3(BLOCK), 0, st, T, b, x, gate);
+}
+
+// ---- cyclePrecision single ----
+void launch_mg_twin(hipStream_t st, const MgCsr &A, const double *inv_d, float *vals32, float *inv_d32, int32_t *bad)
+{
+    MG_LAUNCH(k_mg_twin, A.n, A, inv_d, vals32, inv_d32, bad);
+}
+void launch_mg_jacobi0_in(hipStream_t st, int32_t n, const double *r, const float *inv_d, float *b, float *x,
+                          const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_jacobi0_in, n, n, r, inv_d, b, x, gate);
+}
+void launch_mg_jacobi0(hipStream_t st, int32_t n, const float *b, const float *inv_d, float *x, const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_jacobi0<float>, n, n, b, inv_d, x, gate);
+}
+void launch_mg_prolong(hipStream_t st, int32_t n, const float *x, const float *xc, const int32_t *agg, float *x_out,
+                       const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_prolong<float>, n, n, x, xc, agg, x_out, gate);
+}
+void launch_mg_csr_sweep(hipStream_t st, const MgCsr32 &A, const float *inv_d, const float *b, const float *x,
+                         const float *xc, const int32_t *agg, float *x_out, double *x_out64, const DevScalars *gate)
+{
+    if (x_out64 && xc)
+        MG_LAUNCH((k_mg_csr_sweep<float, double, true>), A.n, A, inv_d, b, x, xc, agg, x_out64, gate);
+    else if (x_out64)
+        MG_LAUNCH((k_mg_csr_sweep<float, double, false>), A.n, A, inv_d, b, x, xc, agg, x_out64, gate);
+    else if (xc)
+        MG_LAUNCH((k_mg_csr_sweep<float, float, true>), A.n, A, inv_d, b, x, xc, agg, x_out, gate);
+    else
+        MG_LAUNCH((k_mg_csr_sweep<float, float, false>), A.n, A, inv_d, b, x, xc, agg, x_out, gate);
+}
+void launch_mg_csr_spmv(hipStream_t st, const MgCsr32 &A, const float *x, float *y, const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_csr_spmv<float>, A.n, A, x, y, gate);
+}
+void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsr32 &A,
+                        const float *b, const float *x, const float *res, float *bc, const DevScalars *gate)
+{
+    if (res)
+        MG_LAUNCH((k_mg_restrict<float, MG_FROM_RES>), nc, nc, agg_ptr, agg_rows, A, b, x, res, bc, gate);
+    else
+        MG_LAUNCH((k_mg_restrict<float, MG_FROM_A>), nc, nc, agg_ptr, agg_rows, A, b, x, res, bc, gate);
+}
+void launch_mg_cg_init(hipStream_t st, int32_t n, const float *b, const double *b64, float *r, float *x, float *p,
+                       const DevScalars *gate)
+{
+    if (b64)
+        MG_LAUNCH((k_mg_cg_init<float, double>), n, n, b64, r, x, p, gate);
+    else
+        MG_LAUNCH((k_mg_cg_init<float, float>), n, n, b, r, x, p, gate);
+}
+void launch_mg_wide_dot(hipStream_t st, int32_t n, const float *a, const float *b, double *part, const DevScalars *gate)
+{
+    const int nc = (n + CHUNK_ROWS - 1) / CHUNK_ROWS;
+    if (nc == 0) return;
+    hipLaunchKernelGGL(k_mg_wide_dot, dim3(nc), dim3(BLOCK), 0, st, n, a, b, part, gate);
+}
+void launch_mg_cg_step1(hipStream_t st, int32_t n, float *p, const float *r, const MgScalars *s, const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_cg_step1<float>, n, n, p, r, s, gate);
+}
+void launch_mg_cg_step2(hipStream_t st, int32_t n, float *x, float *r, const float *p, const float *q,
+                        const MgScalars *s, const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_cg_step2<float>, n, n, x, r, p, q, s, gate);
+}
+void launch_mg_widen(hipStream_t st, int32_t n, const float *x, double *out, const DevScalars *gate)
+{
+    MG_LAUNCH(k_mg_widen, n, n, x, out, gate);
+}
+void launch_mg_tail(hipStream_t st, const MgTail32 &T, const float *b, float *x, const DevScalars *gate)
+{
+    hipLaunchKernelGGL(k_mg_tail<float>, dim3(1), dim3(BLOCK), 0, st, T, b, x, gate);
 }
 
 }  // namespace ogl

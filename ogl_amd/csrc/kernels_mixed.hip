@@ -60,15 +60,48 @@ __global__ __launch_bounds__(BLOCK) void k_mx_refresh(long n, const int *__restr
 struct MxOffsets {
     int d[SYM_MAX_OFFSETS];
 };
-template <int ND, bool FAST>
+// EPI (MxEpilogue): what follows the product.  MX_EPI_PI: the inner solve's y and partial.  The others serve the fine level
+// of Multigrid's cycle in single precision: gated by the Krylov loop's stop flag, they write y = A x
+// (_PLAIN), the sweep x + omega32 ((b - A x) inv_d) (_SWEEP; _SWEEP64: as doubles) or the residual b - A x (_RESIDUAL) --
+// the row's own x is in registers already, so no elementwise pass follows the product.
+template <int EPI>
+__device__ __forceinline__ void mg_epilogue(const MgEpi &e, const RowPair &rp, const float2 &xd, const float2 &acc)
+{
+    const float2 bv = ld2f(e.b, rp);
+    float2 o;
+    if (EPI == MX_EPI_RESIDUAL) {
+        o.x = bv.x - acc.x;
+        o.y = bv.y - acc.y;
+    } else {
+        const float2 dv = ld2f(e.inv_d, rp);
+        const float w = (float)MG_OMEGA;
+        const float u0 = w * ((bv.x - acc.x) * dv.x), u1 = w * ((bv.y - acc.y) * dv.y);
+        o.x = xd.x + u0;
+        o.y = xd.y + u1;
+    }
+    if (EPI == MX_EPI_SWEEP64) {
+        double2 z;
+        z.x = (double)o.x;
+        z.y = (double)o.y;
+        st2(e.out64, rp, z);
+    } else {
+        st2f(e.out, rp, o);
+    }
+}
+
+template <int ND, bool FAST, int EPI>
 __global__ __launch_bounds__(BLOCK) void k_mx_spmv_sym(int n_rows, int n_chunks, MxOffsets off,
                                                        const uint8_t *__restrict__ mask, const float *__restrict__ planes,
                                                        const float *__restrict__ x, float *__restrict__ y,
                                                        double *__restrict__ part, const MixedScalars *gate,
-                                                       const int *__restrict__ block_order)
+                                                       const int *__restrict__ block_order, MgEpi epi)
 {
     __shared__ double slot[N_WAVES];
-    if (mx_gated(gate)) return;
+    if (EPI == MX_EPI_PI) {
+        if (mx_gated(gate)) return;
+    } else if (epi.gate && epi.gate->stop) {
+        return;
+    }
     const int chunk = block_order ? block_order[blockIdx.x] : xcd_chunk(blockIdx.x);
     if (chunk < 0 || chunk >= n_chunks) return;
     const RowPair rp = my_rows(chunk, n_rows);
@@ -123,8 +156,12 @@ __global__ __launch_bounds__(BLOCK) void k_mx_spmv_sym(int n_rows, int n_chunks,
         if ((m0 >> (ND - 1 + j)) & 1u) acc.x = acc.x + up[j].x * xu[j].x;
         if ((m1 >> (ND - 1 + j)) & 1u) acc.y = acc.y + up[j].y * xu[j].y;
     }
+    if (EPI > MX_EPI_PLAIN) {
+        mg_epilogue<EPI>(epi, rp, xd, acc);
+        return;
+    }
     st2f(y, rp, acc);
-    if (part) {
+    if (EPI == MX_EPI_PI && part) {
         double d = 0.0;
         if (rp.n > 0) d += (double)xd.x * (double)acc.x;
         if (rp.n > 1) d += (double)xd.y * (double)acc.y;
@@ -135,15 +172,20 @@ __global__ __launch_bounds__(BLOCK) void k_mx_spmv_sym(int n_rows, int n_chunks,
 
 // ... and on the fp32 value array beside the device CSR (k_spmv_stream's walk: the chunk's entries as 8-byte value and
 // column pairs, the products parked in LDS, every thread adds up its rows left to right)
+template <int EPI>
 __global__ __launch_bounds__(BLOCK) void k_mx_spmv_csr(int n_rows, int n_chunks, const int *__restrict__ row_ptrs,
                                                        const int *__restrict__ cols, const float *__restrict__ vals,
                                                        const float *__restrict__ x, float *__restrict__ y,
                                                        double *__restrict__ part, const MixedScalars *gate, int xgroup,
-                                                       const int *__restrict__ block_order)
+                                                       const int *__restrict__ block_order, MgEpi epi)
 {
     __shared__ __attribute__((aligned(16))) float prod[SPMV_TILE];
     __shared__ double slot[N_WAVES];
-    if (mx_gated(gate)) return;
+    if (EPI == MX_EPI_PI) {
+        if (mx_gated(gate)) return;
+    } else if (epi.gate && epi.gate->stop) {
+        return;
+    }
     const int chunk = block_order ? block_order[blockIdx.x] : xcd_chunk(blockIdx.x, xgroup);
     if (chunk < 0 || chunk >= n_chunks) return;
     const int tid = threadIdx.x;
@@ -183,15 +225,34 @@ __global__ __launch_bounds__(BLOCK) void k_mx_spmv_csr(int n_rows, int n_chunks,
         }
         __syncthreads();
     }
+    if (EPI > MX_EPI_PLAIN) {  // (Multigrid's fine level: the epilogue of mg_epilogue, row by row)
+#pragma unroll
+        for (int j = 0; j < ROWS_PER_THREAD; ++j) {
+            const int i = row + j;
+            if (i >= r1) continue;
+            const float res = epi.b[i] - acc[j];
+            if (EPI == MX_EPI_RESIDUAL) {
+                epi.out[i] = res;
+                continue;
+            }
+            const float u = (float)MG_OMEGA * (res * epi.inv_d[i]);
+            const float o = x[i] + u;
+            if (EPI == MX_EPI_SWEEP64)
+                epi.out64[i] = (double)o;
+            else
+                epi.out[i] = o;
+        }
+        return;
+    }
     double d = 0.0;
 #pragma unroll
     for (int j = 0; j < ROWS_PER_THREAD; ++j) {
         if (row + j < r1) {
             y[row + j] = acc[j];
-            if (part) d += (double)x[row + j] * (double)acc[j];
+            if (EPI == MX_EPI_PI && part) d += (double)x[row + j] * (double)acc[j];
         }
     }
-    if (part) {
+    if (EPI == MX_EPI_PI && part) {
         const double s = block_sum(d, slot);
         if (tid == 0) part[chunk] = s;
     }
@@ -488,8 +549,9 @@ void launch_mixed_reset(hipStream_t st, MixedScalars *m, const DevCriterion &cri
     hipLaunchKernelGGL(k_mx_reset, dim3(1), dim3(64), 0, st, m, crit, inner_rel_tol, inner_max_iter);
 }
 
-void launch_mixed_spmv_sym(hipStream_t st, const DevSym &A, const float *planes, const float *x, float *y, double *part,
-                           const MixedScalars *gate)
+template <int EPI>
+static void mx_launch_sym(hipStream_t st, const DevSym &A, const float *planes, const float *x, float *y, double *part,
+                          const MixedScalars *gate, const MgEpi &e)
 {
     if (A.n_rows == 0) return;
     const int nc = (int)n_chunks(A.n_rows);
@@ -501,11 +563,11 @@ void launch_mixed_spmv_sym(hipStream_t st, const DevSym &A, const float *planes,
 #define OGL_MX_SYM(ND)                                                                                                  \
     do {                                                                                                                \
         if (fast)                                                                                                       \
-            hipLaunchKernelGGL((k_mx_spmv_sym<ND, true>), grid, block, 0, st, A.n_rows, nc, off, A.mask, planes, x, y,   \
-                               part, gate, A.block_order);                                                              \
+            hipLaunchKernelGGL((k_mx_spmv_sym<ND, true, EPI>), grid, block, 0, st, A.n_rows, nc, off, A.mask, planes, x, \
+                               y, part, gate, A.block_order, e);                                                        \
         else                                                                                                            \
-            hipLaunchKernelGGL((k_mx_spmv_sym<ND, false>), grid, block, 0, st, A.n_rows, nc, off, A.mask, planes, x, y,  \
-                               part, gate, A.block_order);                                                              \
+            hipLaunchKernelGGL((k_mx_spmv_sym<ND, false, EPI>), grid, block, 0, st, A.n_rows, nc, off, A.mask, planes,  \
+                               x, y, part, gate, A.block_order, e);                                                     \
     } while (0)
     if (A.nd == 2)
         OGL_MX_SYM(2);
@@ -517,15 +579,51 @@ void launch_mixed_spmv_sym(hipStream_t st, const DevSym &A, const float *planes,
 #undef OGL_MX_SYM
 }
 
-void launch_mixed_spmv_csr(hipStream_t st, const DevCsr &A, const float *vals, const float *x, float *y, double *part,
-                           const MixedScalars *gate)
+template <int EPI>
+static void mx_launch_csr(hipStream_t st, const DevCsr &A, const float *vals, const float *x, float *y, double *part,
+                          const MixedScalars *gate, const MgEpi &e)
 {
     if (A.n_rows == 0) return;
     const int nc = (int)n_chunks(A.n_rows);
     const int xg = A.xcd_group > 0 ? A.xcd_group : XCD_GROUP;
     const dim3 grid(A.block_order ? A.n_blocks : xcd_grid(nc, xg)), block(BLOCK);
-    hipLaunchKernelGGL(k_mx_spmv_csr, grid, block, 0, st, A.n_rows, nc, A.row_ptrs, A.cols, vals, x, y, part, gate, xg,
-                       A.block_order);
+    hipLaunchKernelGGL(k_mx_spmv_csr<EPI>, grid, block, 0, st, A.n_rows, nc, A.row_ptrs, A.cols, vals, x, y, part, gate, xg,
+                       A.block_order, e);
+}
+
+void launch_mixed_spmv_sym(hipStream_t st, const DevSym &A, const float *planes, const float *x, float *y, double *part,
+                           const MixedScalars *gate)
+{
+    mx_launch_sym<MX_EPI_PI>(st, A, planes, x, y, part, gate, MgEpi{});
+}
+
+void launch_mixed_spmv_csr(hipStream_t st, const DevCsr &A, const float *vals, const float *x, float *y, double *part,
+                           const MixedScalars *gate)
+{
+    mx_launch_csr<MX_EPI_PI>(st, A, vals, x, y, part, gate, MgEpi{});
+}
+
+// (MX_EPI_PLAIN: the product lands in e.out)
+void launch_mg_fine_sym(hipStream_t st, const DevSym &A, const float *planes, MxEpilogue epi, const float *x, const MgEpi &e)
+{
+    switch (epi) {
+    case MX_EPI_PLAIN: mx_launch_sym<MX_EPI_PLAIN>(st, A, planes, x, e.out, nullptr, nullptr, e); break;
+    case MX_EPI_SWEEP: mx_launch_sym<MX_EPI_SWEEP>(st, A, planes, x, nullptr, nullptr, nullptr, e); break;
+    case MX_EPI_RESIDUAL: mx_launch_sym<MX_EPI_RESIDUAL>(st, A, planes, x, nullptr, nullptr, nullptr, e); break;
+    case MX_EPI_SWEEP64: mx_launch_sym<MX_EPI_SWEEP64>(st, A, planes, x, nullptr, nullptr, nullptr, e); break;
+    default: break;
+    }
+}
+
+void launch_mg_fine_csr(hipStream_t st, const DevCsr &A, const float *vals, MxEpilogue epi, const float *x, const MgEpi &e)
+{
+    switch (epi) {
+    case MX_EPI_PLAIN: mx_launch_csr<MX_EPI_PLAIN>(st, A, vals, x, e.out, nullptr, nullptr, e); break;
+    case MX_EPI_SWEEP: mx_launch_csr<MX_EPI_SWEEP>(st, A, vals, x, nullptr, nullptr, nullptr, e); break;
+    case MX_EPI_RESIDUAL: mx_launch_csr<MX_EPI_RESIDUAL>(st, A, vals, x, nullptr, nullptr, nullptr, e); break;
+    case MX_EPI_SWEEP64: mx_launch_csr<MX_EPI_SWEEP64>(st, A, vals, x, nullptr, nullptr, nullptr, e); break;
+    default: break;
+    }
 }
 
 void launch_mixed_head(hipStream_t st, MixedScalars *m, DevScalars *s, const double *part, int32_t n_part, double *history)

@@ -32,6 +32,21 @@ struct MgLevel {
     DevBuf<int32_t> agg, agg_ptr, agg_rows;    // fine-to-coarse map, members per coarse row (ascending)
     DevBuf<double> b, xa, xb, t, r, p;         // right-hand side (levels >= 1), iterates, A x; r, p: the coarsest level's CG
     DevBuf<double> part;                       // ... its per-chunk partials
+    // keyword cyclePrecision single: the binary32 twin -- values (where the level keeps a matrix of
+    // its own) and 1 / d rounded from the doubles above, on the same index arrays -- and the level's vectors in binary32.
+    // Built by the first apply in single precision of a generated hierarchy (MultigridPart::twin_of); they only grow.
+    DevBuf<float> vals32, inv_d32;
+    DevBuf<float> b32, xa32, xb32, t32, r32, p32;
+    MgCsr32 view32() const
+    {
+        MgCsr32 A;
+        A.n = n;
+        A.nnz = nnz;
+        A.row_ptrs = row_ptrs.p;
+        A.cols = cols.p;
+        A.vals = vals32.p;
+        return A;
+    }
     MgCsr view() const
     {
         MgCsr A;
@@ -218,10 +233,19 @@ struct MultigridPart {
     // aggregatePasses > 1: the matrices between two kept levels (one read, one written) and a pass's own aggregation
     DevBuf<int32_t> pass_row_ptrs[2], pass_cols[2], pass_agg;
     DevBuf<double> pass_vals[2];
+    // cyclePrecision single: `generated` counts the generations of this object, twin_of names the one the levels' binary32
+    // twins were rounded from (0: none); bad: the overflow words of the conversions -- [0] the position in the fine level's
+    // fp32 copy (Fp32Dev), [1 + l] the row of level l's twin.  The twin is a cache of the hierarchy, made by whichever
+    // solver first applies it in single precision: hence mutable.
+    uint64_t generated = 0;
+    mutable uint64_t twin_of = 0;
+    mutable DevBuf<int32_t> bad;
     void release()
     {
         levels.clear();
         n_levels = 0;
+        twin_of = 0;
+        bad.release();
         scal.release();
         for (DevBuf<int32_t> *b : {&map0, &s, &flag, &incl, &cidx, &rows, &sorted, &left, &pass_agg, &pass_row_ptrs[0],
                                    &pass_row_ptrs[1], &pass_cols[0], &pass_cols[1]})
@@ -503,6 +527,12 @@ struct ogl_solver {
     void mg_cycle(int level, const double *b, double *x, const ogl::DevScalars *gate, int &launches, bool continued);
     int prepare_multigrid_apply();
     int mg_coarse_visits = 1;  // keyword coarseVisits as this solver's applies use it (prepare_multigrid_apply)
+    // keyword cyclePrecision as this solver's applies use it: the cycle on binary32 operands
+    bool mg_single = false;
+    int prepare_multigrid_single();  // the levels' twin, the fine level's fp32 copy, the vectors; the overflow check
+    void mg_cycle32(int level, const float *b, float *x, const double *in64, double *out64, const ogl::DevScalars *gate,
+                    int &launches, bool continued);
+    void mg_fine32(ogl::MxEpilogue epi, const float *x, const ogl::MgEpi &e);  // level 0's product with its epilogue
     // A x of a level (0: the system matrix on the in-loop layout, local part only)
     void mg_product(int level, const double *x, double *y, const ogl::DevScalars *gate);
     int check_multigrid_keywords();
@@ -584,6 +614,7 @@ struct ogl_solver {
     int mixed_requested(bool *on);      // the keywords' validation and the refusals (OGL_ERR_INVALID / _UNSUPPORTED)
     // buffers, the scalars reset for a solve, the fp32 copy of the matrix current for this values epoch
     int mixed_storage(const ogl::DevCriterion &crit, double inner_rel_tol, int inner_max_iter);
+    int fp32_bad_row(int64_t position, int64_t *row) const;  // the device row of a position in fp32_dev's value array
     int mixed_overflow(const ogl::MixedScalars &m);  // OGL_ERR_INVALID naming the row when a value overflowed binary32
     void mixed_spmv(const float *x, float *y, double *part, const ogl::MixedScalars *gate);
     int run_mixed(ogl_perf *perf);

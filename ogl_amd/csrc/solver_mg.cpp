@@ -1,6 +1,6 @@
 // solver_mg.cpp -- preconditioner Multigrid (Preconditioner.H:259-341): generation of the aggregation hierarchy on the
 // device, one V-cycle as the apply (coarseVisits > 1: every coarse level but the coarsest visited that often per visit of
-// its parent), and the entry points that hand the hierarchy out.  Kernels: kernels_mg.hip; the contract: DESIGN.md
+// its parent; cyclePrecision single: on binary32 operands), and the entry points that hand the hierarchy out.  Kernels: kernels_mg.hip; the contract: DESIGN.md
 // section 7b.
 #include "solver_internal.hpp"
 
@@ -50,6 +50,10 @@ int ogl_solver::check_multigrid_keywords()
     const double visits = prop("coarseVisits", 1.0);
     if (!(visits >= 1.0 && visits <= (double)MG_MAX_COARSE_VISITS) || visits != (double)(int)visits)
         return fail(OGL_ERR_INVALID, "preconditioner Multigrid: coarseVisits %g outside [1, %d]", visits, MG_MAX_COARSE_VISITS);
+    const double precision = prop("cyclePrecision", 0.0);
+    if (precision != 0.0 && precision != 1.0)
+        return fail(OGL_ERR_INVALID, "preconditioner Multigrid: cyclePrecision %g is neither 0 (double) nor 1 (single)",
+                    precision);
     return OGL_OK;
 }
 
@@ -73,6 +77,73 @@ int ogl_solver::prepare_multigrid_apply()
                     "raise aggregatePasses for a shallower hierarchy, or lower coarseVisits or maxLevels",
                     mg_coarse_visits, M.n_levels, total, MG_MAX_VISITS_PER_APPLY);
     for (int l = 0; l < M.n_levels; ++l) props["mgVisits" + std::to_string(l)] = visits[(size_t)l];
+    // cyclePrecision is the applier's too: a stored hierarchy gets its binary32 twin when a solver first asks for it
+    mg_single = prop("cyclePrecision", 0.0) == 1.0;
+    if (mg_single) OGL_TRY(prepare_multigrid_single());
+    props["mgCyclePrecisionInUse"] = mg_single ? 1.0 : 0.0;
+    return OGL_OK;
+}
+
+// cyclePrecision single ("the cycle in single precision"): what an apply on binary32 operands needs
+// besides the hierarchy.  (1) The levels' twin -- values and 1 / d rounded from the stored doubles by one kernel per level,
+// and the levels' vectors -- once per generated hierarchy, whoever applies it.  (2) Where level 0 is the system matrix in
+// the in-loop layout, the fp32 copy the mixed-precision mode uses (Fp32Dev), refreshed per values epoch.  A value that is
+// finite in fp64 and not in binary32 fails the solve; what failed is left stale, so that the next solve converts -- and
+// reports -- again.
+int ogl_solver::prepare_multigrid_single()
+{
+    hipStream_t st = reg->stream;
+    const MultigridPart &M = precond_data->mg;
+    const int nl = M.n_levels;
+    OGL_TRY(grow(M.bad, (size_t)nl + 1, st));
+    bool converted = false;
+    if (M.twin_of != M.generated) {
+        OGL_HIP_CHECK(hipMemsetAsync(M.bad.p, 0x7f, ((size_t)nl + 1) * sizeof(int32_t), st));
+        for (int l = 0; l < nl; ++l) {
+            MgLevel &L = *M.levels[(size_t)l];
+            const size_t nv = (size_t)L.n + 4;  // (a trailing pair access of the last odd row stays inside)
+            OGL_TRY(grow(L.inv_d32, nv, st));
+            if (L.own) OGL_TRY(grow(L.vals32, (size_t)L.nnz + 2, st));
+            for (DevBuf<float> *v : {&L.b32, &L.xa32, &L.xb32, &L.t32}) OGL_TRY(grow(*v, nv, st));
+            if (l == nl - 1) {
+                OGL_TRY(grow(L.r32, nv, st));
+                OGL_TRY(grow(L.p32, nv, st));
+            }
+            launch_mg_twin(st, L.view(), L.inv_d.p, L.own ? L.vals32.p : nullptr, L.inv_d32.p, M.bad.p + 1 + l);
+        }
+        converted = true;
+    }
+    const MgLevel &L0 = *M.levels[0];
+    if (!L0.own) {
+        const bool half = spmv_layout == SpmvLayout::Sym;
+        if (half) refresh_values(SpmvLayout::Sym);
+        OGL_TRY(fp32_dev.ensure(half, pat_id, half ? sym_dev.map.n : d_vals.n, st));
+        if (fp32_dev.epoch != vals_epoch || vals_epoch == 0) {
+            if (!converted) OGL_HIP_CHECK(hipMemsetAsync(M.bad.p, 0x7f, sizeof(int32_t), st));
+            fp32_dev.refresh(half ? sym_dev.map.p : nullptr, d_vals.p, M.bad.p, st);
+            fp32_dev.epoch = vals_epoch;
+            converted = true;
+        }
+    }
+    if (!converted) return OGL_OK;
+    std::vector<int32_t> bad((size_t)nl + 1);
+    OGL_HIP_CHECK(hipMemcpyAsync(bad.data(), M.bad.p, bad.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    OGL_HIP_CHECK(hipStreamSynchronize(st));
+    for (int l = 0; l <= nl; ++l) {  // (the fine level's coefficients first, then level by level)
+        if (bad[(size_t)l] == MG_NONE_BAD) continue;
+        int64_t row = bad[(size_t)l];
+        if (l == 0) {
+            fp32_dev.epoch = 0;
+            OGL_TRY(fp32_bad_row(bad[0], &row));
+            row = std::max<int64_t>(0, std::min<int64_t>(row, (int64_t)pat.n_rows - 1));
+        }
+        M.twin_of = 0;
+        return fail(OGL_ERR_INVALID,
+                    "preconditioner Multigrid: cyclePrecision single: a coefficient or the inverse diagonal of row %lld of "
+                    "level %d%s is finite in double precision and not in single precision",
+                    (long long)row, l == 0 ? 0 : l - 1, l <= 1 ? " (caller's numbering)" : "");
+    }
+    M.twin_of = M.generated;
     return OGL_OK;
 }
 
@@ -275,6 +346,7 @@ int ogl_solver::generate_multigrid(PrecondData &P)
         if (k + 1 < M.n_levels) props["mgPasses" + std::to_string(k)] = (double)M.levels[(size_t)k]->passes;
     }
     props["mgOperatorComplexity"] = M.levels[0]->nnz > 0 ? total / (double)M.levels[0]->nnz : 1.0;
+    ++M.generated;  // (the levels' binary32 twin, if there is one, is that of the generation before)
     return OGL_OK;
 }
 
@@ -391,6 +463,129 @@ void ogl_solver::mg_cycle(int level, const double *b, double *x, const DevScalar
     }
 }
 
+// Level 0's product in single precision with its epilogue (kernels_mixed.hip): on the fp32 twin of the half storage's
+// planes where that is the in-loop layout, else on the fp32 value array beside the device CSR.
+void ogl_solver::mg_fine32(MxEpilogue epi, const float *x, const MgEpi &e)
+{
+    if (fp32_dev.half)
+        launch_mg_fine_sym(reg->stream, sym(), fp32_dev.planes.p, epi, x, e);
+    else
+        launch_mg_fine_csr(reg->stream, csr(false), fp32_dev.vals.p, epi, x, e);
+}
+
+// mg_cycle on binary32 operands (cyclePrecision single): the same steps in the same order on the levels' twin and fp32
+// vectors.  Level 0 (in64 != nullptr) reads the fp64 residual in64 -- b = fl32(in64) is formed by its first pre-sweep -- and
+// its last post-sweep writes out64 as doubles; its products, where it is the system matrix in the in-loop layout, carry
+// the sweep or the residual as their epilogue, so no elementwise pass follows a product.
+void ogl_solver::mg_cycle32(int level, const float *b, float *x, const double *in64, double *out64, const DevScalars *gate,
+                            int &launches, bool continued)
+{
+    hipStream_t st = reg->stream;
+    const MultigridPart &M = precond_data->mg;
+    MgLevel &L = *M.levels[(size_t)level];
+    const int32_t n = L.n;
+    if (level >= mg_tail_first) {  // (never level 0: apply_multigrid)
+        MgTail32 T;
+        T.count = M.n_levels - level;
+        T.cg_iters = M.cg_iters;
+        T.coarse_visits = mg_coarse_visits;
+        T.continued = continued ? 1 : 0;
+        for (int k = 0; k < T.count; ++k) {
+            const MgLevel &S = *M.levels[(size_t)(level + k)];
+            MgTailLevelOf<float> &D = T.lev[k];
+            D.n = S.n;
+            D.n_coarse = S.n_coarse;
+            D.row_ptrs = S.row_ptrs.p;
+            D.cols = S.cols.p;
+            D.vals = S.vals32.p;
+            D.inv_d = S.inv_d32.p;
+            D.agg = S.agg.p;
+            D.agg_ptr = S.agg_ptr.p;
+            D.agg_rows = S.agg_rows.p;
+            D.b = S.b32.p;
+            D.xa = S.xa32.p;
+            D.xb = S.xb32.p;
+            D.t = S.t32.p;
+            D.r = S.r32.p;
+            D.p = S.p32.p;
+            D.part = S.part.p;
+        }
+        launch_mg_tail(st, T, b, x, gate);
+        ++launches;
+        return;
+    }
+    const bool fine = in64 && !L.own;  // level 0 as the system matrix in the in-loop layout
+    MgEpi e;
+    e.b = b;
+    e.inv_d = L.inv_d32.p;
+    e.gate = gate;
+    if (level == M.n_levels - 1) {
+        // the coarsest solver; its sums are wide (fp64 products of the casts) in the loop's tree
+        MgScalars *sc = M.scal.p;
+        const int n_part = (int)n_chunks(n);
+        launch_mg_cg_init(st, n, b, in64, L.r32.p, x, L.p32.p, gate);
+        ++launches;
+        for (int it = 0; it < M.cg_iters; ++it) {
+            launch_mg_wide_dot(st, n, L.r32.p, L.r32.p, L.part.p, gate);
+            launch_mg_cg_fin(st, L.part.p, n_part, 0, it == 0, sc, gate);
+            launch_mg_cg_step1(st, n, L.p32.p, L.r32.p, sc, gate);
+            if (fine) {
+                e.out = L.t32.p;
+                mg_fine32(MX_EPI_PLAIN, L.p32.p, e);
+            } else {
+                launch_mg_csr_spmv(st, L.view32(), L.p32.p, L.t32.p, gate);
+            }
+            launch_mg_wide_dot(st, n, L.p32.p, L.t32.p, L.part.p, gate);
+            launch_mg_cg_fin(st, L.part.p, n_part, 1, 0, sc, gate);
+            launch_mg_cg_step2(st, n, x, L.r32.p, L.p32.p, L.t32.p, sc, gate);
+            launches += 7;
+        }
+        if (in64) {  // (a hierarchy of one level)
+            launch_mg_widen(st, n, x, out64, gate);
+            ++launches;
+        }
+        return;
+    }
+    MgLevel &C = *M.levels[(size_t)level + 1];
+    const MgCsr32 A = L.view32();
+    // 2 pre-sweeps, residual and restriction
+    if (in64)
+        launch_mg_jacobi0_in(st, n, in64, L.inv_d32.p, L.b32.p, L.xa32.p, gate);
+    else if (continued)
+        launch_mg_csr_sweep(st, A, L.inv_d32.p, b, x, nullptr, nullptr, L.xa32.p, nullptr, gate);
+    else
+        launch_mg_jacobi0(st, n, b, L.inv_d32.p, L.xa32.p, gate);
+    if (fine) {
+        e.out = L.xb32.p;
+        mg_fine32(MX_EPI_SWEEP, L.xa32.p, e);
+        e.out = L.t32.p;
+        mg_fine32(MX_EPI_RESIDUAL, L.xb32.p, e);
+        launch_mg_restrict(st, C.n, L.agg_ptr.p, L.agg_rows.p, A, b, L.xb32.p, L.t32.p, C.b32.p, gate);
+        launches += 4;
+    } else {
+        launch_mg_csr_sweep(st, A, L.inv_d32.p, b, L.xa32.p, nullptr, nullptr, L.xb32.p, nullptr, gate);
+        launch_mg_restrict(st, C.n, L.agg_ptr.p, L.agg_rows.p, A, b, L.xb32.p, nullptr, C.b32.p, gate);
+        launches += 3;
+    }
+    mg_cycle32(level + 1, C.b32.p, C.xb32.p, nullptr, nullptr, gate, launches, false);
+    if (level + 2 < M.n_levels)
+        for (int visit = 1; visit < mg_coarse_visits; ++visit)
+            mg_cycle32(level + 1, C.b32.p, C.xb32.p, nullptr, nullptr, gate, launches, true);
+    // correction and 2 post-sweeps
+    if (fine) {
+        launch_mg_prolong(st, n, L.xb32.p, C.xb32.p, L.agg.p, L.xa32.p, gate);
+        e.out = L.xb32.p;
+        mg_fine32(MX_EPI_SWEEP, L.xa32.p, e);
+        e.out64 = out64;
+        mg_fine32(MX_EPI_SWEEP64, L.xb32.p, e);
+        launches += 3;
+    } else {
+        launch_mg_csr_sweep(st, A, L.inv_d32.p, b, L.xb32.p, C.xb32.p, L.agg.p, L.xa32.p, nullptr, gate);
+        launch_mg_csr_sweep(st, A, L.inv_d32.p, b, L.xa32.p, nullptr, nullptr, in64 ? nullptr : x, out64, gate);
+        launches += 2;
+    }
+}
+
 void ogl_solver::apply_multigrid(const double *in, double *out, const DevScalars *gate, double *dot_part)
 {
     int launches = 0;
@@ -402,9 +597,22 @@ void ogl_solver::apply_multigrid(const double *in, double *out, const DevScalars
     while (mg_tail_first > 0 && M.n_levels - mg_tail_first < MG_TAIL_MAX_LEVELS &&
            (double)M.levels[(size_t)mg_tail_first - 1]->n <= tail_rows)
         --mg_tail_first;
+    // (single precision: level 0 arrives and leaves in fp64 and takes its products from the in-loop layout's fp32 copy --
+    //  it is launched, whatever its size)
+    if (mg_single && mg_tail_first < 1) mg_tail_first = 1;
     props["mgTailLevels"] = (double)(M.n_levels - mg_tail_first);
     props["mgTailRows"] = tail_rows;
-    if (pat.renumbered()) {  // (the vectors carried into the caller's order and back, as apply_factor does)
+    if (mg_single) {
+        MgLevel &L0 = *M.levels[0];
+        if (pat.renumbered()) {
+            launch_factor_gather_perm(reg->stream, pat.n_rows, d_new_id.p, in, M.in.p, gate);
+            mg_cycle32(0, L0.b32.p, L0.xb32.p, M.in.p, M.out.p, gate, launches, false);
+            launch_factor_scatter_perm(reg->stream, pat.n_rows, d_new_id.p, M.out.p, out, gate);
+            launches += 2;
+        } else {
+            mg_cycle32(0, L0.b32.p, L0.xb32.p, in, out, gate, launches, false);
+        }
+    } else if (pat.renumbered()) {  // (the vectors carried into the caller's order and back, as apply_factor does)
         launch_factor_gather_perm(reg->stream, pat.n_rows, d_new_id.p, in, M.in.p, gate);
         mg_cycle(0, M.in.p, M.out.p, gate, launches, false);
         launch_factor_scatter_perm(reg->stream, pat.n_rows, d_new_id.p, M.out.p, out, gate);

@@ -76,6 +76,20 @@ void ogl_solver::mixed_spmv(const float *x, float *y, double *part, const MixedS
         launch_mixed_spmv_csr(reg->stream, csr(false), fp32_dev.vals.p, x, y, part, gate);
 }
 
+// The device row that holds position `position` of fp32_dev's value array (the planes' twin or the CSR values).
+int ogl_solver::fp32_bad_row(int64_t position, int64_t *row) const
+{
+    if (fp32_dev.half) {
+        const int64_t per_chunk = (int64_t)sym_dev.nd * CHUNK_ROWS;
+        *row = (position / per_chunk) * CHUNK_ROWS + position % CHUNK_ROWS;
+        return OGL_OK;
+    }
+    std::vector<int32_t> rp((size_t)pat.n_rows + 1);
+    OGL_HIP_CHECK(hipMemcpy(rp.data(), d_row_ptrs.p, rp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    *row = (int64_t)(std::upper_bound(rp.begin(), rp.end(), position) - rp.begin()) - 1;
+    return OGL_OK;
+}
+
 // A coefficient or an inverse diagonal that is finite in fp64 and not in binary32: the solve fails and names the row
 // (the caller's numbering).  The copy is marked stale, so that the next call converts -- and reports -- again.
 int ogl_solver::mixed_overflow(const MixedScalars &m)
@@ -84,14 +98,7 @@ int ogl_solver::mixed_overflow(const MixedScalars &m)
     fp32_dev.epoch = 0;
     const bool coef = m.bad_coef != INT_MAX;
     int64_t row = m.bad_invd;
-    if (coef && fp32_dev.half) {
-        const int64_t per_chunk = (int64_t)sym_dev.nd * CHUNK_ROWS;
-        row = (m.bad_coef / per_chunk) * CHUNK_ROWS + m.bad_coef % CHUNK_ROWS;
-    } else if (coef) {
-        std::vector<int32_t> rp((size_t)pat.n_rows + 1);
-        OGL_HIP_CHECK(hipMemcpy(rp.data(), d_row_ptrs.p, rp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        row = (int64_t)(std::upper_bound(rp.begin(), rp.end(), m.bad_coef) - rp.begin()) - 1;
-    }
+    if (coef) OGL_TRY(fp32_bad_row(m.bad_coef, &row));
     row = std::max<int64_t>(0, std::min<int64_t>(row, (int64_t)pat.n_rows - 1));
     if (pat.renumbered() && (size_t)row < pat.old_of.size()) row = pat.old_of[(size_t)row];
     return fail(OGL_ERR_INVALID, "mixedPrecision: %s of row %lld is finite in double precision and not in single precision",
