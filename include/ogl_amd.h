@@ -70,7 +70,10 @@ typedef enum {
      * of the last three is OGL_ERR_INVALID, and a hierarchy on which coarseVisits makes more than 4096 level visits per
      * apply fails the solve with OGL_ERR_UNSUPPORTED.  cyclePrecision (0 = double; 1 = single: the cycle on binary32
      * operands, the hierarchy still generated and handed out in fp64; any other value is OGL_ERR_INVALID, and so is a
-     * coefficient or inverse diagonal of a level that is finite in fp64 and not in binary32).  Read-only after a solve:
+     * coefficient or inverse diagonal of a level that is finite in fp64 and not in binary32).  smootherSweeps (2; 1 ... 4
+     * sweeps before and after the coarse correction on every level) and correctionScale (1.0; the factor on every
+     * prolongated correction, finite and inside (0, 2)): any other value is OGL_ERR_INVALID naming keyword and value; both
+     * belong to the solver that applies the hierarchy, like coarseVisits and cyclePrecision.  Read-only after a solve:
      * mgLevels, mgRows<l>, mgNnz<l>, mgPasses<l>, mgVisits<l>, mgOperatorComplexity, mgCyclePrecisionInUse (0 | 1). */
     OGL_PRECOND_MULTIGRID = 7
 } ogl_precond_kind;

@@ -21,7 +21,7 @@ PRECOND_IC, PRECOND_ILU, PRECOND_IRILU = 4, 5, 6
 PRECOND_MULTIGRID = 7
 # keywords of the Multigrid sub-dictionary (Preconditioner.H:297-317): they travel as properties; cycle as a number
 MG_KEYWORDS = ("maxLevels", "minCoarseRows", "coarseSolverIters", "cycle", "zeroGuess", "aggregation", "aggregatePasses",
-               "coarseVisits", "cyclePrecision")
+               "coarseVisits", "cyclePrecision", "smootherSweeps", "correctionScale")
 MG_CYCLE = {"v": 0, "w": 1, "f": 2}
 MG_AGGREGATION = {"pgm": 0, "hashed": 1}
 MG_CYCLE_PRECISION = {"double": 0, "single": 1}
@@ -398,7 +398,8 @@ class Solver:
 
     def set_multigrid(self, **kw):
         """The Multigrid keywords (MG_KEYWORDS; cycle as 'v' | 'w' | 'f', aggregation as 'pgm' | 'hashed', cyclePrecision as
-        'double' | 'single' -- each also as its number --, zeroGuess as a bool) for the next solves."""
+        'double' | 'single' -- each also as its number --, zeroGuess as a bool, smootherSweeps 1 .. 4 and correctionScale in
+        (0, 2) as numbers) for the next solves."""
         for k, v in kw.items():
             if k not in MG_KEYWORDS:
                 raise KeyError(k)

@@ -360,6 +360,8 @@ struct MgScalars {                // the coarsest level's CG
 // every level below the first, the coarsest excepted, is visited that often per visit of its parent -- the first visit from
 // nothing, the others continued from the answer before with the same right-hand side.  The first level has one visit per
 // launch; continued != 0: that visit starts from what x holds (the launcher's own revisit of it) instead of from nothing.
+// sweeps (keyword smootherSweeps, 1 .. 4): sweeps before and after the coarse correction on every level; scale (keyword
+// correctionScale): the factor on every prolongated correction, held as a double and rounded to T in the kernel.
 template <class T>
 struct MgTailLevelOf {
     int32_t n = 0, n_coarse = 0;
@@ -373,10 +375,12 @@ constexpr int MG_TAIL_MAX_LEVELS = 16;
 constexpr int MG_TAIL_DEFAULT_ROWS = 512;  // property mgTailRows
 constexpr int MG_TAIL_MAX_ROWS = 1024 * 512;  // (the finaliser's tree inside the workgroup: one partial per virtual thread)
 constexpr int MG_MAX_COARSE_VISITS = 3;     // keyword coarseVisits (k_mg_tail counts a level's visits in two bits)
+constexpr int MG_MAX_SWEEPS = 4;            // keyword smootherSweeps: sweeps before and after the coarse correction
 constexpr int MG_MAX_VISITS_PER_APPLY = 4096;  // level visits of one apply, summed over the levels: beyond it the solve is refused
 template <class T>
 struct MgTailOf {
-    int32_t count = 0, cg_iters = 0, coarse_visits = 1, continued = 0;
+    int32_t count = 0, cg_iters = 0, coarse_visits = 1, continued = 0, sweeps = 2;
+    double scale = 1.0;
     MgTailLevelOf<T> lev[MG_TAIL_MAX_LEVELS];
 };
 using MgTail = MgTailOf<double>;
@@ -408,15 +412,15 @@ hipError_t mg_sort_rows(hipStream_t st, void *temp, size_t temp_bytes, const int
                         const int32_t *rows, int32_t *rows_out, int32_t n);
 hipError_t mg_sort_entries(hipStream_t st, void *temp, size_t temp_bytes, const unsigned long long *keys,
                            unsigned long long *keys_out, const double *vals, double *vals_out, int32_t m);
-// apply: x = omega (b inv_d) | x_out = x + omega ((b - ax) inv_d) | x_out = x + xc[agg]
+// apply: x = omega (b inv_d) | x_out = x + omega ((b - ax) inv_d) | x_out = x + scale xc[agg]
 void launch_mg_jacobi0(hipStream_t st, int32_t n, const double *b, const double *inv_d, double *x, const DevScalars *gate);
 void launch_mg_sweep_epi(hipStream_t st, int32_t n, const double *b, const double *ax, const double *inv_d, const double *x,
                          double *x_out, const DevScalars *gate);
-void launch_mg_prolong(hipStream_t st, int32_t n, const double *x, const double *xc, const int32_t *agg, double *x_out,
-                       const DevScalars *gate);
-// one sweep on a CSR level (x_out != x); xc != nullptr: on t = x + xc[agg], the prolongation folded in
+void launch_mg_prolong(hipStream_t st, int32_t n, const double *x, const double *xc, const int32_t *agg, double scale,
+                       double *x_out, const DevScalars *gate);
+// one sweep on a CSR level (x_out != x); xc != nullptr: on t = x + scale xc[agg], the prolongation folded in
 void launch_mg_csr_sweep(hipStream_t st, const MgCsr &A, const double *inv_d, const double *b, const double *x,
-                         const double *xc, const int32_t *agg, double *x_out, const DevScalars *gate);
+                         const double *xc, const int32_t *agg, double scale, double *x_out, const DevScalars *gate);
 void launch_mg_csr_spmv(hipStream_t st, const MgCsr &A, const double *x, double *y, const DevScalars *gate);
 // bc[I] = sum of b_i - (A x)_i over the members of I, ascending; ax != nullptr: the products are there already
 void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsr &A,
@@ -439,11 +443,12 @@ void launch_mg_twin(hipStream_t st, const MgCsr &A, const double *inv_d, float *
 void launch_mg_jacobi0_in(hipStream_t st, int32_t n, const double *r, const float *inv_d, float *b, float *x,
                           const DevScalars *gate);
 void launch_mg_jacobi0(hipStream_t st, int32_t n, const float *b, const float *inv_d, float *x, const DevScalars *gate);
-void launch_mg_prolong(hipStream_t st, int32_t n, const float *x, const float *xc, const int32_t *agg, float *x_out,
-                       const DevScalars *gate);
+void launch_mg_prolong(hipStream_t st, int32_t n, const float *x, const float *xc, const int32_t *agg, float scale,
+                       float *x_out, const DevScalars *gate);
 // x_out64 != nullptr: the sweep's result is written there as doubles (level 0's last post-sweep) instead of x_out
 void launch_mg_csr_sweep(hipStream_t st, const MgCsr32 &A, const float *inv_d, const float *b, const float *x,
-                         const float *xc, const int32_t *agg, float *x_out, double *x_out64, const DevScalars *gate);
+                         const float *xc, const int32_t *agg, float scale, float *x_out, double *x_out64,
+                         const DevScalars *gate);
 void launch_mg_csr_spmv(hipStream_t st, const MgCsr32 &A, const float *x, float *y, const DevScalars *gate);
 // res != nullptr: bc[I] = sum of res_i (the residuals another kernel has formed); else of b_i - (A x)_i
 void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsr32 &A,

@@ -293,23 +293,24 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_sweep_epi(int n, const double *
     if (i < n) x_out[i] = x[i] + MG_OMEGA * ((b[i] - ax[i]) * inv_d[i]);
 }
 
+// x_out = x + scale xc[agg] (keyword correctionScale; the product rounded once, then the sum)
 template <class T>
 __global__ __launch_bounds__(MG_BLOCK) void k_mg_prolong(int n, const T *__restrict__ x, const T *__restrict__ xc,
-                                                         const int32_t *__restrict__ agg, T *__restrict__ x_out,
+                                                         const int32_t *__restrict__ agg, T scale, T *__restrict__ x_out,
                                                          const DevScalars *gate)
 {
     MG_GATE();
     const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
-    if (i < n) x_out[i] = x[i] + xc[agg[i]];
+    if (i < n) x_out[i] = x[i] + scale * xc[agg[i]];
 }
 
-// one sweep on a CSR level, x_out != x; xc != nullptr: the sweep reads t_j = x_j + xc[agg[j]] (the prolongation folded in);
+// one sweep on a CSR level, x_out != x; xc != nullptr: the sweep reads t_j = x_j + scale xc[agg[j]] (the prolongation folded in);
 // TO: the type the result is stored as (double: level 0's last post-sweep of the single-precision cycle writes z)
 template <class T, class TO, bool PROLONG>
 __global__ __launch_bounds__(MG_BLOCK) void k_mg_csr_sweep(MgCsrOf<T> A, const T *__restrict__ inv_d,
                                                            const T *__restrict__ b, const T *__restrict__ x,
                                                            const T *__restrict__ xc, const int32_t *__restrict__ agg,
-                                                           TO *__restrict__ x_out, const DevScalars *gate)
+                                                           T scale, TO *__restrict__ x_out, const DevScalars *gate)
 {
     MG_GATE();
     const int i = blockIdx.x * MG_BLOCK + threadIdx.x;
@@ -318,11 +319,11 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_csr_sweep(MgCsrOf<T> A, const T
     for (int k = A.row_ptrs[i]; k < A.row_ptrs[i + 1]; ++k) {
         const int j = A.cols[k];
         T t = x[j];
-        if (PROLONG) t = t + xc[agg[j]];
+        if (PROLONG) t = t + scale * xc[agg[j]];
         s += A.vals[k] * t;
     }
     T ti = x[i];
-    if (PROLONG) ti = ti + xc[agg[i]];
+    if (PROLONG) ti = ti + scale * xc[agg[i]];
     x_out[i] = (TO)(ti + (T)MG_OMEGA * ((b[i] - s) * inv_d[i]));
 }
 
@@ -451,26 +452,26 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_cg_step2(int n, T *__restrict__
 // bytes).  The same operations in the same order as the kernels above, hence the same bits.
 // ------------------------------------------------------------------------------------------
 template <class T>
-__device__ __forceinline__ T tail_row_product(const MgTailLevelOf<T> &L, int i, const T *x, const T *xc)
+__device__ __forceinline__ T tail_row_product(const MgTailLevelOf<T> &L, int i, const T *x, const T *xc, T scale)
 {
     T s = 0;
     for (int k = L.row_ptrs[i]; k < L.row_ptrs[i + 1]; ++k) {
         const int j = L.cols[k];
         T t = x[j];
-        if (xc) t = t + xc[L.agg[j]];
+        if (xc) t = t + scale * xc[L.agg[j]];
         s += L.vals[k] * t;
     }
     return s;
 }
 
-// x_out = t + omega ((b - A t) inv_d), t = x (+ xc[agg]); x_out != x
+// x_out = t + omega ((b - A t) inv_d), t = x (+ scale xc[agg]); x_out != x
 template <class T>
-__device__ __forceinline__ void tail_sweep(const MgTailLevelOf<T> &L, const T *b, const T *x, const T *xc, T *x_out)
+__device__ __forceinline__ void tail_sweep(const MgTailLevelOf<T> &L, const T *b, const T *x, const T *xc, T scale, T *x_out)
 {
     for (int i = threadIdx.x; i < L.n; i += BLOCK) {
-        const T s = tail_row_product(L, i, x, xc);
+        const T s = tail_row_product(L, i, x, xc, scale);
         T ti = x[i];
-        if (xc) ti = ti + xc[L.agg[i]];
+        if (xc) ti = ti + scale * xc[L.agg[i]];
         x_out[i] = ti + (T)MG_OMEGA * ((b[i] - s) * L.inv_d[i]);
     }
     __syncthreads();
@@ -512,32 +513,43 @@ __device__ __forceinline__ double tail_dot(int n, const T *a, const T *b, double
 // <= 3).  Both are the same in every thread, so every barrier is reached by the whole workgroup.  The first of the tail's
 // levels is visited once per launch -- from nothing, or continued from the x_out of the launch before (T.continued); the
 // levels below it coarse_visits times per visit of their parent, the coarsest once.
+// A visit runs Tl.sweeps (keyword smootherSweeps) sweeps down and as many up.  x ping-pongs between the level's xa and xb so
+// that no sweep writes the vector it reads: the first pre-sweep writes xa, so the last one leaves x in xa for an odd count
+// and in xb for an even one; the post-sweeps go on alternating from there, which makes the last of them write xb (the
+// tail's first level: x_out) whatever the count.  The count and the scale are the same in every thread.
 template <class T>
 __global__ __launch_bounds__(BLOCK) void k_mg_tail(MgTailOf<T> Tl, const T *b_in, T *x_out, const DevScalars *gate)
 {
     __shared__ double lds[2 * FIN_WAVES];
     MG_GATE();
     const int last = Tl.count - 1;
+    const int nu = Tl.sweeps;
+    const T scale = (T)Tl.scale;
     uint32_t seen = 0;
     int l = 0;
     bool continued = Tl.continued != 0;
     for (;;) {
-        if (l < last) {  // ---- down: the 2 pre-sweeps, residual and restriction of one visit of level l ----
+        if (l < last) {  // ---- down: the pre-sweeps, residual and restriction of one visit of level l ----
             const MgTailLevelOf<T> &L = Tl.lev[l];
             const T *b = l == 0 ? b_in : L.b;
             if (continued) {
-                tail_sweep<T>(L, b, l == 0 ? x_out : L.xb, nullptr, L.xa);
+                tail_sweep<T>(L, b, l == 0 ? x_out : L.xb, nullptr, scale, L.xa);
             } else {
                 for (int i = threadIdx.x; i < L.n; i += BLOCK) L.xa[i] = (T)MG_OMEGA * (b[i] * L.inv_d[i]);
                 __syncthreads();
             }
-            tail_sweep<T>(L, b, L.xa, nullptr, L.xb);
+            const T *cur = L.xa;
+            for (int k = 1; k < nu; ++k) {
+                T *const next = cur == L.xa ? L.xb : L.xa;
+                tail_sweep<T>(L, b, cur, nullptr, scale, next);
+                cur = next;
+            }
             T *bc = Tl.lev[l + 1].b;
             for (int I = threadIdx.x; I < L.n_coarse; I += BLOCK) {
                 T acc = 0;
                 for (int m = L.agg_ptr[I]; m < L.agg_ptr[I + 1]; ++m) {
                     const int i = L.agg_rows[m];
-                    acc += b[i] - tail_row_product<T>(L, i, L.xb, nullptr);
+                    acc += b[i] - tail_row_product<T>(L, i, cur, nullptr, scale);
                 }
                 bc[I] = acc;
             }
@@ -564,7 +576,7 @@ __global__ __launch_bounds__(BLOCK) void k_mg_tail(MgTailOf<T> Tl, const T *b_in
                 const T tmp = (T)((prev == 0.0) ? 0.0 : rho / prev);
                 for (int i = threadIdx.x; i < L.n; i += BLOCK) L.p[i] = L.r[i] + tmp * L.p[i];
                 __syncthreads();
-                for (int i = threadIdx.x; i < L.n; i += BLOCK) L.t[i] = tail_row_product<T>(L, i, L.p, nullptr);
+                for (int i = threadIdx.x; i < L.n; i += BLOCK) L.t[i] = tail_row_product<T>(L, i, L.p, nullptr, scale);
                 __syncthreads();
                 const double beta = tail_dot<T>(L.n, L.p, L.t, L.part, lds);
                 if (beta != 0.0) {
@@ -577,14 +589,18 @@ __global__ __launch_bounds__(BLOCK) void k_mg_tail(MgTailOf<T> Tl, const T *b_in
                 __syncthreads();
             }
         }
-        // ---- up: correction and 2 post-sweeps, level by level, until a level is due another visit ----
+        // ---- up: the scaled correction and the post-sweeps, level by level, until a level is due another visit ----
         for (;;) {
             if (l == 0) return;
             --l;
             const MgTailLevelOf<T> &L = Tl.lev[l];
             const T *b = l == 0 ? b_in : L.b;
-            tail_sweep<T>(L, b, L.xb, Tl.lev[l + 1].xb, L.xa);
-            tail_sweep<T>(L, b, L.xa, nullptr, l == 0 ? x_out : L.xb);
+            const T *cur = (nu & 1) ? L.xa : L.xb;  // (what the last pre-sweep wrote)
+            for (int k = 0; k < nu; ++k) {
+                T *const next = k == nu - 1 ? (l == 0 ? x_out : L.xb) : (cur == L.xa ? L.xb : L.xa);
+                tail_sweep<T>(L, b, cur, k == 0 ? Tl.lev[l + 1].xb : nullptr, scale, next);
+                cur = next;
+            }
             if (l == 0) return;
             const uint32_t had = (seen >> (2 * l)) & 3u;
             if ((int)had < Tl.coarse_visits) {  // (same b, continued from the level's xb)
@@ -681,18 +697,18 @@ void launch_mg_sweep_epi(hipStream_t st, int32_t n, const double *b, const doubl
 {
     MG_LAUNCH(k_mg_sweep_epi, n, n, b, ax, inv_d, x, x_out, gate);
 }
-void launch_mg_prolong(hipStream_t st, int32_t n, const double *x, const double *xc, const int32_t *agg, double *x_out,
-                       const DevScalars *gate)
+void launch_mg_prolong(hipStream_t st, int32_t n, const double *x, const double *xc, const int32_t *agg, double scale,
+                       double *x_out, const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_prolong<double>, n, n, x, xc, agg, x_out, gate);
+    MG_LAUNCH(k_mg_prolong<double>, n, n, x, xc, agg, scale, x_out, gate);
 }
 void launch_mg_csr_sweep(hipStream_t st, const MgCsr &A, const double *inv_d, const double *b, const double *x,
-                         const double *xc, const int32_t *agg, double *x_out, const DevScalars *gate)
+                         const double *xc, const int32_t *agg, double scale, double *x_out, const DevScalars *gate)
 {
     if (xc)
-        MG_LAUNCH((k_mg_csr_sweep<double, double, true>), A.n, A, inv_d, b, x, xc, agg, x_out, gate);
+        MG_LAUNCH((k_mg_csr_sweep<double, double, true>), A.n, A, inv_d, b, x, xc, agg, scale, x_out, gate);
     else
-        MG_LAUNCH((k_mg_csr_sweep<double, double, false>), A.n, A, inv_d, b, x, xc, agg, x_out, gate);
+        MG_LAUNCH((k_mg_csr_sweep<double, double, false>), A.n, A, inv_d, b, x, xc, agg, scale, x_out, gate);
 }
 void launch_mg_csr_spmv(hipStream_t st, const MgCsr &A, const double *x, double *y, const DevScalars *gate)
 {
@@ -744,22 +760,23 @@ void launch_mg_jacobi0(hipStream_t st, int32_t n, const float *b, const float *i
 {
     MG_LAUNCH(k_mg_jacobi0<float>, n, n, b, inv_d, x, gate);
 }
-void launch_mg_prolong(hipStream_t st, int32_t n, const float *x, const float *xc, const int32_t *agg, float *x_out,
-                       const DevScalars *gate)
+void launch_mg_prolong(hipStream_t st, int32_t n, const float *x, const float *xc, const int32_t *agg, float scale,
+                       float *x_out, const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_prolong<float>, n, n, x, xc, agg, x_out, gate);
+    MG_LAUNCH(k_mg_prolong<float>, n, n, x, xc, agg, scale, x_out, gate);
 }
 void launch_mg_csr_sweep(hipStream_t st, const MgCsr32 &A, const float *inv_d, const float *b, const float *x,
-                         const float *xc, const int32_t *agg, float *x_out, double *x_out64, const DevScalars *gate)
+                         const float *xc, const int32_t *agg, float scale, float *x_out, double *x_out64,
+                         const DevScalars *gate)
 {
     if (x_out64 && xc)
-        MG_LAUNCH((k_mg_csr_sweep<float, double, true>), A.n, A, inv_d, b, x, xc, agg, x_out64, gate);
+        MG_LAUNCH((k_mg_csr_sweep<float, double, true>), A.n, A, inv_d, b, x, xc, agg, scale, x_out64, gate);
     else if (x_out64)
-        MG_LAUNCH((k_mg_csr_sweep<float, double, false>), A.n, A, inv_d, b, x, xc, agg, x_out64, gate);
+        MG_LAUNCH((k_mg_csr_sweep<float, double, false>), A.n, A, inv_d, b, x, xc, agg, scale, x_out64, gate);
     else if (xc)
-        MG_LAUNCH((k_mg_csr_sweep<float, float, true>), A.n, A, inv_d, b, x, xc, agg, x_out, gate);
+        MG_LAUNCH((k_mg_csr_sweep<float, float, true>), A.n, A, inv_d, b, x, xc, agg, scale, x_out, gate);
     else
-        MG_LAUNCH((k_mg_csr_sweep<float, float, false>), A.n, A, inv_d, b, x, xc, agg, x_out, gate);
+        MG_LAUNCH((k_mg_csr_sweep<float, float, false>), A.n, A, inv_d, b, x, xc, agg, scale, x_out, gate);
 }
 void launch_mg_csr_spmv(hipStream_t st, const MgCsr32 &A, const float *x, float *y, const DevScalars *gate)
 {

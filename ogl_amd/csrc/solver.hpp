@@ -527,6 +527,8 @@ struct ogl_solver {
     void mg_cycle(int level, const double *b, double *x, const ogl::DevScalars *gate, int &launches, bool continued);
     int prepare_multigrid_apply();
     int mg_coarse_visits = 1;  // keyword coarseVisits as this solver's applies use it (prepare_multigrid_apply)
+    int mg_sweeps = 2;         // keyword smootherSweeps, likewise: sweeps before and after the coarse correction
+    double mg_scale = 1.0;     // keyword correctionScale, likewise: the factor on every prolongated correction
     // keyword cyclePrecision as this solver's applies use it: the cycle on binary32 operands
     bool mg_single = false;
     int prepare_multigrid_single();  // the levels' twin, the fine level's fp32 copy, the vectors; the overflow check

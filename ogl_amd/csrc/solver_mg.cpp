@@ -1,7 +1,8 @@
 // solver_mg.cpp -- preconditioner Multigrid (Preconditioner.H:259-341): generation of the aggregation hierarchy on the
 // device, one V-cycle as the apply (coarseVisits > 1: every coarse level but the coarsest visited that often per visit of
-// its parent; cyclePrecision single: on binary32 operands), and the entry points that hand the hierarchy out.  Kernels: kernels_mg.hip; the contract: DESIGN.md
-// section 7b.
+// its parent; cyclePrecision single: on binary32 operands; smootherSweeps sweeps before and after the coarse correction,
+// which is scaled by correctionScale), and the entry points that hand the hierarchy out.  Kernels: kernels_mg.hip; the
+// contract: DESIGN.md section 7b.
 #include "solver_internal.hpp"
 
 #include <algorithm>
@@ -54,6 +55,13 @@ int ogl_solver::check_multigrid_keywords()
     if (precision != 0.0 && precision != 1.0)
         return fail(OGL_ERR_INVALID, "preconditioner Multigrid: cyclePrecision %g is neither 0 (double) nor 1 (single)",
                     precision);
+    const double sweeps = prop("smootherSweeps", 2.0);
+    if (!(sweeps >= 1.0 && sweeps <= (double)MG_MAX_SWEEPS) || sweeps != (double)(int)sweeps)
+        return fail(OGL_ERR_INVALID, "preconditioner Multigrid: smootherSweeps %g outside [1, %d]", sweeps, MG_MAX_SWEEPS);
+    // (a condition, not a tuning value: with an exact coarse solve the correction step I - scale Pi stops contracting at 2)
+    const double scale = prop("correctionScale", 1.0);
+    if (!(scale > 0.0 && scale < 2.0))
+        return fail(OGL_ERR_INVALID, "preconditioner Multigrid: correctionScale %g outside (0, 2)", scale);
     return OGL_OK;
 }
 
@@ -65,6 +73,15 @@ int ogl_solver::prepare_multigrid_apply()
     const MultigridPart &M = precond_data->mg;
     mg_coarse_visits = (int)prop("coarseVisits", 1.0);
     props["coarseVisits"] = (double)mg_coarse_visits;
+    // smootherSweeps and correctionScale are the applier's too; check_multigrid_keywords has refused the rest, and an
+    // apply never runs with a count the ping-pong of the sweeps was not built for
+    mg_sweeps = (int)prop("smootherSweeps", 2.0);
+    mg_scale = prop("correctionScale", 1.0);
+    if (mg_sweeps < 1 || mg_sweeps > MG_MAX_SWEEPS || !(mg_scale > 0.0 && mg_scale < 2.0))
+        return fail(OGL_ERR_INVALID, "preconditioner Multigrid: smootherSweeps %d outside [1, %d] or correctionScale %g outside (0, 2)",
+                    mg_sweeps, MG_MAX_SWEEPS, mg_scale);
+    props["smootherSweeps"] = (double)mg_sweeps;
+    props["correctionScale"] = mg_scale;
     std::vector<double> visits((size_t)M.n_levels, 1.0);
     double total = 0.0;
     for (int l = 0; l < M.n_levels; ++l) {
@@ -374,6 +391,8 @@ void ogl_solver::mg_cycle(int level, const double *b, double *x, const DevScalar
         T.cg_iters = M.cg_iters;
         T.coarse_visits = mg_coarse_visits;
         T.continued = continued ? 1 : 0;
+        T.sweeps = mg_sweeps;
+        T.scale = mg_scale;
         for (int k = 0; k < T.count; ++k) {
             const MgLevel &S = *M.levels[(size_t)(level + k)];
             MgTailLevel &D = T.lev[k];
@@ -425,41 +444,61 @@ void ogl_solver::mg_cycle(int level, const double *b, double *x, const DevScalar
     }
     const MgLevel &C = *M.levels[(size_t)level + 1];
     const MgCsr A = L.view();
-    // 2 pre-sweeps (the first from x = 0: no product; of a continued visit: a full sweep from x), residual and restriction
+    // smootherSweeps pre-sweeps (the first from x = 0: no product; of a continued visit: a full sweep from x), residual and
+    // restriction.  x ping-pongs between xa and xb (no sweep writes the vector it reads): the first pre-sweep writes xa, so
+    // `cur`, what the last one wrote and the restriction reads, is xa for an odd count and xb for an even one.
+    const int nu = mg_sweeps;
+    const double scale = mg_scale;
+    double *cur = L.xa.p;
+    const auto other = [&L](const double *v) { return v == L.xa.p ? L.xb.p : L.xa.p; };
     if (continued)
-        launch_mg_csr_sweep(st, A, L.inv_d.p, b, x, nullptr, nullptr, L.xa.p, gate);
+        launch_mg_csr_sweep(st, A, L.inv_d.p, b, x, nullptr, nullptr, scale, cur, gate);
     else
-        launch_mg_jacobi0(st, n, b, L.inv_d.p, L.xa.p, gate);
+        launch_mg_jacobi0(st, n, b, L.inv_d.p, cur, gate);
+    ++launches;
     const bool layout = !L.own;  // (level 0 in the caller's numbering: products on the in-loop layout, sweeps behind them)
     if (layout) {
-        mg_product(0, L.xa.p, L.t.p, gate);
-        launch_mg_sweep_epi(st, n, b, L.t.p, L.inv_d.p, L.xa.p, L.xb.p, gate);
-        mg_product(0, L.xb.p, L.t.p, gate);
-        launch_mg_restrict(st, C.n, L.agg_ptr.p, L.agg_rows.p, A, b, L.xb.p, L.t.p, C.b.p, gate);
-        launches += 5;
+        for (int k = 1; k < nu; ++k, cur = other(cur)) {
+            mg_product(0, cur, L.t.p, gate);
+            launch_mg_sweep_epi(st, n, b, L.t.p, L.inv_d.p, cur, other(cur), gate);
+            launches += 2;
+        }
+        mg_product(0, cur, L.t.p, gate);
+        launch_mg_restrict(st, C.n, L.agg_ptr.p, L.agg_rows.p, A, b, cur, L.t.p, C.b.p, gate);
+        launches += 2;
     } else {
-        launch_mg_csr_sweep(st, A, L.inv_d.p, b, L.xa.p, nullptr, nullptr, L.xb.p, gate);
-        launch_mg_restrict(st, C.n, L.agg_ptr.p, L.agg_rows.p, A, b, L.xb.p, nullptr, C.b.p, gate);
-        launches += 3;
+        for (int k = 1; k < nu; ++k, cur = other(cur)) {
+            launch_mg_csr_sweep(st, A, L.inv_d.p, b, cur, nullptr, nullptr, scale, other(cur), gate);
+            ++launches;
+        }
+        launch_mg_restrict(st, C.n, L.agg_ptr.p, L.agg_rows.p, A, b, cur, nullptr, C.b.p, gate);
+        ++launches;
     }
     // the coarse correction lands in the coarse level's xb (its last post-sweep writes there; the coarsest CG too); the
     // visits after the first continue from there with the same C.b
     mg_cycle(level + 1, C.b.p, C.xb.p, gate, launches, false);
     if (level + 2 < M.n_levels)
         for (int visit = 1; visit < mg_coarse_visits; ++visit) mg_cycle(level + 1, C.b.p, C.xb.p, gate, launches, true);
-    // correction and 2 post-sweeps
+    // the scaled correction and smootherSweeps post-sweeps, the last of them into x (level 0: the caller's vector; below
+    // it the level's xb, where the alternation lands whatever the count)
     if (layout) {
-        launch_mg_prolong(st, n, L.xb.p, C.xb.p, L.agg.p, L.xa.p, gate);
-        mg_product(0, L.xa.p, L.t.p, gate);
-        launch_mg_sweep_epi(st, n, b, L.t.p, L.inv_d.p, L.xa.p, L.xb.p, gate);
-        mg_product(0, L.xb.p, L.t.p, gate);
-        launch_mg_sweep_epi(st, n, b, L.t.p, L.inv_d.p, L.xb.p, x, gate);
-        launches += 5;
+        launch_mg_prolong(st, n, cur, C.xb.p, L.agg.p, scale, other(cur), gate);
+        cur = other(cur);
+        ++launches;
+        for (int k = 0; k < nu; ++k, cur = other(cur)) {
+            mg_product(0, cur, L.t.p, gate);
+            launch_mg_sweep_epi(st, n, b, L.t.p, L.inv_d.p, cur, k == nu - 1 ? x : other(cur), gate);
+            launches += 2;
+        }
     } else {
-        // (the prolongation folded into the first post-sweep: t_j = x_j + x_c[agg(j)], rounded once)
-        launch_mg_csr_sweep(st, A, L.inv_d.p, b, L.xb.p, C.xb.p, L.agg.p, L.xa.p, gate);
-        launch_mg_csr_sweep(st, A, L.inv_d.p, b, L.xa.p, nullptr, nullptr, x, gate);
-        launches += 2;
+        // (the prolongation folded into the first post-sweep: t_j = x_j + scale x_c[agg(j)], product and sum rounded once each)
+        for (int k = 0; k < nu; ++k, cur = other(cur)) {
+            if (k == 0)
+                launch_mg_csr_sweep(st, A, L.inv_d.p, b, cur, C.xb.p, L.agg.p, scale, k == nu - 1 ? x : other(cur), gate);
+            else
+                launch_mg_csr_sweep(st, A, L.inv_d.p, b, cur, nullptr, nullptr, scale, k == nu - 1 ? x : other(cur), gate);
+            ++launches;
+        }
     }
 }
 
@@ -490,6 +529,8 @@ void ogl_solver::mg_cycle32(int level, const float *b, float *x, const double *i
         T.cg_iters = M.cg_iters;
         T.coarse_visits = mg_coarse_visits;
         T.continued = continued ? 1 : 0;
+        T.sweeps = mg_sweeps;
+        T.scale = mg_scale;
         for (int k = 0; k < T.count; ++k) {
             const MgLevel &S = *M.levels[(size_t)(level + k)];
             MgTailLevelOf<float> &D = T.lev[k];
@@ -548,41 +589,60 @@ void ogl_solver::mg_cycle32(int level, const float *b, float *x, const double *i
     }
     MgLevel &C = *M.levels[(size_t)level + 1];
     const MgCsr32 A = L.view32();
-    // 2 pre-sweeps, residual and restriction
+    // smootherSweeps pre-sweeps, residual and restriction; the buffers by parity as in mg_cycle
+    const int nu = mg_sweeps;
+    const float scale = (float)mg_scale;  // (fl32 of the keyword's value)
+    float *cur = L.xa32.p;
+    const auto other = [&L](const float *v) { return v == L.xa32.p ? L.xb32.p : L.xa32.p; };
     if (in64)
-        launch_mg_jacobi0_in(st, n, in64, L.inv_d32.p, L.b32.p, L.xa32.p, gate);
+        launch_mg_jacobi0_in(st, n, in64, L.inv_d32.p, L.b32.p, cur, gate);
     else if (continued)
-        launch_mg_csr_sweep(st, A, L.inv_d32.p, b, x, nullptr, nullptr, L.xa32.p, nullptr, gate);
+        launch_mg_csr_sweep(st, A, L.inv_d32.p, b, x, nullptr, nullptr, scale, cur, nullptr, gate);
     else
-        launch_mg_jacobi0(st, n, b, L.inv_d32.p, L.xa32.p, gate);
+        launch_mg_jacobi0(st, n, b, L.inv_d32.p, cur, gate);
+    ++launches;
     if (fine) {
-        e.out = L.xb32.p;
-        mg_fine32(MX_EPI_SWEEP, L.xa32.p, e);
+        for (int k = 1; k < nu; ++k, cur = other(cur)) {
+            e.out = other(cur);
+            mg_fine32(MX_EPI_SWEEP, cur, e);
+            ++launches;
+        }
         e.out = L.t32.p;
-        mg_fine32(MX_EPI_RESIDUAL, L.xb32.p, e);
-        launch_mg_restrict(st, C.n, L.agg_ptr.p, L.agg_rows.p, A, b, L.xb32.p, L.t32.p, C.b32.p, gate);
-        launches += 4;
+        mg_fine32(MX_EPI_RESIDUAL, cur, e);
+        launch_mg_restrict(st, C.n, L.agg_ptr.p, L.agg_rows.p, A, b, cur, L.t32.p, C.b32.p, gate);
+        launches += 2;
     } else {
-        launch_mg_csr_sweep(st, A, L.inv_d32.p, b, L.xa32.p, nullptr, nullptr, L.xb32.p, nullptr, gate);
-        launch_mg_restrict(st, C.n, L.agg_ptr.p, L.agg_rows.p, A, b, L.xb32.p, nullptr, C.b32.p, gate);
-        launches += 3;
+        for (int k = 1; k < nu; ++k, cur = other(cur)) {
+            launch_mg_csr_sweep(st, A, L.inv_d32.p, b, cur, nullptr, nullptr, scale, other(cur), nullptr, gate);
+            ++launches;
+        }
+        launch_mg_restrict(st, C.n, L.agg_ptr.p, L.agg_rows.p, A, b, cur, nullptr, C.b32.p, gate);
+        ++launches;
     }
     mg_cycle32(level + 1, C.b32.p, C.xb32.p, nullptr, nullptr, gate, launches, false);
     if (level + 2 < M.n_levels)
         for (int visit = 1; visit < mg_coarse_visits; ++visit)
             mg_cycle32(level + 1, C.b32.p, C.xb32.p, nullptr, nullptr, gate, launches, true);
-    // correction and 2 post-sweeps
+    // the scaled correction and smootherSweeps post-sweeps; the last of them writes x, or (level 0) out64 as doubles
     if (fine) {
-        launch_mg_prolong(st, n, L.xb32.p, C.xb32.p, L.agg.p, L.xa32.p, gate);
-        e.out = L.xb32.p;
-        mg_fine32(MX_EPI_SWEEP, L.xa32.p, e);
-        e.out64 = out64;
-        mg_fine32(MX_EPI_SWEEP64, L.xb32.p, e);
-        launches += 3;
+        launch_mg_prolong(st, n, cur, C.xb32.p, L.agg.p, scale, other(cur), gate);
+        cur = other(cur);
+        ++launches;
+        for (int k = 0; k < nu; ++k, cur = other(cur)) {
+            const bool end = k == nu - 1;
+            e.out = end ? nullptr : other(cur);
+            e.out64 = end ? out64 : nullptr;
+            mg_fine32(end ? MX_EPI_SWEEP64 : MX_EPI_SWEEP, cur, e);
+            ++launches;
+        }
     } else {
-        launch_mg_csr_sweep(st, A, L.inv_d32.p, b, L.xb32.p, C.xb32.p, L.agg.p, L.xa32.p, nullptr, gate);
-        launch_mg_csr_sweep(st, A, L.inv_d32.p, b, L.xa32.p, nullptr, nullptr, in64 ? nullptr : x, out64, gate);
-        launches += 2;
+        for (int k = 0; k < nu; ++k, cur = other(cur)) {
+            const bool end = k == nu - 1;
+            float *const dst = end ? (in64 ? nullptr : x) : other(cur);
+            launch_mg_csr_sweep(st, A, L.inv_d32.p, b, cur, k == 0 ? C.xb32.p : nullptr, k == 0 ? L.agg.p : nullptr, scale, dst,
+                                end ? out64 : nullptr, gate);
+            ++launches;
+        }
     }
 }
 
