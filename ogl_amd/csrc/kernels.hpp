@@ -346,8 +346,7 @@ struct MgCsrOf {  // one matrix of the hierarchy: columns ascending per row
     const int32_t *row_ptrs = nullptr, *cols = nullptr;
     const T *vals = nullptr;
 };
-using MgCsr = MgCsrOf<double>;
-using MgCsr32 = MgCsrOf<float>;  // keyword cyclePrecision single: the binary32 twin of a level, on the same index arrays
+using MgCsr = MgCsrOf<double>;  // (MgCsrOf<float>, keyword cyclePrecision single: binary32 values on the same index arrays)
 constexpr double MG_OMEGA = 0.9;  // the smoother's relaxation factor
 constexpr int MG_ROUNDS = 15;     // matching rounds per coarsening
 constexpr int MG_MAX_PASSES = 4;  // keyword aggregatePasses: pairwise coarsenings per kept level
@@ -370,7 +369,6 @@ struct MgTailLevelOf {
     T *b = nullptr, *xa = nullptr, *xb = nullptr, *t = nullptr, *r = nullptr, *p = nullptr;
     double *part = nullptr;  // (the partials of the coarsest CG's sums are doubles in either precision)
 };
-using MgTailLevel = MgTailLevelOf<double>;
 constexpr int MG_TAIL_MAX_LEVELS = 16;
 constexpr int MG_TAIL_DEFAULT_ROWS = 512;  // property mgTailRows
 constexpr int MG_TAIL_MAX_ROWS = 1024 * 512;  // (the finaliser's tree inside the workgroup: one partial per virtual thread)
@@ -383,10 +381,8 @@ struct MgTailOf {
     double scale = 1.0;
     MgTailLevelOf<T> lev[MG_TAIL_MAX_LEVELS];
 };
-using MgTail = MgTailOf<double>;
-using MgTail32 = MgTailOf<float>;
-void launch_mg_tail(hipStream_t st, const MgTail &T, const double *b, double *x, const DevScalars *gate);
-void launch_mg_tail(hipStream_t st, const MgTail32 &T, const float *b, float *x, const DevScalars *gate);
+template <class T>
+void launch_mg_tail(hipStream_t st, const MgTailOf<T> &Tl, const T *b, T *x, const DevScalars *gate);
 // generation: diag[i] = A(i, i), inv_d[i] = 1 / A(i, i) (inv_d nullptr: not wanted)
 void launch_mg_diag(hipStream_t st, const MgCsr &A, double *diag, double *inv_d);
 // s[i] = strongest unaggregated (want 0) / aggregated (want 1) neighbour of the unaggregated row i (-1 none, -2 row aggregated);
@@ -412,54 +408,53 @@ hipError_t mg_sort_rows(hipStream_t st, void *temp, size_t temp_bytes, const int
                         const int32_t *rows, int32_t *rows_out, int32_t n);
 hipError_t mg_sort_entries(hipStream_t st, void *temp, size_t temp_bytes, const unsigned long long *keys,
                            unsigned long long *keys_out, const double *vals, double *vals_out, int32_t m);
-// apply: x = omega (b inv_d) | x_out = x + omega ((b - ax) inv_d) | x_out = x + scale xc[agg]
-void launch_mg_jacobi0(hipStream_t st, int32_t n, const double *b, const double *inv_d, double *x, const DevScalars *gate);
+// apply.  The launchers of the cycle's kernels are templates over the operand type T, instantiated for double and for float
+// (keyword cyclePrecision single, DESIGN.md section 7b, "the cycle in single precision": the same kernels on binary32
+// operands with binary32 operations; the scalars of the coarsest CG stay doubles, formed from wide sums -- products of the
+// float64 casts in the loop's tree -- and rounded once where a vector kernel takes them).  What only one precision has a
+// kernel for is refused by an assert in the launcher.
+// x = omega (b inv_d) | x_out = x + omega ((b - ax) inv_d) | x_out = x + scale xc[agg]
+template <class T>
+void launch_mg_jacobi0(hipStream_t st, int32_t n, const T *b, const T *inv_d, T *x, const DevScalars *gate);
 void launch_mg_sweep_epi(hipStream_t st, int32_t n, const double *b, const double *ax, const double *inv_d, const double *x,
                          double *x_out, const DevScalars *gate);
-void launch_mg_prolong(hipStream_t st, int32_t n, const double *x, const double *xc, const int32_t *agg, double scale,
-                       double *x_out, const DevScalars *gate);
-// one sweep on a CSR level (x_out != x); xc != nullptr: on t = x + scale xc[agg], the prolongation folded in
-void launch_mg_csr_sweep(hipStream_t st, const MgCsr &A, const double *inv_d, const double *b, const double *x,
-                         const double *xc, const int32_t *agg, double scale, double *x_out, const DevScalars *gate);
-void launch_mg_csr_spmv(hipStream_t st, const MgCsr &A, const double *x, double *y, const DevScalars *gate);
-// bc[I] = sum of b_i - (A x)_i over the members of I, ascending; ax != nullptr: the products are there already
-void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsr &A,
-                        const double *b, const double *x, const double *ax, double *bc, const DevScalars *gate);
-void launch_mg_cg_init(hipStream_t st, int32_t n, const double *b, double *r, double *x, double *p, const DevScalars *gate);
+template <class T>
+void launch_mg_prolong(hipStream_t st, int32_t n, const T *x, const T *xc, const int32_t *agg, T scale, T *x_out,
+                       const DevScalars *gate);
+// one sweep on a CSR level (x_out != x); xc != nullptr: on t = x + scale xc[agg], the prolongation folded in;
+// x_out64 != nullptr (float only): the result is written there as doubles (level 0's last post-sweep) instead of x_out
+template <class T>
+void launch_mg_csr_sweep(hipStream_t st, const MgCsrOf<T> &A, const T *inv_d, const T *b, const T *x, const T *xc,
+                         const int32_t *agg, T scale, T *x_out, double *x_out64, const DevScalars *gate);
+template <class T>
+void launch_mg_csr_spmv(hipStream_t st, const MgCsrOf<T> &A, const T *x, T *y, const DevScalars *gate);
+// bc[I] = sum of r_i = b_i - (A x)_i over the members of I, ascending.  from: MG_FROM_A the kernel forms the products
+// itself (src unused), MG_FROM_AX src holds A x (double only), MG_FROM_RES src holds the residuals r (float only)
+enum MgRestrictFrom { MG_FROM_A = 0, MG_FROM_AX = 1, MG_FROM_RES = 2 };
+template <class T>
+void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsrOf<T> &A,
+                        const T *b, const T *x, MgRestrictFrom from, const T *src, T *bc, const DevScalars *gate);
+// r = b, x = p = 0; b64 != nullptr (float only): r = fl32(b64) (a hierarchy of one level: the CG runs on the fp64
+// residual's rounding)
+template <class T>
+void launch_mg_cg_init(hipStream_t st, int32_t n, const T *b, const double *b64, T *r, T *x, T *p, const DevScalars *gate);
 // what 0: prev_rho <- rho (1 when first), rho <- sum(part); 1: beta <- sum(part) -- in the finaliser's tree
 void launch_mg_cg_fin(hipStream_t st, const double *part, int32_t n_part, int what, int first, MgScalars *s,
                       const DevScalars *gate);
-void launch_mg_cg_step1(hipStream_t st, int32_t n, double *p, const double *r, const MgScalars *s, const DevScalars *gate);
-void launch_mg_cg_step2(hipStream_t st, int32_t n, double *x, double *r, const double *p, const double *q,
-                        const MgScalars *s, const DevScalars *gate);
-// --- keyword cyclePrecision single ("the cycle in single precision"): the same kernels on binary32
-// operands with binary32 operations; the scalars of the coarsest CG stay doubles, formed from wide sums (products of the
-// float64 casts in the loop's tree) and rounded once where a vector kernel takes them ---
+template <class T>
+void launch_mg_cg_step1(hipStream_t st, int32_t n, T *p, const T *r, const MgScalars *s, const DevScalars *gate);
+template <class T>
+void launch_mg_cg_step2(hipStream_t st, int32_t n, T *x, T *r, const T *p, const T *q, const MgScalars *s,
+                        const DevScalars *gate);
+// --- what only the cycle in single precision launches ---
 constexpr int32_t MG_NONE_BAD = 0x7f7f7f7f;  // an overflow word nothing has lowered (set by a byte fill)
-// the twin of one level: vals32 = fl32(A.vals) (nullptr: the level keeps no matrix of its own), inv_d32 = fl32(inv_d);
-// *bad = the smallest row with a value that is finite in fp64 and not in binary32
+// the float operands of one level: vals32 = fl32(A.vals) (nullptr: the level keeps no matrix of its own), inv_d32 =
+// fl32(inv_d); *bad = the smallest row with a value that is finite in fp64 and not in binary32
 void launch_mg_twin(hipStream_t st, const MgCsr &A, const double *inv_d, float *vals32, float *inv_d32, int32_t *bad);
 // level 0's first pre-sweep from the fp64 residual: b = fl32(r), x = omega32 (b inv_d)
 void launch_mg_jacobi0_in(hipStream_t st, int32_t n, const double *r, const float *inv_d, float *b, float *x,
                           const DevScalars *gate);
-void launch_mg_jacobi0(hipStream_t st, int32_t n, const float *b, const float *inv_d, float *x, const DevScalars *gate);
-void launch_mg_prolong(hipStream_t st, int32_t n, const float *x, const float *xc, const int32_t *agg, float scale,
-                       float *x_out, const DevScalars *gate);
-// x_out64 != nullptr: the sweep's result is written there as doubles (level 0's last post-sweep) instead of x_out
-void launch_mg_csr_sweep(hipStream_t st, const MgCsr32 &A, const float *inv_d, const float *b, const float *x,
-                         const float *xc, const int32_t *agg, float scale, float *x_out, double *x_out64,
-                         const DevScalars *gate);
-void launch_mg_csr_spmv(hipStream_t st, const MgCsr32 &A, const float *x, float *y, const DevScalars *gate);
-// res != nullptr: bc[I] = sum of res_i (the residuals another kernel has formed); else of b_i - (A x)_i
-void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsr32 &A,
-                        const float *b, const float *x, const float *res, float *bc, const DevScalars *gate);
-// b64 != nullptr: r = fl32(b64) (a hierarchy of one level: the CG runs on the fp64 residual's rounding)
-void launch_mg_cg_init(hipStream_t st, int32_t n, const float *b, const double *b64, float *r, float *x, float *p,
-                       const DevScalars *gate);
 void launch_mg_wide_dot(hipStream_t st, int32_t n, const float *a, const float *b, double *part, const DevScalars *gate);
-void launch_mg_cg_step1(hipStream_t st, int32_t n, float *p, const float *r, const MgScalars *s, const DevScalars *gate);
-void launch_mg_cg_step2(hipStream_t st, int32_t n, float *x, float *r, const float *p, const float *q,
-                        const MgScalars *s, const DevScalars *gate);
 void launch_mg_widen(hipStream_t st, int32_t n, const float *x, double *out, const DevScalars *gate);
 
 // renumbering (keyword `renumber`): host vectors arrive in the caller's cell order

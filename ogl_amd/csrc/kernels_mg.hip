@@ -8,6 +8,9 @@
 // (run_sum); the coarse matrices have one entry per column.
 #include <hipcub/hipcub.hpp>
 
+#include <cassert>
+#include <type_traits>
+
 #include "device_common.hpp"
 
 namespace ogl {
@@ -340,8 +343,7 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_csr_spmv(MgCsrOf<T> A, const T 
 }
 
 // b_c[I] = sum over the members i of I, ascending, of r_i = b_i - (A x)_i; FROM: MG_FROM_AX the products come from `ax`,
-// MG_FROM_RES the residuals themselves do
-enum { MG_FROM_A = 0, MG_FROM_AX = 1, MG_FROM_RES = 2 };
+// MG_FROM_RES the residuals themselves do (MgRestrictFrom, kernels.hpp)
 template <class T, int FROM>
 __global__ __launch_bounds__(MG_BLOCK) void k_mg_restrict(int nc, const int32_t *__restrict__ agg_ptr,
                                                           const int32_t *__restrict__ agg_rows, MgCsrOf<T> A,
@@ -688,65 +690,115 @@ hipError_t mg_sort_entries(hipStream_t st, void *temp, size_t temp_bytes, const 
     return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys, keys_out, vals, vals_out, m, 0, 64, st);
 }
 
-void launch_mg_jacobi0(hipStream_t st, int32_t n, const double *b, const double *inv_d, double *x, const DevScalars *gate)
+// ---- the cycle's kernels: one launcher per kernel template, instantiated for double and float below.  Only the kernel
+//      instantiations the cycles use exist: what has none is refused by an assert ----
+template <class T>
+constexpr bool mg_is_float = std::is_same<T, float>::value;
+
+template <class T>
+void launch_mg_jacobi0(hipStream_t st, int32_t n, const T *b, const T *inv_d, T *x, const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_jacobi0<double>, n, n, b, inv_d, x, gate);
+    MG_LAUNCH(k_mg_jacobi0<T>, n, n, b, inv_d, x, gate);
 }
 void launch_mg_sweep_epi(hipStream_t st, int32_t n, const double *b, const double *ax, const double *inv_d, const double *x,
                          double *x_out, const DevScalars *gate)
 {
     MG_LAUNCH(k_mg_sweep_epi, n, n, b, ax, inv_d, x, x_out, gate);
 }
-void launch_mg_prolong(hipStream_t st, int32_t n, const double *x, const double *xc, const int32_t *agg, double scale,
-                       double *x_out, const DevScalars *gate)
+template <class T>
+void launch_mg_prolong(hipStream_t st, int32_t n, const T *x, const T *xc, const int32_t *agg, T scale, T *x_out,
+                       const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_prolong<double>, n, n, x, xc, agg, scale, x_out, gate);
+    MG_LAUNCH(k_mg_prolong<T>, n, n, x, xc, agg, scale, x_out, gate);
 }
-void launch_mg_csr_sweep(hipStream_t st, const MgCsr &A, const double *inv_d, const double *b, const double *x,
-                         const double *xc, const int32_t *agg, double scale, double *x_out, const DevScalars *gate)
+template <class T>
+void launch_mg_csr_sweep(hipStream_t st, const MgCsrOf<T> &A, const T *inv_d, const T *b, const T *x, const T *xc,
+                         const int32_t *agg, T scale, T *x_out, double *x_out64, const DevScalars *gate)
 {
+    if constexpr (mg_is_float<T>) {
+        if (x_out64) {
+            if (xc)
+                MG_LAUNCH((k_mg_csr_sweep<float, double, true>), A.n, A, inv_d, b, x, xc, agg, scale, x_out64, gate);
+            else
+                MG_LAUNCH((k_mg_csr_sweep<float, double, false>), A.n, A, inv_d, b, x, xc, agg, scale, x_out64, gate);
+            return;
+        }
+    }
+    assert(!x_out64);
     if (xc)
-        MG_LAUNCH((k_mg_csr_sweep<double, double, true>), A.n, A, inv_d, b, x, xc, agg, scale, x_out, gate);
+        MG_LAUNCH((k_mg_csr_sweep<T, T, true>), A.n, A, inv_d, b, x, xc, agg, scale, x_out, gate);
     else
-        MG_LAUNCH((k_mg_csr_sweep<double, double, false>), A.n, A, inv_d, b, x, xc, agg, scale, x_out, gate);
+        MG_LAUNCH((k_mg_csr_sweep<T, T, false>), A.n, A, inv_d, b, x, xc, agg, scale, x_out, gate);
 }
-void launch_mg_csr_spmv(hipStream_t st, const MgCsr &A, const double *x, double *y, const DevScalars *gate)
+template <class T>
+void launch_mg_csr_spmv(hipStream_t st, const MgCsrOf<T> &A, const T *x, T *y, const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_csr_spmv<double>, A.n, A, x, y, gate);
+    MG_LAUNCH(k_mg_csr_spmv<T>, A.n, A, x, y, gate);
 }
-void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsr &A,
-                        const double *b, const double *x, const double *ax, double *bc, const DevScalars *gate)
+template <class T>
+void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsrOf<T> &A,
+                        const T *b, const T *x, MgRestrictFrom from, const T *src, T *bc, const DevScalars *gate)
 {
-    if (ax)
-        MG_LAUNCH((k_mg_restrict<double, MG_FROM_AX>), nc, nc, agg_ptr, agg_rows, A, b, x, ax, bc, gate);
+    // (what stands behind a product of the in-loop layout: A x in double precision, the residual in single precision)
+    constexpr MgRestrictFrom behind = mg_is_float<T> ? MG_FROM_RES : MG_FROM_AX;
+    assert(from == MG_FROM_A || from == behind);
+    if (from == behind)
+        MG_LAUNCH((k_mg_restrict<T, behind>), nc, nc, agg_ptr, agg_rows, A, b, x, src, bc, gate);
     else
-        MG_LAUNCH((k_mg_restrict<double, MG_FROM_A>), nc, nc, agg_ptr, agg_rows, A, b, x, ax, bc, gate);
+        MG_LAUNCH((k_mg_restrict<T, MG_FROM_A>), nc, nc, agg_ptr, agg_rows, A, b, x, src, bc, gate);
 }
-void launch_mg_cg_init(hipStream_t st, int32_t n, const double *b, double *r, double *x, double *p, const DevScalars *gate)
+template <class T>
+void launch_mg_cg_init(hipStream_t st, int32_t n, const T *b, const double *b64, T *r, T *x, T *p, const DevScalars *gate)
 {
-    MG_LAUNCH((k_mg_cg_init<double, double>), n, n, b, r, x, p, gate);
+    if constexpr (mg_is_float<T>) {
+        if (b64) {
+            MG_LAUNCH((k_mg_cg_init<float, double>), n, n, b64, r, x, p, gate);
+            return;
+        }
+    }
+    assert(!b64);
+    MG_LAUNCH((k_mg_cg_init<T, T>), n, n, b, r, x, p, gate);
 }
 void launch_mg_cg_fin(hipStream_t st, const double *part, int32_t n_part, int what, int first, MgScalars *s,
                       const DevScalars *gate)
 {
     hipLaunchKernelGGL(k_mg_cg_fin, dim3(1), dim3(FIN_BLOCK), 0, st, part, n_part, what, first, s, gate);
 }
-void launch_mg_cg_step1(hipStream_t st, int32_t n, double *p, const double *r, const MgScalars *s, const DevScalars *gate)
+template <class T>
+void launch_mg_cg_step1(hipStream_t st, int32_t n, T *p, const T *r, const MgScalars *s, const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_cg_step1<double>, n, n, p, r, s, gate);
+    MG_LAUNCH(k_mg_cg_step1<T>, n, n, p, r, s, gate);
 }
-void launch_mg_cg_step2(hipStream_t st, int32_t n, double *x, double *r, const double *p, const double *q,
-                        const MgScalars *s, const DevScalars *gate)
+template <class T>
+void launch_mg_cg_step2(hipStream_t st, int32_t n, T *x, T *r, const T *p, const T *q, const MgScalars *s,
+                        const DevScalars *gate)
 {
-    MG_LAUNCH(k_mg_cg_step2<double>, n, n, x, r, p, q, s, gate);
+    MG_LAUNCH(k_mg_cg_step2<T>, n, n, x, r, p, q, s, gate);
+}
+template <class T>
+void launch_mg_tail(hipStream_t st, const MgTailOf<T> &Tl, const T *b, T *x, const DevScalars *gate)
+{
+    hipLaunchKernelGGL(k_mg_tail<T>, dim3(1), dim3(BLOCK), 0, st, Tl, b, x, gate);
 }
 
-void launch_mg_tail(hipStream_t st, const MgTail &T, const double *b, double *x, const DevScalars *gate)
-{
-    hipLaunchKernelGGL(k_mg_tail<double>, dim3(1), dim3(BLOCK), 0, st, T, b, x, gate);
-}
+#define MG_INSTANTIATE(T)                                                                                                      \
+    template void launch_mg_jacobi0<T>(hipStream_t, int32_t, const T *, const T *, T *, const DevScalars *);                   \
+    template void launch_mg_prolong<T>(hipStream_t, int32_t, const T *, const T *, const int32_t *, T, T *, const DevScalars *); \
+    template void launch_mg_csr_sweep<T>(hipStream_t, const MgCsrOf<T> &, const T *, const T *, const T *, const T *,          \
+                                         const int32_t *, T, T *, double *, const DevScalars *);                               \
+    template void launch_mg_csr_spmv<T>(hipStream_t, const MgCsrOf<T> &, const T *, T *, const DevScalars *);                  \
+    template void launch_mg_restrict<T>(hipStream_t, int32_t, const int32_t *, const int32_t *, const MgCsrOf<T> &, const T *, \
+                                        const T *, MgRestrictFrom, const T *, T *, const DevScalars *);                        \
+    template void launch_mg_cg_init<T>(hipStream_t, int32_t, const T *, const double *, T *, T *, T *, const DevScalars *);    \
+    template void launch_mg_cg_step1<T>(hipStream_t, int32_t, T *, const T *, const MgScalars *, const DevScalars *);          \
+    template void launch_mg_cg_step2<T>(hipStream_t, int32_t, T *, T *, const T *, const T *, const MgScalars *,               \
+                                        const DevScalars *);                                                                   \
+    template void launch_mg_tail<T>(hipStream_t, const MgTailOf<T> &, const T *, T *, const DevScalars *);
+MG_INSTANTIATE(double)
+MG_INSTANTIATE(float)
+#undef MG_INSTANTIATE
 
-// ---- cyclePrecision single ----
+// ---- what only the cycle in single precision launches ----
 void launch_mg_twin(hipStream_t st, const MgCsr &A, const double *inv_d, float *vals32, float *inv_d32, int32_t *bad)
 {
     MG_LAUNCH(k_mg_twin, A.n, A, inv_d, vals32, inv_d32, bad);
@@ -756,70 +808,15 @@ void launch_mg_jacobi0_in(hipStream_t st, int32_t n, const double *r, const floa
 {
     MG_LAUNCH(k_mg_jacobi0_in, n, n, r, inv_d, b, x, gate);
 }
-void launch_mg_jacobi0(hipStream_t st, int32_t n, const float *b, const float *inv_d, float *x, const DevScalars *gate)
-{
-    MG_LAUNCH(k_mg_jacobi0<float>, n, n, b, inv_d, x, gate);
-}
-void launch_mg_prolong(hipStream_t st, int32_t n, const float *x, const float *xc, const int32_t *agg, float scale,
-                       float *x_out, const DevScalars *gate)
-{
-    MG_LAUNCH(k_mg_prolong<float>, n, n, x, xc, agg, scale, x_out, gate);
-}
-void launch_mg_csr_sweep(hipStream_t st, const MgCsr32 &A, const float *inv_d, const float *b, const float *x,
-                         const float *xc, const int32_t *agg, float scale, float *x_out, double *x_out64,
-                         const DevScalars *gate)
-{
-    if (x_out64 && xc)
-        MG_LAUNCH((k_mg_csr_sweep<float, double, true>), A.n, A, inv_d, b, x, xc, agg, scale, x_out64, gate);
-    else if (x_out64)
-        MG_LAUNCH((k_mg_csr_sweep<float, double, false>), A.n, A, inv_d, b, x, xc, agg, scale, x_out64, gate);
-    else if (xc)
-        MG_LAUNCH((k_mg_csr_sweep<float, float, true>), A.n, A, inv_d, b, x, xc, agg, scale, x_out, gate);
-    else
-        MG_LAUNCH((k_mg_csr_sweep<float, float, false>), A.n, A, inv_d, b, x, xc, agg, scale, x_out, gate);
-}
-void launch_mg_csr_spmv(hipStream_t st, const MgCsr32 &A, const float *x, float *y, const DevScalars *gate)
-{
-    MG_LAUNCH(k_mg_csr_spmv<float>, A.n, A, x, y, gate);
-}
-void launch_mg_restrict(hipStream_t st, int32_t nc, const int32_t *agg_ptr, const int32_t *agg_rows, const MgCsr32 &A,
-                        const float *b, const float *x, const float *res, float *bc, const DevScalars *gate)
-{
-    if (res)
-        MG_LAUNCH((k_mg_restrict<float, MG_FROM_RES>), nc, nc, agg_ptr, agg_rows, A, b, x, res, bc, gate);
-    else
-        MG_LAUNCH((k_mg_restrict<float, MG_FROM_A>), nc, nc, agg_ptr, agg_rows, A, b, x, res, bc, gate);
-}
-void launch_mg_cg_init(hipStream_t st, int32_t n, const float *b, const double *b64, float *r, float *x, float *p,
-                       const DevScalars *gate)
-{
-    if (b64)
-        MG_LAUNCH((k_mg_cg_init<float, double>), n, n, b64, r, x, p, gate);
-    else
-        MG_LAUNCH((k_mg_cg_init<float, float>), n, n, b, r, x, p, gate);
-}
 void launch_mg_wide_dot(hipStream_t st, int32_t n, const float *a, const float *b, double *part, const DevScalars *gate)
 {
     const int nc = (n + CHUNK_ROWS - 1) / CHUNK_ROWS;
     if (nc == 0) return;
     hipLaunchKernelGGL(k_mg_wide_dot, dim3(nc), dim3(BLOCK), 0, st, n, a, b, part, gate);
 }
-void launch_mg_cg_step1(hipStream_t st, int32_t n, float *p, const float *r, const MgScalars *s, const DevScalars *gate)
-{
-    MG_LAUNCH(k_mg_cg_step1<float>, n, n, p, r, s, gate);
-}
-void launch_mg_cg_step2(hipStream_t st, int32_t n, float *x, float *r, const float *p, const float *q,
-                        const MgScalars *s, const DevScalars *gate)
-{
-    MG_LAUNCH(k_mg_cg_step2<float>, n, n, x, r, p, q, s, gate);
-}
 void launch_mg_widen(hipStream_t st, int32_t n, const float *x, double *out, const DevScalars *gate)
 {
     MG_LAUNCH(k_mg_widen, n, n, x, out, gate);
-}
-void launch_mg_tail(hipStream_t st, const MgTail32 &T, const float *b, float *x, const DevScalars *gate)
-{
-    hipLaunchKernelGGL(k_mg_tail<float>, dim3(1), dim3(BLOCK), 0, st, T, b, x, gate);
 }
 
 }  // namespace ogl

@@ -8,6 +8,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "comm.hpp"
@@ -19,6 +20,14 @@
 
 namespace ogl {
 
+// What a level of a Multigrid hierarchy holds once per precision of the cycle: the values (where the level keeps a matrix
+// of its own), 1 / diagonal, and the vectors -- right-hand side (levels >= 1), iterates, A x; r, p: the coarsest level's CG.
+template <class T>
+struct MgOperands {
+    DevBuf<T> vals, inv_d;
+    DevBuf<T> b, xa, xb, t, r, p;
+};
+
 // One matrix of a Multigrid hierarchy with what its V-cycle needs (kernels_mg.hip).  Level 0 is the system matrix itself:
 // it keeps no copy of it, only 1 / diagonal, the aggregates and the vectors.
 struct MgLevel {
@@ -28,35 +37,37 @@ struct MgLevel {
     // the hierarchy lives -- the products then run on it instead of the in-loop layout)
     bool own = true;
     DevBuf<int32_t> row_ptrs, cols;
-    DevBuf<double> vals, inv_d;
     DevBuf<int32_t> agg, agg_ptr, agg_rows;    // fine-to-coarse map, members per coarse row (ascending)
-    DevBuf<double> b, xa, xb, t, r, p;         // right-hand side (levels >= 1), iterates, A x; r, p: the coarsest level's CG
-    DevBuf<double> part;                       // ... its per-chunk partials
-    // keyword cyclePrecision single: the binary32 twin -- values (where the level keeps a matrix of
-    // its own) and 1 / d rounded from the doubles above, on the same index arrays -- and the level's vectors in binary32.
-    // Built by the first apply in single precision of a generated hierarchy (MultigridPart::twin_of); they only grow.
-    DevBuf<float> vals32, inv_d32;
-    DevBuf<float> b32, xa32, xb32, t32, r32, p32;
-    MgCsr32 view32() const
+    DevBuf<double> part;                       // the per-chunk partials of the coarsest CG's sums (doubles in either precision)
+    // dbl: what the generation makes.  flt (keyword cyclePrecision single): the binary32 twin -- values
+    // and 1 / d rounded from dbl's, on the same index arrays -- and the level's vectors in binary32.  Built by the first
+    // apply in single precision of a generated hierarchy (MultigridPart::twin_of); they only grow.
+    MgOperands<double> dbl;
+    MgOperands<float> flt;
+    template <class T>
+    const MgOperands<T> &ops() const
     {
-        MgCsr32 A;
-        A.n = n;
-        A.nnz = nnz;
-        A.row_ptrs = row_ptrs.p;
-        A.cols = cols.p;
-        A.vals = vals32.p;
-        return A;
+        if constexpr (std::is_same<T, double>::value) return dbl;
+        else return flt;
     }
-    MgCsr view() const
-    {
-        MgCsr A;
-        A.n = n;
-        A.nnz = nnz;
-        A.row_ptrs = row_ptrs.p;
-        A.cols = cols.p;
-        A.vals = vals.p;
-        return A;
-    }
+    template <class T>
+    MgCsrOf<T> view() const { return MgCsrOf<T>{n, nnz, row_ptrs.p, cols.p, ops<T>().vals.p}; }
+};
+
+// One apply of a hierarchy as the steps of its cycle see it: the gate of every launch, and how many there were (property
+// mgLaunchesPerApply).  A step gets the stream of a launch from next(), which counts it: the count is kept where the
+// launches are made.
+struct MgRun {
+    hipStream_t st = nullptr;
+    const DevScalars *gate = nullptr;
+    int launches = 0;
+    hipStream_t next() { return ++launches, st; }
+};
+// The fp64 ends of the cycle in single precision: level 0 reads the residual from `in` and writes z to `out` as doubles.
+// Empty for every other level, and in double precision (where level 0's b and x are those vectors themselves).
+struct MgWide {
+    const double *in = nullptr;
+    double *out = nullptr;
 };
 
 // The preconditioner kinds.  precond_kind_of is the only place that turns the configuration (the public OGL_PRECOND_*
@@ -523,8 +534,27 @@ struct ogl_solver {
     ogl::DevBuf<double> d_fac_tmp[3];  // IC / ILU / IRILU: vectors in the caller's order, IRILU's iterates
     // Multigrid: generation of the hierarchy (per-round and per-level sizes are the only host round trips) and one V-cycle
     int generate_multigrid(ogl::PrecondData &P);
+    int mg_caller_numbered_level0(ogl::PrecondData &P);  // a renumbered device copy: level 0's pattern in the caller's numbering
     void apply_multigrid(const double *in, double *out, const ogl::DevScalars *gate, double *dot_part);
-    void mg_cycle(int level, const double *b, double *x, const ogl::DevScalars *gate, int &launches, bool continued);
+    // the matrix a level really is: level 0 that keeps none of its own is the system matrix's CSR arrays (double; in single
+    // precision such a level has no CSR matrix, and nothing that needs one -- the tail -- is given level 0)
+    template <class T>
+    ogl::MgCsrOf<T> mg_matrix(const ogl::MgLevel &L) const;
+    // The cycle, one body for both operand types (instantiated for double and float in solver_mg.cpp).  What differs
+    // between them at level 0 is in the overloads below it; every step counts its launches in `run`.
+    template <class T>
+    void mg_cycle(int level, const T *b, T *x, const ogl::MgWide &ends, ogl::MgRun &run, bool continued);
+    template <class T>
+    ogl::MgTailOf<T> mg_tail_table(int first, bool continued) const;
+    // A x of a level: on its own CSR matrix, or (level 0 without one) on the in-loop layout, local part only
+    void mg_product(const ogl::MgLevel &L, const double *x, double *y, ogl::MgRun &run);
+    void mg_product(const ogl::MgLevel &L, const float *x, float *y, ogl::MgRun &run);
+    // one sweep of level 0 on the in-loop layout, x_out = x + omega ((b - A x) / d) (out64: written there as doubles)
+    void mg_layout_sweep(const ogl::MgLevel &L, const double *b, const double *x, double *x_out, double *out64, ogl::MgRun &run);
+    void mg_layout_sweep(const ogl::MgLevel &L, const float *b, const float *x, float *x_out, double *out64, ogl::MgRun &run);
+    // what the restriction of level 0 on the in-loop layout reads, left in the level's t; returns what it is
+    ogl::MgRestrictFrom mg_layout_residual(const ogl::MgLevel &L, const double *b, const double *x, ogl::MgRun &run);
+    ogl::MgRestrictFrom mg_layout_residual(const ogl::MgLevel &L, const float *b, const float *x, ogl::MgRun &run);
     int prepare_multigrid_apply();
     int mg_coarse_visits = 1;  // keyword coarseVisits as this solver's applies use it (prepare_multigrid_apply)
     int mg_sweeps = 2;         // keyword smootherSweeps, likewise: sweeps before and after the coarse correction
@@ -532,11 +562,8 @@ struct ogl_solver {
     // keyword cyclePrecision as this solver's applies use it: the cycle on binary32 operands
     bool mg_single = false;
     int prepare_multigrid_single();  // the levels' twin, the fine level's fp32 copy, the vectors; the overflow check
-    void mg_cycle32(int level, const float *b, float *x, const double *in64, double *out64, const ogl::DevScalars *gate,
-                    int &launches, bool continued);
-    void mg_fine32(ogl::MxEpilogue epi, const float *x, const ogl::MgEpi &e);  // level 0's product with its epilogue
-    // A x of a level (0: the system matrix on the in-loop layout, local part only)
-    void mg_product(int level, const double *x, double *y, const ogl::DevScalars *gate);
+    // level 0's product in single precision with its epilogue (one launch)
+    void mg_fine32(ogl::MxEpilogue epi, const float *x, const ogl::MgEpi &e, ogl::MgRun &run);
     int check_multigrid_keywords();
     int mg_tail_first = 0;  // first level the single-workgroup tail kernel takes in this solver's applies (mg_levels: none)
     bool precond_ready = false;        // a solve has set up precond_data (ogl_solver_apply_preconditioner)
