@@ -352,15 +352,18 @@ int ogl_solver_spmv(ogl_solver *s, const ogl_scalar *x, ogl_scalar *y);
 /* Mixed precision for GKOCG (property mixedPrecision 1, with innerRelTol 1e-4 and innerMaxIter 1000; DESIGN.md section
  * 7c): the Krylov turns run in single precision on a single-precision copy of the matrix, as the inner solver of a
  * double-precision iterative refinement -- residual, criterion, norm factor and x stay the double path's own, so the
- * answer meets the same criterion on the true residual; refinement costs 10-30 % more turns.  Applies to GKOCG on one
- * rank with preconditioner none or BJ with maxBlockSize 1; anything else with the property set fails the solve with
- * OGL_ERR_UNSUPPORTED, a coefficient that overflows single precision with OGL_ERR_INVALID.  After a solve the properties
+ * answer meets the same criterion on the true residual; refinement costs 10-30 % more turns.  Applies to GKOCG on any
+ * number of ranks with preconditioner none or BJ with maxBlockSize 1; anything else with the property set fails the solve
+ * with OGL_ERR_UNSUPPORTED, a coefficient that overflows single precision with OGL_ERR_INVALID -- on every rank, at the
+ * first check: the rank that owns it names the row, the others say that it is on another rank.  After a solve the properties
  * mixedPrecisionInUse, mixedOuterSteps, mixedInnerTurns, mixedStopReason (0 criterion, 1 maxIter, 2 no progress, 3 inner
- * breakdown) and mixedInnerLayout (2 half storage, 0 single-precision values beside the device CSR) describe it;
+ * breakdown), mixedInnerLayout (2 half storage, 0 single-precision values beside the device CSR) and mixedHaloBytes (bytes
+ * per halo value on the wire: 4 on the peer mesh, 8 through RCCL and the host callback) describe it;
  * ogl_perf::n_iterations is inner turns + 1.
  * This call: y = A32 x through the inner SpMV of the layout in use (A32 = the coefficients rounded to single precision;
  * x, y: host vectors of n_rows in the caller's cell order, every row summed from 0 in ascending column order in single
- * precision).  One rank only. */
+ * precision).  Several ranks: the distributed product -- boundary rows continue over their non-local entries in stored
+ * order on the neighbours' single-precision x -- and the call is collective: every rank calls it. */
 int ogl_solver_spmv_f32(ogl_solver *s, const float *x, float *y);
 /* z = M^-1 r with the preconditioner of the last solve (r, z: host vectors of n_rows in the caller's cell order; the
  * local operator only).  OGL_ERR_STATE before the first solve. */

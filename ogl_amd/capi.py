@@ -368,7 +368,8 @@ class Solver:
         return y
 
     def spmv_f32(self, x):
-        """y = A32 x through the inner SpMV of the mixed-precision mode (float32 in, float32 out, caller's cell order)."""
+        """y = A32 x through the inner SpMV of the mixed-precision mode (float32 in, float32 out, caller's cell order).
+        Several ranks: the distributed product, collective -- every rank calls it."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         y = np.zeros_like(x)
         fp = C.POINTER(C.c_float)

@@ -411,8 +411,6 @@ extern "C" int ogl_solver_spmv_f32(ogl_solver *s, const float *x, float *y)
     OGL_GUARD_BEGIN
     if (!s || !x || !y) return fail(OGL_ERR_INVALID, "NULL argument");
     if (!s->matrix_set) return fail(OGL_ERR_STATE, "spmv_f32 before set_matrix");
-    if (s->reg->comm && s->reg->comm->multi())
-        return fail(OGL_ERR_UNSUPPORTED, "spmv_f32: the mixed-precision mode runs on one rank (%d ranks)", s->reg->comm->n_ranks);
     OGL_HIP_CHECK(hipSetDevice(s->reg->device));
     return s->spmv_f32(x, y);
     OGL_GUARD_END

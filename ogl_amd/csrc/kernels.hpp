@@ -781,9 +781,19 @@ struct MixedScalars {
     int32_t bad_coef, bad_invd;           // first matrix value / inverse-diagonal row that overflows binary32 (INT_MAX: none)
     int32_t inner_max_iter;               // keyword innerMaxIter
     DevCriterion crit;
+    // several ranks: the rank's sums of a finaliser staged for the all-reduce of the RCCL / host-buffer rungs; the number
+    // of overflow words set over all ranks (the first outer check's all-reduce carries it next to S); a neighbour or a
+    // rank that did not show up within the time-out (the solve fails with OGL_ERR_COMM); where the turns waited, as
+    // DevScalars counts it for the double path
+    double sums[2];
+    int32_t bad_global, comm_error;
+    uint32_t halo_waits, reduce_waits;
+    unsigned long long halo_wait_ticks, reduce_wait_ticks;
 };
-// out[i] = fl32(src[map[i]]) (0 where map[i] < 0; map == nullptr: src[i]); *bad = min(*bad, i) where a finite value overflows
-void launch_mixed_refresh(hipStream_t st, int64_t n, const int32_t *map, const double *src, float *out, int32_t *bad);
+// out[i] = fl32(src[map[i]]) (0 where map[i] < 0; map == nullptr: src[i]); *bad = min(*bad, base + i) where a finite value
+// overflows (base: the non-local coefficients report positions behind the local ones)
+void launch_mixed_refresh(hipStream_t st, int64_t n, const int32_t *map, const double *src, float *out, int32_t *bad,
+                          int64_t base = 0);
 void launch_mixed_reset(hipStream_t st, MixedScalars *m, const DevCriterion &crit, double inner_rel_tol, int inner_max_iter);
 // y = A32 x on the fp32 twin of the half storage's planes / on the fp32 value array beside the device CSR; every row from
 // 0.0f in ascending column order.  part != nullptr: the per-chunk partials of sum (double)x_i (double)y_i
@@ -804,16 +814,49 @@ void launch_mixed_spmv_sym(hipStream_t st, const DevSym &A, const float *planes,
                            const MixedScalars *gate);
 void launch_mixed_spmv_csr(hipStream_t st, const DevCsr &A, const float *vals, const float *x, float *y, double *part,
                            const MixedScalars *gate);
-// the check of an outer step on the partials of sum |r|, then the step's inner tolerance and budget (one workgroup)
-void launch_mixed_head(hipStream_t st, MixedScalars *m, DevScalars *s, const double *part, int32_t n_part, double *history);
-// r32 = fl32(r / S), z = r32 * inv_d (inv_d == nullptr: z is r32 itself and not written), u = 0; + the finaliser of rho, tau0
+// The four finalisers of the mode (one workgroup each): the check of an outer step on the partials of sum |r| with the
+// step's inner tolerance and budget (HEAD; `s`: the double path's scalars, `history`), and the inner solve's START (rho,
+// tau0) | PI (pi, a32) | RHO (rho, tau, b32, the inner stop gate).  Several ranks: the sums -- S and the overflow count |
+// rho, tau0 | pi | rho, tau -- are all-reduced between the reduction and the logic, inside the launch on the peer mesh
+// (peer.world > 1), else by the caller between a do_reduce and a do_logic launch (MixedScalars::sums), as FinArgs has it.
+enum MixedFin { MIXED_FIN_HEAD = 0, MIXED_FIN_START = 1, MIXED_FIN_PI = 2, MIXED_FIN_RHO = 3 };
+struct MixedFinArgs {
+    PeerArgs peer{};
+    const double *part[2] = {nullptr, nullptr};
+    int32_t n_part = 0;
+    int32_t do_reduce = 1, do_logic = 1;
+    double *history = nullptr;
+};
+void launch_mixed_fin(hipStream_t st, int phase, MixedScalars *m, DevScalars *s, const MixedFinArgs &a);
+// r32 = fl32(r / S), z = r32 * inv_d (inv_d == nullptr: z is r32 itself and not written), u = 0; the partials of rho, tau0
 void launch_mixed_start(hipStream_t st, int32_t n, const double *r, const float *inv_d, float *r32, float *z, float *u,
                         double *part_rho, double *part_tau, MixedScalars *m);
 void launch_mixed_step1(hipStream_t st, int32_t n, float *p, const float *z, const MixedScalars *m);
-void launch_mixed_fin_pi(hipStream_t st, MixedScalars *m, const double *part, int32_t n_part);
-// u += a p, r -= a q, z = r * inv_d; + the finaliser of rho, tau and the inner stop gate
+// u += a p, r -= a q, z = r * inv_d; the partials of rho, tau
 void launch_mixed_step2(hipStream_t st, int32_t n, float *u, float *r, const float *p, const float *q, const float *inv_d,
                         float *z, double *part_rho, double *part_tau, MixedScalars *m);
+// The halo of the inner product on several ranks.  Every kernel returns at once past a stop of `gate` (may be nullptr);
+// a neighbour that does not show up within P.timeout_ticks raises comm_error and both stops in `m` and the stop of `s`.
+// Peer mesh: p32 at the send rows as 4-byte values into the neighbours' receive segments (P.remote_recv holds float
+// addresses: ogl_solver::peer_halo_args with f32), flags by the last workgroup through `ticket` ...
+void launch_mixed_put(hipStream_t st, const DevHalo &H, const PeerHalo &P, const float *x, const MixedScalars *gate,
+                      unsigned *ticket);
+// ... and after the local product one workgroup per boundary chunk: wait, q_i = q_i + a32nl_k recv32[col_k] in stored
+// order, the chunk's pi partial over the finished q (part != nullptr) ...
+void launch_mixed_halo_finish(hipStream_t st, const DevHalo &H, const float *nl_vals, int32_t n_rows,
+                              const int32_t *chunk_list, const int32_t *chunk_row_ptr, int32_t n_chunks_b, const float *recv,
+                              const float *x, float *y, double *part, const PeerHalo &P, const MixedScalars *gate,
+                              MixedScalars *m, DevScalars *s);
+// ... or (peerSafeWait) a single waiting workgroup, then launch_mixed_non_local and launch_mixed_pi_chunks
+void launch_mixed_halo_wait(hipStream_t st, const PeerHalo &P, const MixedScalars *gate, MixedScalars *m, DevScalars *s);
+// RCCL / host-buffer rungs: send[j] = (double)x[send_idxs[j]] for Comm::exchange (exact), narrowed again on arrival
+void launch_mixed_pack_wide(hipStream_t st, const DevHalo &H, const float *x, double *send, const MixedScalars *gate);
+// the non-local part over the boundary rows; exactly one of recv32 / recv64 (narrowed on read) is given
+void launch_mixed_non_local(hipStream_t st, const DevHalo &H, const float *nl_vals, const float *recv32, const double *recv64,
+                            float *y, const MixedScalars *gate);
+// the pi partials of the listed (boundary) chunks again, in the local kernels' tree
+void launch_mixed_pi_chunks(hipStream_t st, int32_t n, const float *x, const float *y, double *part,
+                            const MixedScalars *gate, const int32_t *chunk_list, int32_t n_list);
 void launch_mixed_add(hipStream_t st, int32_t n, double *x, const float *u, const MixedScalars *m);
 // scatter: out[new_id[i]] = in[i]; gather: out[i] = in[new_id[i]]
 void launch_mixed_permute(hipStream_t st, int32_t n, const int32_t *new_id, const float *in, float *out, bool gather);

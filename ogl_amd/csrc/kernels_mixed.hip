@@ -35,9 +35,9 @@ __device__ __forceinline__ bool mx_gated(const MixedScalars *m) { return m && (m
 __device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }  // (false for NaN)
 
 // out[i] = fl32(map ? src[map[i]] (0 where map[i] < 0) : src[i]); *bad = the smallest i whose value is finite in fp64
-// and not in fp32
+// and not in fp32, counted from `base`
 __global__ __launch_bounds__(BLOCK) void k_mx_refresh(long n, const int *__restrict__ map, const double *__restrict__ src,
-                                                      float *__restrict__ out, int *bad)
+                                                      float *__restrict__ out, int *bad, long base)
 {
     for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * BLOCK) {
         double v = 0.0;
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(BLOCK) void k_mx_refresh(long n, const int *__restr
         }
         const float f = (float)v;
         out[i] = f;
-        if (finite_d(v) && !(fabsf(f) <= 3.402823466e38f)) atomicMin(bad, (int)min(i, (long)(INT_MAX - 1)));
+        if (finite_d(v) && !(fabsf(f) <= 3.402823466e38f)) atomicMin(bad, (int)min(base + i, (long)(INT_MAX - 1)));
     }
 }
 
@@ -392,23 +392,221 @@ __global__ __launch_bounds__(BLOCK) void k_mx_permute(int n, const int *__restri
         out[new_id[i]] = in[i];
 }
 
+// Several ranks: a neighbour's values or a rank's sums did not arrive within the time-out -- the solve ends on every
+// kernel's gate and the host reports OGL_ERR_COMM
+__device__ __forceinline__ void mx_comm_failed(MixedScalars *m, DevScalars *s)
+{
+    m->comm_error = 1;
+    m->outer_stop = 1;
+    m->inner_stop = 1;
+    if (s) s->stop = 1;
+}
+
+// ------------------------------------------------------------------------------------------
+// the halo of the inner product on several ranks ("several ranks"): q = A32 p continues, for a
+// boundary row, acc = q_i; acc = acc + a32nl_k * recv32[col_k] over the row's non-local entries in stored order -- the
+// order of k_halo_finish and k_spmv_non_local on binary32 operands
+// ------------------------------------------------------------------------------------------
+// pack + put + signal, the fp32 form of k_pack_put_signal: P.remote_recv[] holds the float addresses of this rank's
+// segments in the neighbours' receive blocks (the arena block viewed as floats); same flags, same sequence
+__global__ __launch_bounds__(BLOCK) void k_mx_put_signal(int n_send, const int *__restrict__ send_idxs, PeerHalo P,
+                                                         const float *__restrict__ x, const MixedScalars *gate,
+                                                         unsigned *ticket)
+{
+    if (mx_gated(gate)) return;
+    const int j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j < n_send) {
+        int i = 0;
+        while (i + 1 < P.n_neigh && j >= P.send_off[i + 1]) ++i;
+        reinterpret_cast<float *>(P.remote_recv[i])[j - P.send_off[i]] = x[send_idxs[j]];
+    }
+    __threadfence_system();
+    __syncthreads();
+    __shared__ int last;
+    if (threadIdx.x == 0) {
+        last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+        if (last) *ticket = 0;
+    }
+    __syncthreads();
+    if (last && (int)threadIdx.x < P.n_neigh) {
+        __threadfence_system();
+        __hip_atomic_store(P.remote_flag[threadIdx.x], (unsigned long long)P.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// lanes 0 .. n_neigh - 1 wait for their neighbour's flag of exchange P.seq; true (to every thread) when all arrived.  The
+// wait goes into the solve's counters; a time-out raises comm_error and the stops.
+__device__ __forceinline__ bool mx_wait_flags(const PeerHalo &P, MixedScalars *m, DevScalars *s, int *timed_out, unsigned *waited)
+{
+    if (threadIdx.x == 0) {
+        *timed_out = 0;
+        *waited = 0;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < P.n_neigh) {
+        const long long t0 = wall_clock64();
+        for (;;) {
+            const unsigned long long f = __hip_atomic_load(P.local_flag + threadIdx.x, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
+            if ((uint32_t)f == P.seq) break;
+            if (wall_clock64() - t0 > P.timeout_ticks) {
+                *timed_out = 1;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(2);
+        }
+        note_wait(waited, t0);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&m->halo_wait_ticks, (unsigned long long)*waited);
+        atomicAdd(&m->halo_waits, 1u);
+        if (*timed_out) mx_comm_failed(m, s);
+    }
+    return *timed_out == 0;
+}
+
+// the pi partial of a chunk over the finished q, in the local kernels' tree
+__device__ __forceinline__ void mx_pi_partial(int n_rows, int chunk, const float *x, const float *y, double *part, double *slot)
+{
+    const RowPair rp = my_rows(chunk, n_rows);
+    const float2 xv = ld2f(x, rp), yv = ld2f(y, rp);
+    double d = 0.0;
+    if (rp.n > 0) d += (double)xv.x * (double)yv.x;
+    if (rp.n > 1) d += (double)xv.y * (double)yv.y;
+    const double sum = block_sum(d, slot);
+    if (threadIdx.x == 0) part[chunk] = sum;
+}
+
+// wait + non-local part + the pi partial of the chunk: one workgroup per chunk that holds boundary rows (a time-out
+// leaves y the local product)
+__global__ __launch_bounds__(BLOCK) void k_mx_halo_finish(int n_rows, const int *__restrict__ chunk_list,
+                                                          const int *__restrict__ chunk_row_ptr,
+                                                          const int *__restrict__ boundary_rows,
+                                                          const int *__restrict__ entry_ptrs, const int *__restrict__ cols,
+                                                          const float *__restrict__ vals, const float *recv, const float *x,
+                                                          float *y, double *part, PeerHalo P, const MixedScalars *gate,
+                                                          MixedScalars *m, DevScalars *s)
+{
+    __shared__ double slot[N_WAVES];
+    __shared__ int timed_out;
+    __shared__ unsigned waited;
+    if (mx_gated(gate)) return;
+    if (!mx_wait_flags(P, m, s, &timed_out, &waited)) return;
+    const int chunk = chunk_list[blockIdx.x];
+    for (int i = chunk_row_ptr[blockIdx.x] + threadIdx.x; i < chunk_row_ptr[blockIdx.x + 1]; i += BLOCK) {
+        const int row = boundary_rows[i];
+        float acc = y[row];
+        for (int k = entry_ptrs[i]; k < entry_ptrs[i + 1]; ++k) {
+            const float t = vals[k] * recv[cols[k]];
+            acc = acc + t;
+        }
+        y[row] = acc;
+    }
+    if (part) {
+        __threadfence_block();
+        __syncthreads();
+        mx_pi_partial(n_rows, chunk, x, y, part, slot);
+    }
+}
+
+// peerSafeWait: the single waiting workgroup of a rank
+__global__ __launch_bounds__(64) void k_mx_halo_wait(PeerHalo P, const MixedScalars *gate, MixedScalars *m, DevScalars *s)
+{
+    __shared__ int timed_out;
+    __shared__ unsigned waited;
+    if (mx_gated(gate)) return;
+    (void)mx_wait_flags(P, m, s, &timed_out, &waited);
+}
+
+// send[j] = (double)x[send_idxs[j]]: the RCCL / host-buffer rungs carry doubles (exact both ways)
+__global__ __launch_bounds__(BLOCK) void k_mx_pack_wide(int n_send, const int *__restrict__ send_idxs,
+                                                        const float *__restrict__ x, double *__restrict__ send,
+                                                        const MixedScalars *gate)
+{
+    if (mx_gated(gate)) return;
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n_send) send[i] = (double)x[send_idxs[i]];
+}
+
+// the non-local part of every boundary row; R = float (the receive block of the peer mesh) | double (narrowed on read)
+template <class R>
+__global__ __launch_bounds__(BLOCK) void k_mx_non_local(int n_boundary, const int *__restrict__ boundary_rows,
+                                                        const int *__restrict__ entry_ptrs, const int *__restrict__ cols,
+                                                        const float *__restrict__ vals, const R *recv, float *__restrict__ y,
+                                                        const MixedScalars *gate)
+{
+    if (mx_gated(gate)) return;
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_boundary) return;
+    const int row = boundary_rows[i];
+    float acc = y[row];
+    for (int k = entry_ptrs[i]; k < entry_ptrs[i + 1]; ++k) {
+        const float t = vals[k] * (float)recv[cols[k]];
+        acc = acc + t;
+    }
+    y[row] = acc;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_mx_pi_chunks(int n_rows, const int *__restrict__ chunk_list, const float *x,
+                                                        const float *y, double *part, const MixedScalars *gate)
+{
+    __shared__ double slot[N_WAVES];
+    if (mx_gated(gate)) return;
+    mx_pi_partial(n_rows, chunk_list[blockIdx.x], x, y, part, slot);
+}
+
 // ------------------------------------------------------------------------------------------
 // finalisers (one workgroup, the finaliser's tree): scalars in fp64, every quotient rounded once to binary32
 // ------------------------------------------------------------------------------------------
-enum MxPhase { MX_START = 0, MX_PI = 1, MX_RHO = 2 };
+// The sums of a finaliser over the ranks, between its reduction and its logic (v: thread 0's).  Peer mesh: inside the
+// launch, ((0 + v_0) + v_1) + ... in rank order.  The other rungs: a do_reduce launch leaves the rank's sums in
+// MixedScalars::sums, the caller all-reduces them there, a do_logic launch picks them up.  Returns false (to every thread)
+// when this launch has no logic to run.
+__device__ __forceinline__ bool mx_global_sums(MixedScalars *m, DevScalars *s, const PeerArgs &pa, int do_reduce, int do_logic,
+                                               double (&v)[2])
+{
+    if (do_reduce && !do_logic) {
+        if (threadIdx.x == 0) {
+            m->sums[0] = v[0];
+            m->sums[1] = v[1];
+        }
+        return false;
+    }
+    if (!do_reduce) {
+        v[0] = m->sums[0];
+        v[1] = m->sums[1];
+        return true;
+    }
+    if (pa.world > 1) {
+        unsigned waited = 0;
+        const bool ok = peer_allreduce2(pa, v[0], v[1], &waited);
+        if (threadIdx.x == 0) {
+            m->reduce_wait_ticks += waited;
+            m->reduce_waits += 1;
+            if (!ok) mx_comm_failed(m, s);
+        }
+        return ok;
+    }
+    return true;
+}
+
 template <int PHASE>
-__global__ __launch_bounds__(FIN_BLOCK) void k_mx_fin(MixedScalars *m, const double *part0, const double *part1, int n_part)
+__global__ __launch_bounds__(FIN_BLOCK) void k_mx_fin(MixedScalars *m, DevScalars *s, const double *part0, const double *part1,
+                                                      int n_part, PeerArgs pa, int do_reduce, int do_logic)
 {
     __shared__ double slot[FIN_WAVES];
     if (m->outer_stop || m->inner_stop) return;
     const double *const parts[2] = {part0, part1};
-    double v[2];
-    if (PHASE == MX_PI)
-        reduce_partials<1>(parts, n_part, slot, v);
-    else
-        reduce_partials<2>(parts, n_part, slot, v);
+    double v[2] = {0.0, 0.0};
+    if (do_reduce) {
+        if (PHASE == MIXED_FIN_PI)
+            reduce_partials<1>(parts, n_part, slot, v);
+        else
+            reduce_partials<2>(parts, n_part, slot, v);
+    }
+    if (!mx_global_sums(m, s, pa, do_reduce, do_logic, v)) return;
     if (threadIdx.x != 0) return;
-    if (PHASE == MX_START) {  // rho = wide(r, z), tau0 = wide1(r); L turns allowed
+    if (PHASE == MIXED_FIN_START) {  // rho = wide(r, z), tau0 = wide1(r); L turns allowed
         m->rho = v[0];
         m->tau0 = v[1];
         m->tau = v[1];
@@ -418,7 +616,7 @@ __global__ __launch_bounds__(FIN_BLOCK) void k_mx_fin(MixedScalars *m, const dou
         } else if (m->inner_cap < 1) {
             m->inner_stop = 1;
         }
-    } else if (PHASE == MX_PI) {  // pi = wide(p, q); a = fl32(rho / pi)
+    } else if (PHASE == MIXED_FIN_PI) {  // pi = wide(p, q); a = fl32(rho / pi)
         const double pi = v[0];
         m->pi = pi;
         if (pi == 0.0) {  // the turn is not counted
@@ -450,15 +648,24 @@ __global__ __launch_bounds__(FIN_BLOCK) void k_mx_fin(MixedScalars *m, const dou
 
 // O1 + O2: S = sum |r| (the partials of the residual), the check of outer step k, then this step's inner tolerance and
 // budget.  `s`: the double path's scalars -- its norm factor is read, its stop flag raised with the outer stop (the outer
-// kernels are the double path's own and gate on it).
+// kernels are the double path's own and gate on it).  Next to S the all-reduce carries the number of overflow words set
+// (a value not representable in binary32): every rank ends the solve when any rank has one.
 __global__ __launch_bounds__(FIN_BLOCK) void k_mx_head(MixedScalars *m, DevScalars *s, const double *part, int n_part,
-                                                       double *history)
+                                                       double *history, PeerArgs pa, int do_reduce, int do_logic)
 {
     __shared__ double slot[FIN_WAVES];
     if (m->outer_stop) return;
+    if (s->comm_error) {  // (an exchange or a sum of the double path's kernels between two checks)
+        if (threadIdx.x == 0) mx_comm_failed(m, s);
+        return;
+    }
     const double *const parts[2] = {part, nullptr};
-    double v[2];
-    reduce_partials<1>(parts, n_part, slot, v);
+    double v[2] = {0.0, 0.0};
+    if (do_reduce) {
+        reduce_partials<1>(parts, n_part, slot, v);
+        v[1] = (m->bad_coef != INT_MAX ? 1.0 : 0.0) + (m->bad_invd != INT_MAX ? 1.0 : 0.0);
+    }
+    if (!mx_global_sums(m, s, pa, do_reduce, do_logic, v)) return;
     if (threadIdx.x != 0) return;
     const double S = v[0], S_prev = m->S;
     const int k = m->outer_steps, T = m->total_turns + m->inner_turns;
@@ -468,8 +675,9 @@ __global__ __launch_bounds__(FIN_BLOCK) void k_mx_head(MixedScalars *m, DevScala
     m->S_prev = S_prev;
     m->S = S;
     m->norm_factor = nf;
+    m->bad_global = (int)v[1];
     int stop = 0, reason = 0;
-    if (m->bad_coef != INT_MAX || m->bad_invd != INT_MAX) {  // a value not representable in binary32: the solve fails
+    if (v[1] != 0.0) {  // a value not representable in binary32, here or on another rank: the solve fails
         stop = 1;
         reason = MIXED_STOP_INVALID;
     }
@@ -537,11 +745,12 @@ __global__ void k_mx_reset(MixedScalars *m, DevCriterion crit, double inner_rel_
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-void launch_mixed_refresh(hipStream_t st, int64_t n, const int32_t *map, const double *src, float *out, int32_t *bad)
+void launch_mixed_refresh(hipStream_t st, int64_t n, const int32_t *map, const double *src, float *out, int32_t *bad,
+                          int64_t base)
 {
     if (n <= 0) return;
     const int64_t blocks = std::min<int64_t>((n + BLOCK - 1) / BLOCK, 8192);
-    hipLaunchKernelGGL(k_mx_refresh, dim3((unsigned)blocks), dim3(BLOCK), 0, st, (long)n, map, src, out, bad);
+    hipLaunchKernelGGL(k_mx_refresh, dim3((unsigned)blocks), dim3(BLOCK), 0, st, (long)n, map, src, out, bad, (long)base);
 }
 
 void launch_mixed_reset(hipStream_t st, MixedScalars *m, const DevCriterion &crit, double inner_rel_tol, int inner_max_iter)
@@ -626,9 +835,21 @@ void launch_mg_fine_csr(hipStream_t st, const DevCsr &A, const float *vals, MxEp
     }
 }
 
-void launch_mixed_head(hipStream_t st, MixedScalars *m, DevScalars *s, const double *part, int32_t n_part, double *history)
+void launch_mixed_fin(hipStream_t st, int phase, MixedScalars *m, DevScalars *s, const MixedFinArgs &a)
 {
-    hipLaunchKernelGGL(k_mx_head, dim3(1), dim3(FIN_BLOCK), 0, st, m, s, part, n_part, history);
+    const dim3 grid(1), block(FIN_BLOCK);
+#define OGL_MX_FIN(PHASE)                                                                                              \
+    hipLaunchKernelGGL((k_mx_fin<PHASE>), grid, block, 0, st, m, s, a.part[0], a.part[1], a.n_part, a.peer, a.do_reduce, \
+                       a.do_logic)
+    switch (phase) {
+    case MIXED_FIN_HEAD:
+        hipLaunchKernelGGL(k_mx_head, grid, block, 0, st, m, s, a.part[0], a.n_part, a.history, a.peer, a.do_reduce, a.do_logic);
+        break;
+    case MIXED_FIN_START: OGL_MX_FIN(MIXED_FIN_START); break;
+    case MIXED_FIN_PI: OGL_MX_FIN(MIXED_FIN_PI); break;
+    default: OGL_MX_FIN(MIXED_FIN_RHO); break;
+    }
+#undef OGL_MX_FIN
 }
 
 void launch_mixed_start(hipStream_t st, int32_t n, const double *r, const float *inv_d, float *r32, float *z, float *u,
@@ -637,7 +858,6 @@ void launch_mixed_start(hipStream_t st, int32_t n, const double *r, const float 
     const int nc = (int)n_chunks(n);
     if (nc == 0) return;
     hipLaunchKernelGGL(k_mx_start, dim3(nc), dim3(BLOCK), 0, st, n, r, inv_d, r32, z, u, part_rho, part_tau, m);
-    hipLaunchKernelGGL((k_mx_fin<MX_START>), dim3(1), dim3(FIN_BLOCK), 0, st, m, part_rho, part_tau, nc);
 }
 
 void launch_mixed_step1(hipStream_t st, int32_t n, float *p, const float *z, const MixedScalars *m)
@@ -647,18 +867,61 @@ void launch_mixed_step1(hipStream_t st, int32_t n, float *p, const float *z, con
     hipLaunchKernelGGL(k_mx_step1, dim3(nc), dim3(BLOCK), 0, st, n, p, z, m);
 }
 
-void launch_mixed_fin_pi(hipStream_t st, MixedScalars *m, const double *part, int32_t n_part)
-{
-    hipLaunchKernelGGL((k_mx_fin<MX_PI>), dim3(1), dim3(FIN_BLOCK), 0, st, m, part, nullptr, n_part);
-}
-
 void launch_mixed_step2(hipStream_t st, int32_t n, float *u, float *r, const float *p, const float *q, const float *inv_d,
                         float *z, double *part_rho, double *part_tau, MixedScalars *m)
 {
     const int nc = (int)n_chunks(n);
     if (nc == 0) return;
     hipLaunchKernelGGL(k_mx_step2, dim3(nc), dim3(BLOCK), 0, st, n, u, r, p, q, inv_d, z, part_rho, part_tau, m);
-    hipLaunchKernelGGL((k_mx_fin<MX_RHO>), dim3(1), dim3(FIN_BLOCK), 0, st, m, part_rho, part_tau, nc);
+}
+
+void launch_mixed_put(hipStream_t st, const DevHalo &H, const PeerHalo &P, const float *x, const MixedScalars *gate,
+                      unsigned *ticket)
+{
+    if (H.n_send == 0) return;
+    hipLaunchKernelGGL(k_mx_put_signal, dim3(blocks_for(H.n_send)), dim3(BLOCK), 0, st, H.n_send, H.send_idxs, P, x, gate, ticket);
+}
+
+void launch_mixed_halo_finish(hipStream_t st, const DevHalo &H, const float *nl_vals, int32_t n_rows,
+                              const int32_t *chunk_list, const int32_t *chunk_row_ptr, int32_t n_chunks_b, const float *recv,
+                              const float *x, float *y, double *part, const PeerHalo &P, const MixedScalars *gate,
+                              MixedScalars *m, DevScalars *s)
+{
+    if (n_chunks_b == 0) return;
+    hipLaunchKernelGGL(k_mx_halo_finish, dim3(n_chunks_b), dim3(BLOCK), 0, st, n_rows, chunk_list, chunk_row_ptr,
+                       H.boundary_rows, H.entry_ptrs, H.cols, nl_vals, recv, x, y, part, P, gate, m, s);
+}
+
+void launch_mixed_halo_wait(hipStream_t st, const PeerHalo &P, const MixedScalars *gate, MixedScalars *m, DevScalars *s)
+{
+    if (P.n_neigh == 0) return;
+    hipLaunchKernelGGL(k_mx_halo_wait, dim3(1), dim3(64), 0, st, P, gate, m, s);
+}
+
+void launch_mixed_pack_wide(hipStream_t st, const DevHalo &H, const float *x, double *send, const MixedScalars *gate)
+{
+    if (H.n_send == 0) return;
+    hipLaunchKernelGGL(k_mx_pack_wide, dim3(blocks_for(H.n_send)), dim3(BLOCK), 0, st, H.n_send, H.send_idxs, x, send, gate);
+}
+
+void launch_mixed_non_local(hipStream_t st, const DevHalo &H, const float *nl_vals, const float *recv32, const double *recv64,
+                            float *y, const MixedScalars *gate)
+{
+    if (H.n_boundary_rows == 0) return;
+    const dim3 grid(blocks_for(H.n_boundary_rows)), block(BLOCK);
+    if (recv32)
+        hipLaunchKernelGGL(k_mx_non_local<float>, grid, block, 0, st, H.n_boundary_rows, H.boundary_rows, H.entry_ptrs, H.cols,
+                           nl_vals, recv32, y, gate);
+    else
+        hipLaunchKernelGGL(k_mx_non_local<double>, grid, block, 0, st, H.n_boundary_rows, H.boundary_rows, H.entry_ptrs, H.cols,
+                           nl_vals, recv64, y, gate);
+}
+
+void launch_mixed_pi_chunks(hipStream_t st, int32_t n, const float *x, const float *y, double *part, const MixedScalars *gate,
+                            const int32_t *chunk_list, int32_t n_list)
+{
+    if (n_list == 0) return;
+    hipLaunchKernelGGL(k_mx_pi_chunks, dim3(n_list), dim3(BLOCK), 0, st, n, chunk_list, x, y, part, gate);
 }
 
 void launch_mixed_add(hipStream_t st, int32_t n, double *x, const float *u, const MixedScalars *m)

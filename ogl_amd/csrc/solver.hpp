@@ -508,7 +508,8 @@ struct ogl_solver {
     uint64_t cg_graph_key = 0;  // hash of everything the captured launches bake in (launch_key.hpp)
     void drop_cg_graph();  // (every pattern / layout rebuild)
     int setup_peer_halo();
-    ogl::PeerHalo peer_halo_args(uint32_t seq) const;
+    // f32: the receive segments viewed as floats (the mixed mode's 4-byte halo; remote_recv then holds float addresses)
+    ogl::PeerHalo peer_halo_args(uint32_t seq, bool f32 = false) const;
     double *peer_recv(uint32_t seq) const;
     // halo part
     std::vector<int32_t> boundary_rows, boundary_ptrs;
@@ -645,7 +646,10 @@ struct ogl_solver {
     int mixed_storage(const ogl::DevCriterion &crit, double inner_rel_tol, int inner_max_iter);
     int fp32_bad_row(int64_t position, int64_t *row) const;  // the device row of a position in fp32_dev's value array
     int mixed_overflow(const ogl::MixedScalars &m);  // OGL_ERR_INVALID naming the row when a value overflowed binary32
-    void mixed_spmv(const float *x, float *y, double *part, const ogl::MixedScalars *gate);
+    // q = A32 p: the local product, on several ranks between the halo's put (or pack + exchange) and its non-local part
+    int mixed_spmv(const float *x, float *y, double *part, const ogl::MixedScalars *gate);
+    // a finaliser of the mode with its sums all-reduced over the ranks (the split of finalize)
+    int mixed_fin(int phase, ogl::MixedFinArgs &a);
     int run_mixed(ogl_perf *perf);
     // property orthoMethod (0 mgs | 1 cgs | 2 cgs2; GKOGMRES only, ignored elsewhere): its validation and the refusal on
     // several ranks (OGL_ERR_INVALID / _UNSUPPORTED)

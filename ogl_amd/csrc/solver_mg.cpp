@@ -143,10 +143,10 @@ int ogl_solver::prepare_multigrid_single()
     if (!L0.own) {
         const bool half = spmv_layout == SpmvLayout::Sym;
         if (half) refresh_values(SpmvLayout::Sym);
-        OGL_TRY(fp32_dev.ensure(half, pat_id, half ? sym_dev.map.n : d_vals.n, st));
+        OGL_TRY(fp32_dev.ensure(half, pat_id, half ? sym_dev.map.n : d_vals.n, 0, st));  // (the cycle is the local block's)
         if (fp32_dev.epoch != vals_epoch || vals_epoch == 0) {
             if (!converted) OGL_HIP_CHECK(hipMemsetAsync(M.bad.p, 0x7f, sizeof(int32_t), st));
-            fp32_dev.refresh(half ? sym_dev.map.p : nullptr, d_vals.p, M.bad.p, st);
+            fp32_dev.refresh(half ? sym_dev.map.p : nullptr, d_vals.p, nullptr, M.bad.p, st);
             fp32_dev.epoch = vals_epoch;
             converted = true;
         }

@@ -23,8 +23,8 @@ int32_t *word_of(MixedScalars *m, size_t offset) { return reinterpret_cast<int32
 
 }  // namespace
 
-// The keywords (properties of the same name) and where the mode applies: GKOCG, one rank, preconditioner none or BJ with
-// maxBlockSize 1.  Anything else with mixedPrecision set is refused, none silently.
+// The keywords (properties of the same name) and where the mode applies: GKOCG, any number of ranks, preconditioner none or
+// BJ with maxBlockSize 1.  Anything else with mixedPrecision set is refused, none silently.
 int ogl_solver::mixed_requested(bool *on)
 {
     *on = prop("mixedPrecision", 0.0) != 0.0;
@@ -36,9 +36,9 @@ int ogl_solver::mixed_requested(bool *on)
     const PrecondKind kind = precond_kind_of(cfg);
     const bool precond_ok = cfg.preconditioner == OGL_PRECOND_NONE || kind == PrecondKind::Jacobi;
     const int n_ranks = reg->comm ? reg->comm->n_ranks : 1;
-    if (cfg.solver != OGL_SOLVER_CG || !precond_ok || n_ranks > 1)
+    if (cfg.solver != OGL_SOLVER_CG || !precond_ok)
         return fail(OGL_ERR_UNSUPPORTED,
-                    "mixedPrecision runs GKOCG on one rank with preconditioner none or BJ with maxBlockSize 1: this is "
+                    "mixedPrecision runs GKOCG with preconditioner none or BJ with maxBlockSize 1: this is "
                     "solver %s, preconditioner %s (maxBlockSize %d), %d rank(s)",
                     solver_name(cfg.solver), cfg.preconditioner == OGL_PRECOND_NONE ? "none" : precond_name(kind),
                     cfg.max_block_size, n_ranks);
@@ -59,26 +59,108 @@ int ogl_solver::mixed_storage(const DevCriterion &crit, double inner_rel_tol, in
     launch_mixed_reset(st, mixed.scal.p, crit, inner_rel_tol, inner_max_iter);
     const bool half = spmv_layout == SpmvLayout::Sym;
     if (half) refresh_values(SpmvLayout::Sym);
-    OGL_TRY(fp32_dev.ensure(half, pat_id, half ? sym_dev.map.n : d_vals.n, st));
+    // (processor interfaces: A32_nl beside it, the halo in fp32 -- nothing but the twin of d_nl_vals is allocated for it)
+    OGL_TRY(fp32_dev.ensure(half, pat_id, half ? sym_dev.map.n : d_vals.n, (size_t)pat.non_local_nnz, st));
     if (fp32_dev.epoch != vals_epoch || vals_epoch == 0) {
-        fp32_dev.refresh(half ? sym_dev.map.p : nullptr, d_vals.p, word_of(mixed.scal.p, offsetof(MixedScalars, bad_coef)), st);
+        fp32_dev.refresh(half ? sym_dev.map.p : nullptr, d_vals.p, d_nl_vals.p,
+                         word_of(mixed.scal.p, offsetof(MixedScalars, bad_coef)), st);
         fp32_dev.epoch = vals_epoch;
     }
     props["mixedInnerLayout"] = half ? 2.0 : 0.0;  // (spmvLayout's codes: 2 half storage, 0 the CSR arrays)
+    props["mixedHaloBytes"] = peer_halo ? 4.0 : 8.0;  // (bytes per halo value on the wire)
     return OGL_OK;
 }
 
-void ogl_solver::mixed_spmv(const float *x, float *y, double *part, const MixedScalars *gate)
+// q = A32 p on this rank's rows.  Several ranks: the neighbours' p32 at their send rows travels while
+// the local product runs -- as 4-byte values through the peer mesh, on the sequence and the flags of the double path's
+// exchanges; widened to doubles through Comm::exchange on the other rungs -- then the boundary rows continue over their
+// non-local entries and the boundary chunks' pi partials are formed again over the finished q.
+int ogl_solver::mixed_spmv(const float *x, float *y, double *part, const MixedScalars *gate)
 {
-    if (fp32_dev.half)
-        launch_mixed_spmv_sym(reg->stream, sym(), fp32_dev.planes.p, x, y, part, gate);
-    else
-        launch_mixed_spmv_csr(reg->stream, csr(false), fp32_dev.vals.p, x, y, part, gate);
+    hipStream_t st = reg->stream;
+    auto local = [&]() {
+        if (fp32_dev.half)
+            launch_mixed_spmv_sym(st, sym(), fp32_dev.planes.p, x, y, part, gate);
+        else
+            launch_mixed_spmv_csr(st, csr(false), fp32_dev.vals.p, x, y, part, gate);
+    };
+    if (pat.non_local_nnz == 0) {
+        local();
+        return OGL_OK;
+    }
+    MixedScalars *m = mixed.scal.p;
+    const DevHalo H = halo();
+    const float *nl = fp32_dev.nl_vals.p;
+    if (peer_halo) {
+        if (++halo_seq == 0) ++halo_seq;
+        const PeerHalo ph = peer_halo_args(halo_seq, /*f32=*/true);
+        const float *recv = reinterpret_cast<const float *>(peer_recv(ph.seq));
+        launch_mixed_put(st, H, ph, x, gate, d_ticket.p);
+        local();
+        if (peer_safe_wait()) {  // (ranks that share a device: no workgroup of a product waits, dist_spmv has the reason)
+            launch_mixed_halo_wait(st, ph, gate, m, d_scal.p);
+            launch_mixed_non_local(st, H, nl, recv, nullptr, y, gate);
+            if (part) launch_mixed_pi_chunks(st, pat.n_rows, x, y, part, gate, d_boundary_chunks.p, n_boundary_chunks);
+        } else {
+            launch_mixed_halo_finish(st, H, nl, pat.n_rows, d_boundary_chunks.p, d_boundary_chunk_ptr.p, n_boundary_chunks,
+                                     recv, x, y, part, ph, gate, m, d_scal.p);
+        }
+        return OGL_OK;
+    }
+    if (!reg->comm_stream) {
+        OGL_HIP_CHECK(stream_create(&reg->comm_stream));
+        OGL_HIP_CHECK(ev_create(&reg->ev_packed, hipEventDisableTiming));
+        OGL_HIP_CHECK(ev_create(&reg->ev_received, hipEventDisableTiming));
+    }
+    launch_mixed_pack_wide(st, H, x, d_send.p, gate);
+    OGL_HIP_CHECK(hipEventRecord(reg->ev_packed, st));
+    OGL_HIP_CHECK(hipStreamWaitEvent(reg->comm_stream, reg->ev_packed, 0));
+    OGL_TRY(reg->comm->exchange(d_send.p, d_recv.p, neighbours, counts, reg->comm_stream));
+    OGL_HIP_CHECK(hipEventRecord(reg->ev_received, reg->comm_stream));
+    local();
+    OGL_HIP_CHECK(hipStreamWaitEvent(st, reg->ev_received, 0));
+    launch_mixed_non_local(st, H, nl, nullptr, d_recv.p, y, gate);
+    if (part) launch_mixed_pi_chunks(st, pat.n_rows, x, y, part, gate, d_boundary_chunks.p, n_boundary_chunks);
+    return OGL_OK;
 }
 
-// The device row that holds position `position` of fp32_dev's value array (the planes' twin or the CSR values).
+// A finaliser of the mode.  Several ranks: its sums are all-reduced between the reduction and the logic -- inside the launch
+// on the peer mesh, by Comm::allreduce between two launches on the other rungs (ogl_solver::finalize has the same split).
+int ogl_solver::mixed_fin(int phase, MixedFinArgs &a)
+{
+    hipStream_t st = reg->stream;
+    MixedScalars *m = mixed.scal.p;
+    a.peer = PeerArgs{};
+    a.do_reduce = a.do_logic = 1;
+    if (!reg->comm->multi()) {
+        launch_mixed_fin(st, phase, m, d_scal.p, a);
+        return OGL_OK;
+    }
+    if (reg->peer_ready) {
+        a.peer = reg->peer_next();
+        launch_mixed_fin(st, phase, m, d_scal.p, a);
+        a.peer = PeerArgs{};
+        return OGL_OK;
+    }
+    a.do_logic = 0;
+    launch_mixed_fin(st, phase, m, d_scal.p, a);
+    OGL_TRY(reg->comm->allreduce(reinterpret_cast<double *>(reinterpret_cast<char *>(m) + offsetof(MixedScalars, sums)), 2, st));
+    a.do_reduce = 0;
+    a.do_logic = 1;
+    launch_mixed_fin(st, phase, m, d_scal.p, a);
+    return OGL_OK;
+}
+
+// The device row that holds position `position` of fp32_dev's value array (the planes' twin or the CSR values; behind
+// them the non-local coefficients, whose row is the boundary row that owns the entry).
 int ogl_solver::fp32_bad_row(int64_t position, int64_t *row) const
 {
+    if (position >= fp32_dev.local_count()) {
+        const int64_t e = position - fp32_dev.local_count();
+        const size_t i = (size_t)(std::upper_bound(boundary_ptrs.begin(), boundary_ptrs.end(), (int32_t)e) - boundary_ptrs.begin());
+        *row = i >= 1 && i - 1 < boundary_rows.size() ? boundary_rows[i - 1] : 0;
+        return OGL_OK;
+    }
     if (fp32_dev.half) {
         const int64_t per_chunk = (int64_t)sym_dev.nd * CHUNK_ROWS;
         *row = (position / per_chunk) * CHUNK_ROWS + position % CHUNK_ROWS;
@@ -91,11 +173,15 @@ int ogl_solver::fp32_bad_row(int64_t position, int64_t *row) const
 }
 
 // A coefficient or an inverse diagonal that is finite in fp64 and not in binary32: the solve fails and names the row
-// (the caller's numbering).  The copy is marked stale, so that the next call converts -- and reports -- again.
+// (the caller's numbering).  The copy is marked stale, so that the next call converts -- and reports -- again.  Several
+// ranks end such a solve together at its first outer check (bad_global): a rank that owns no such value says so.
 int ogl_solver::mixed_overflow(const MixedScalars &m)
 {
-    if (m.bad_coef == INT_MAX && m.bad_invd == INT_MAX) return OGL_OK;
+    if (m.bad_coef == INT_MAX && m.bad_invd == INT_MAX && m.bad_global == 0) return OGL_OK;
     fp32_dev.epoch = 0;
+    if (m.bad_coef == INT_MAX && m.bad_invd == INT_MAX)
+        return fail(OGL_ERR_INVALID, "mixedPrecision: a value on another rank is finite in double precision and not in single "
+                                     "precision (that rank names the row)");
     const bool coef = m.bad_coef != INT_MAX;
     int64_t row = m.bad_invd;
     if (coef) OGL_TRY(fp32_bad_row(m.bad_coef, &row));
@@ -138,12 +224,24 @@ int ogl_solver::run_mixed(ogl_perf *perf)
     // O0: the double path's prologue -- norm factor, r = b - A x on the in-loop layout, the partials of sum |r|
     const double t_start = now_ms();
     launch_reset_scalars(st, s, crit);
+    double n_global = (double)n;
+    if (reg->comm->multi()) {  // the global row count, as krylov_plan has it
+        const double mine[2] = {(double)n, 0.0};
+        double got[2] = {0.0, 0.0};
+        OGL_HIP_CHECK(hipMemcpyAsync(sums_ptr(s), mine, sizeof(mine), hipMemcpyHostToDevice, st));
+        OGL_HIP_CHECK(hipStreamSynchronize(st));
+        OGL_TRY(reg->allreduce(sums_ptr(s), 2));
+        OGL_HIP_CHECK(hipMemcpyAsync(got, sums_ptr(s), sizeof(got), hipMemcpyDeviceToHost, st));
+        OGL_HIP_CHECK(hipStreamSynchronize(st));
+        n_global = got[0];
+    }
     launch_partials_sum(st, n, d_x.p, d_part0.p);
     FinArgs fa{};
     fa.part[0] = d_part0.p;
     fa.n_part = nc;
     fa.n_sums = 1;
-    fa.n_local = fa.n_global = (double)n;
+    fa.n_local = (double)n;
+    fa.n_global = n_global;
     OGL_TRY(finalize(FIN_MEAN, fa));
     launch_fill_xbar(st, n, d_w.p, s);
     OGL_TRY(dist_spmv(SPMV_PLAIN, d_w.p, nullptr, d_q.p, SpmvDots{}, nullptr));
@@ -162,13 +260,24 @@ int ogl_solver::run_mixed(ogl_perf *perf)
         return OGL_OK;
     };
     // one inner turn, five launches: step 1 | SpMV (pi partials) | a | steps 4, 5 (rho, tau partials) | rho, tau, the gate
-    auto enqueue_turns = [&](int count) {
+    // (several ranks: + the halo's put and finish; every rank enqueues the same launches and calls the same collectives
+    //  whatever its row count -- a finaliser runs on a rank without rows too)
+    MixedFinArgs f_head{}, f_pi{}, f_rho{};
+    f_head.part[0] = d_part2.p;
+    f_head.history = d_history.p;
+    f_pi.part[0] = d_part2.p;
+    f_rho.part[0] = d_part0.p;
+    f_rho.part[1] = d_part1.p;
+    f_head.n_part = f_pi.n_part = f_rho.n_part = nc;
+    auto enqueue_turns = [&](int count) -> int {
         for (int i = 0; i < count; ++i) {
             launch_mixed_step1(st, n, mixed.p.p, z, m);
-            mixed_spmv(mixed.p.p, mixed.q.p, d_part2.p, m);
-            launch_mixed_fin_pi(st, m, d_part2.p, nc);
+            OGL_TRY(mixed_spmv(mixed.p.p, mixed.q.p, d_part2.p, m));
+            OGL_TRY(mixed_fin(MIXED_FIN_PI, f_pi));
             launch_mixed_step2(st, n, mixed.u.p, mixed.r.p, mixed.p.p, mixed.q.p, inv_d, mixed.z.p, d_part0.p, d_part1.p, m);
+            OGL_TRY(mixed_fin(MIXED_FIN_RHO, f_rho));
         }
+        return OGL_OK;
     };
     const int batch = 16;
     int turns = 0, enqueued = 0;  // inner turns so far (the device's total_turns); turns put into the stream
@@ -176,26 +285,28 @@ int ogl_solver::run_mixed(ogl_perf *perf)
     for (int k = 0;; ++k) {
         // O1, O2 (one launch), O3 + the start of the inner solve
         if (k == 0) OGL_HIP_CHECK(hipEventRecord(chk_ev[0], st));
-        launch_mixed_head(st, m, s, d_part2.p, nc, d_history.p);
+        OGL_TRY(mixed_fin(MIXED_FIN_HEAD, f_head));
         if (k == 0) OGL_HIP_CHECK(hipEventRecord(chk_ev[1], st));
         launch_mixed_start(st, n, d_r.p, inv_d, mixed.r.p, z, mixed.u.p, d_part0.p, d_part1.p, m);
+        OGL_TRY(mixed_fin(MIXED_FIN_START, f_rho));
         // O4: the device's budget of this step is min(innerMaxIter, maxIter - T); the host knows T exactly, so it never
         // enqueues past it, and it looks at the flags of batch j only after batch j + 1 is in the queue
         const int cap = std::max(0, std::min(inner_max_iter, crit.max_iter - turns));
         int enq = 0;
-        auto next_batch = [&]() {
+        auto next_batch = [&]() -> int {
             const int count = std::min(batch, cap - enq);
-            enqueue_turns(count);
+            OGL_TRY(enqueue_turns(count));
             enq += count;
             enqueued += count;
+            return OGL_OK;
         };
-        next_batch();
+        OGL_TRY(next_batch());
         OGL_TRY(poll_record(0));
         MixedScalars seen{};
         for (int j = 0;; ++j) {
             const bool more = enq < cap;
             if (more) {
-                next_batch();
+                OGL_TRY(next_batch());
                 OGL_TRY(poll_record((j + 1) & 1));
             }
             OGL_HIP_CHECK(hipEventSynchronize(poll_ev[j & 1]));
@@ -215,8 +326,20 @@ int ogl_solver::run_mixed(ogl_perf *perf)
     }
     OGL_HIP_CHECK(hipStreamSynchronize(st));
     OGL_HIP_CHECK(hipGetLastError());
+    if (fin.comm_error)
+        return fail(OGL_ERR_COMM, "mixedPrecision: peer all-reduce or halo exchange timed out: a rank did not take part "
+                                  "(outer step %d, inner turn %d)", fin.outer_steps, fin.inner_turns);
     if (fin.stop_reason == MIXED_STOP_INVALID) OGL_TRY(mixed_overflow(fin));
     const double t_solve = now_ms() - t_start;
+    // where the turns waited: the inner solve's exchanges and sums (MixedScalars) and the double path's of O0 and O6
+    DevScalars outer{};
+    if (reg->comm->multi()) OGL_HIP_CHECK(hipMemcpy(&outer, s, sizeof(outer), hipMemcpyDeviceToHost));
+    props["haloWaits"] = (double)fin.halo_waits + (double)outer.halo_waits;
+    props["haloWaitUs"] = ((double)fin.halo_wait_ticks + (double)outer.halo_wait_ticks) / 100.0;
+    props["allreduceWaits"] = (double)fin.reduce_waits + (double)outer.reduce_waits;
+    props["allreduceWaitUs"] = ((double)fin.reduce_wait_ticks + (double)outer.reduce_wait_ticks) / 100.0;
+    props["peerSafeWaitInUse"] = (pat.non_local_nnz > 0 && peer_halo && peer_safe_wait()) ? 1.0 : 0.0;
+    props["peerSharedDevice"] = reg->peer_shared_device ? 1.0 : 0.0;
     history.clear();
     if (cfg.export_res) {  // entry j: the j-th evaluated check
         history.resize((size_t)fin.n_evals);
@@ -240,12 +363,13 @@ int ogl_solver::run_mixed(ogl_perf *perf)
     props[is_final ? "prevSolveIters_final" : "prevSolveIters"] = perf->n_iterations;
     const double res_norm_time = std::max(1e-3, (double)chk_ms * 1e3);
     perf->t_res_norm_us = res_norm_time;
-    perf->n_global_rows = (double)n;
+    perf->n_global_rows = n_global;
     props["_prev_solve"] = std::floor(t_solve * 1e3 / std::max(perf->n_iterations, 1) / res_norm_time);
     return OGL_OK;
 }
 
-// y = A32 x through the inner SpMV of the layout in use, both vectors in the caller's order
+// y = A32 x through the inner SpMV of the layout in use, both vectors in the caller's order.  Several ranks: the
+// distributed product, collective -- every rank calls it.
 int ogl_solver::spmv_f32(const float *x, float *y)
 {
     hipStream_t st = reg->stream;
@@ -259,7 +383,7 @@ int ogl_solver::spmv_f32(const float *x, float *y)
     } else {
         OGL_TRY(reg->stager.h2d(mixed.p.p, x, bytes, st));
     }
-    mixed_spmv(mixed.p.p, mixed.q.p, nullptr, nullptr);
+    OGL_TRY(mixed_spmv(mixed.p.p, mixed.q.p, nullptr, nullptr));
     // property mixedTimedSpmvs > 0 (measurements only): that many inner SpMVs with the pi partials, as a turn runs them,
     // timed with HIP events -> mixedSpmvUs
     if (const int timed = (int)prop("mixedTimedSpmvs", 0.0); timed > 0) {
@@ -267,10 +391,10 @@ int ogl_solver::spmv_f32(const float *x, float *y)
         OGL_HIP_CHECK(ev_create(&ev[0]));
         OGL_HIP_CHECK(ev_create(&ev[1]));
         OGL_HIP_CHECK(hipMemcpyAsync(mixed.r.p, mixed.p.p, bytes, hipMemcpyDeviceToDevice, st));
-        mixed_spmv(mixed.r.p, mixed.z.p, d_part2.p, nullptr);  // warm-up
+        OGL_TRY(mixed_spmv(mixed.r.p, mixed.z.p, d_part2.p, nullptr));  // warm-up
         OGL_HIP_CHECK(hipEventRecord(ev[0], st));
         for (int i = 0; i < timed; ++i)  // (alternating inputs: no launch reads what the last one wrote)
-            mixed_spmv((i & 1) ? mixed.r.p : mixed.p.p, mixed.z.p, d_part2.p, nullptr);
+            OGL_TRY(mixed_spmv((i & 1) ? mixed.r.p : mixed.p.p, mixed.z.p, d_part2.p, nullptr));
         OGL_HIP_CHECK(hipEventRecord(ev[1], st));
         OGL_HIP_CHECK(hipEventSynchronize(ev[1]));
         float ms = 0.f;
@@ -288,5 +412,7 @@ int ogl_solver::spmv_f32(const float *x, float *y)
     OGL_HIP_CHECK(hipStreamSynchronize(st));
     OGL_HIP_CHECK(hipGetLastError());
     got = mixed.h_scal[0];
+    if (got.comm_error)
+        return fail(OGL_ERR_COMM, "spmv_f32: halo exchange timed out: a neighbour's values did not arrive");
     return mixed_overflow(got);
 }

@@ -239,7 +239,7 @@ int ogl_solver::setup_peer_halo()
     return OGL_OK;
 }
 
-PeerHalo ogl_solver::peer_halo_args(uint32_t seq) const
+PeerHalo ogl_solver::peer_halo_args(uint32_t seq, bool f32) const
 {
     const ogl_registry &R = *reg;
     const int nn = (int)neighbours.size();
@@ -255,8 +255,9 @@ PeerHalo ogl_solver::peer_halo_args(uint32_t seq) const
         const PeerNeighbour &nb = peer_nb[i];
         unsigned long long *base = R.peer.box[neighbours[i]] + PEER_ARENA_OFF + nb.block;
         P.remote_flag[i] = base + (size_t)par * nb.n_neigh + nb.my_index;
-        P.remote_recv[i] = reinterpret_cast<double *>(base + 2 * (size_t)nb.n_neigh +
-                                                      (size_t)par * nb.n_halo + nb.my_seg);
+        unsigned long long *block = base + 2 * (size_t)nb.n_neigh + (size_t)par * nb.n_halo;
+        P.remote_recv[i] = f32 ? reinterpret_cast<double *>(reinterpret_cast<float *>(block) + nb.my_seg)
+                               : reinterpret_cast<double *>(block + nb.my_seg);
     }
     P.send_off[nn] = off;
     P.local_flag = R.peer_local + PEER_ARENA_OFF + peer_block + (size_t)par * nn;

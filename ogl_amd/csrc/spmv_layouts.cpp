@@ -445,27 +445,31 @@ void Stream21Dev::view(DevCsr &A) const
 }
 
 // ---- fp32 copy for the mixed-precision mode ----
-int Fp32Dev::ensure(bool half_storage, uint64_t pattern, size_t count, hipStream_t st)
+int Fp32Dev::ensure(bool half_storage, uint64_t pattern, size_t count, size_t nl_count, hipStream_t st)
 {
     DevBuf<float> &b = half_storage ? planes : vals;
-    if (half != half_storage || pat_id != pattern || b.n != count) epoch = 0;
+    if (half != half_storage || pat_id != pattern || b.n != count || nl_vals.n != nl_count) epoch = 0;
     half = half_storage;
     pat_id = pattern;
     (half_storage ? vals : planes).release();
+    if (nl_count == 0) nl_vals.release();
+    else if (int rc = nl_vals.alloc(nl_count, st)) return rc;
     return b.alloc(count, st);
 }
 
-void Fp32Dev::refresh(const int32_t *map, const double *csr_vals, int32_t *bad, hipStream_t st)
+void Fp32Dev::refresh(const int32_t *map, const double *csr_vals, const double *nl_csr_vals, int32_t *bad, hipStream_t st)
 {
     DevBuf<float> &b = half ? planes : vals;
     // (the planes carry two slots of padding behind the map's last entry, as SymDev::refresh knows)
-    launch_mixed_refresh(st, half ? (int64_t)b.n - 2 : (int64_t)b.n, map, csr_vals, b.p, bad);
+    launch_mixed_refresh(st, local_count(), map, csr_vals, b.p, bad);
+    if (nl_vals.n) launch_mixed_refresh(st, (int64_t)nl_vals.n, nullptr, nl_csr_vals, nl_vals.p, bad, local_count());
 }
 
 void Fp32Dev::release()
 {
     planes.release();
     vals.release();
+    nl_vals.release();
     epoch = 0;
 }
 

@@ -128,15 +128,18 @@ struct Stream21Dev {
 // twin of the half storage's planes when that is the in-loop layout -- it shares SymDev's mask, map and order -- and an
 // fp32 value array beside the device CSR (sharing its row pointers and columns) for every other in-loop layout.
 // Allocated at the first mixed solve and kept; refreshed from the CSR values under the values epoch by one kernel that
-// also reports the first value that overflows binary32.
+// also reports the first value that overflows binary32.  A solver with processor interfaces keeps the fp32 twin of the
+// non-local coefficients (A32_nl) next to it: same epoch, same overflow word, positions counted behind the local ones.
 struct Fp32Dev {
-    DevBuf<float> planes, vals;
+    DevBuf<float> planes, vals, nl_vals;
     bool half = false;     // which of the two is in use
     uint64_t pat_id = 0;   // the pattern the buffers were sized for
     uint64_t epoch = 0;    // 0: stale
-    int ensure(bool half_storage, uint64_t pattern, size_t count, hipStream_t st);
+    int ensure(bool half_storage, uint64_t pattern, size_t count, size_t nl_count, hipStream_t st);
     // map: SymDev::map (half storage) or nullptr (CSR values); bad: device word that receives the overflowing position
-    void refresh(const int32_t *map, const double *csr_vals, int32_t *bad, hipStream_t st);
+    // (a non-local coefficient: local_count() + its position)
+    void refresh(const int32_t *map, const double *csr_vals, const double *nl_csr_vals, int32_t *bad, hipStream_t st);
+    int64_t local_count() const { return half ? (int64_t)planes.n - 2 : (int64_t)vals.n; }
     const float *values() const { return half ? planes.p : vals.p; }
     void release();
 };
