@@ -116,25 +116,110 @@ __device__ __forceinline__ void reduce_partials(const double *const (&part)[2], 
     out[1] = K > 1 ? fin_block_sum(s[1], slot) : 0.0;
 }
 
-// Non-local part of a chunk's rows inside the local SpMV kernel (HaloFused, kernels.hpp).  acc0 / acc1: the
-// accumulators of this thread's two rows after the local entries; ys: CHUNK_ROWS doubles of LDS that the
-// kernel does not need any more.  Workgroup-uniform: chunks without boundary rows return at once.
-// TURN (the merged step_1x + SpMV kernel of a multi-rank GKOCG turn): what the neighbours have put is z, not p -- the
-// new p of a halo column is recomputed here from it and the OLD p of that column, which this rank keeps
-// (p_new = z + tmp p_old: the expression, scalars and operands of the owner's own update, hence its bits), and left
-// behind in the other of two halo-p buffers for the next turn.
+// ------------------------------------------------------------------------------------------
+// The peer-put halo exchange (PeerHalo, kernels.hpp): every step of the protocol, once
+// ------------------------------------------------------------------------------------------
 // wait accounting (DevScalars::halo_wait_ticks): the waiting lanes leave their wait in *longest (LDS, zeroed before),
 // one thread adds the workgroup's figure to the solve's counters afterwards
 __device__ __forceinline__ void note_wait(unsigned *longest, long long t0)
 {
     atomicMax(longest, (unsigned)min((long long)0xffffffffll, wall_clock64() - t0));
 }
-__device__ __forceinline__ void add_halo_wait(DevScalars *s, unsigned longest)
+
+// The poll: lane i < n_neigh waits for neighbour i's flag of exchange W.seq and leaves *timed_out = 1 when it does not
+// come.  No barrier in here: the caller has zeroed the two LDS words behind a barrier and reads them behind another.
+__device__ __forceinline__ void halo_poll(const HaloWait &W, int *timed_out, unsigned *longest)
 {
-    atomicAdd(&s->halo_wait_ticks, (unsigned long long)longest);
-    atomicAdd(&s->halo_waits, 1u);
+    if ((int)threadIdx.x < W.n_neigh) {
+        const long long t0 = wall_clock64();
+        for (;;) {
+            const unsigned long long f =
+                __hip_atomic_load(W.local_flag + threadIdx.x, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
+            if ((uint32_t)f == W.seq) break;
+            if (wall_clock64() - t0 > W.timeout_ticks) {
+                *timed_out = 1;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(2);
+        }
+        note_wait(longest, t0);
+    }
 }
 
+// Whose exchange (HaloOwner / MixedHaloOwner, kernels.hpp): is the launch gated, and the outcome of a workgroup's wait
+// (one thread calls it) -- the wait goes into the solve's counters; a neighbour that did not show up ends the solve on
+// every kernel's gate, and the host reports OGL_ERR_COMM.
+__device__ __forceinline__ bool mx_gated(const MixedScalars *m) { return m && (m->outer_stop || m->inner_stop); }
+// (also a rank's sums that did not arrive: mx_global_sums, kernels_mixed.hip)
+__device__ __forceinline__ void mx_comm_failed(MixedScalars *m, DevScalars *s)
+{
+    m->comm_error = 1;
+    m->outer_stop = 1;
+    m->inner_stop = 1;
+    if (s) s->stop = 1;
+}
+__device__ __forceinline__ bool halo_gated(const HaloOwner &o) { return o.gate && o.gate->stop; }
+__device__ __forceinline__ bool halo_gated(const MixedHaloOwner &o) { return mx_gated(o.gate); }
+__device__ __forceinline__ void halo_wait_outcome(const HaloOwner &o, unsigned longest, int timed_out)
+{
+    atomicAdd(&o.s->halo_wait_ticks, (unsigned long long)longest);
+    atomicAdd(&o.s->halo_waits, 1u);
+    if (timed_out) {
+        o.s->comm_error = 1;
+        o.s->stop = 1;
+    }
+}
+__device__ __forceinline__ void halo_wait_outcome(const MixedHaloOwner &o, unsigned longest, int timed_out)
+{
+    atomicAdd(&o.m->halo_wait_ticks, (unsigned long long)longest);
+    atomicAdd(&o.m->halo_waits, 1u);
+    if (timed_out) mx_comm_failed(o.m, o.s);
+}
+
+// A workgroup's wait for exchange W.seq; true (to every thread) when every neighbour's values have arrived.
+template <class Owner>
+__device__ __forceinline__ bool halo_wait(const HaloWait &W, const Owner &own)
+{
+    __shared__ int timed_out;
+    __shared__ unsigned waited;
+    if (threadIdx.x == 0) {
+        timed_out = 0;
+        waited = 0;
+    }
+    __syncthreads();
+    halo_poll(W, &timed_out, &waited);
+    __syncthreads();
+    if (threadIdx.x == 0) halo_wait_outcome(own, waited, timed_out);
+    return timed_out == 0;
+}
+
+// A boundary row continued over its non-local entries k0 .. k1 - 1 in stored order -- local first, then non-local, as
+// distributed::Matrix::apply does; acc: the row's accumulator after the local entries; R: the receive block's type.
+// TURN (the merged step_1x + SpMV kernel of a multi-rank GKOCG turn): what the neighbours have put is z, not p -- the
+// new p of a halo column is recomputed here from it and the OLD p of that column, which this rank keeps
+// (p_new = z + tmp p_old: the expression, scalars and operands of the owner's own update, hence its bits), and left
+// behind in the other of two halo-p buffers for the next turn.
+template <int MODE, bool TURN = false, class T, class R>
+__device__ __forceinline__ T halo_row(T acc, int k0, int k1, const int *cols, const T *vals, const R *recv, T tmp = 0,
+                                      const T *ph_in = nullptr, T *ph_out = nullptr)
+{
+    for (int k = k0; k < k1; ++k) {
+        const int c = cols[k];
+        T v = (T)recv[c];
+        if (TURN) {
+            v = v + tmp * ph_in[c];
+            ph_out[c] = v;
+        }
+        const T t = vals[k] * v;
+        acc = (MODE == SPMV_RESIDUAL) ? acc - t : acc + t;
+    }
+    return acc;
+}
+
+// Non-local part of a chunk's rows inside the local SpMV kernel (HaloFused, kernels.hpp).  acc0 / acc1: the
+// accumulators of this thread's two rows after the local entries; ys: CHUNK_ROWS doubles of LDS that the
+// kernel does not need any more.  Workgroup-uniform: chunks without boundary rows return at once.  The accumulators go
+// to LDS between the poll and its barrier, while the flags are on their way.
 template <int MODE, bool TURN = false>
 __device__ __forceinline__ void halo_fused_add(const HaloFused &H, int chunk, double &acc0, double &acc1, double *ys,
                                                double tmp = 0.0, const double *__restrict__ ph_in = nullptr,
@@ -149,45 +234,16 @@ __device__ __forceinline__ void halo_fused_add(const HaloFused &H, int chunk, do
         halo_waited = 0;
     }
     __syncthreads();
-    if ((int)threadIdx.x < H.n_neigh) {
-        const long long t0 = wall_clock64();
-        for (;;) {
-            const unsigned long long f =
-                __hip_atomic_load(H.local_flag + threadIdx.x, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
-            if ((uint32_t)f == H.seq) break;
-            if (wall_clock64() - t0 > H.timeout_ticks) {
-                halo_timed_out = 1;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        note_wait(&halo_waited, t0);
-    }
+    halo_poll(H.wait, &halo_timed_out, &halo_waited);
     ys[ROWS_PER_THREAD * threadIdx.x] = acc0;
     ys[ROWS_PER_THREAD * threadIdx.x + 1] = acc1;
     __syncthreads();
-    if (threadIdx.x == 0) add_halo_wait(H.s, halo_waited);
-    if (halo_timed_out) {  // a neighbour is gone: end the solve (y stays the local product)
-        if (threadIdx.x == 0) {
-            H.s->comm_error = 1;
-            H.s->stop = 1;
-        }
-        return;
-    }
+    if (threadIdx.x == 0) halo_wait_outcome(HaloOwner{nullptr, H.s}, halo_waited, halo_timed_out);
+    if (halo_timed_out) return;  // a neighbour is gone: the solve ends (y stays the local product)
     for (int i = b0 + threadIdx.x; i < b1; i += BLOCK) {
         const int li = H.boundary_rows[i] - chunk * CHUNK_ROWS;
-        double a = ys[li];
-        for (int k = H.entry_ptrs[i]; k < H.entry_ptrs[i + 1]; ++k) {
-            const int c = H.cols[k];
-            double v = H.recv[c];
-            if (TURN) {
-                v = v + tmp * ph_in[c];
-                ph_out[c] = v;
-            }
-            const double t = H.vals[k] * v;
-            a = (MODE == SPMV_RESIDUAL) ? a - t : a + t;
-        }
-        ys[li] = a;
+        ys[li] = halo_row<MODE, TURN>(ys[li], H.entry_ptrs[i], H.entry_ptrs[i + 1], H.cols, H.vals, H.recv, tmp, ph_in,
+                                      ph_out);
     }
     __syncthreads();
     acc0 = ys[ROWS_PER_THREAD * threadIdx.x];
@@ -232,21 +288,34 @@ __device__ __forceinline__ RowPair my_rows(int chunk, int n_rows)
     r.n = left >= ROWS_PER_THREAD ? ROWS_PER_THREAD : (left > 0 ? left : 0);
     return r;
 }
-__device__ __forceinline__ double2 ld2(const double *__restrict__ p, const RowPair &r)
+// the thread's two rows of a vector of doubles (one 16-byte access) or floats (one 8-byte access)
+template <class T>
+struct PairOf;
+template <>
+struct PairOf<double> {
+    typedef double2 type;
+};
+template <>
+struct PairOf<float> {
+    typedef float2 type;
+};
+template <class T>
+__device__ __forceinline__ typename PairOf<T>::type ld2(const T *__restrict__ p, const RowPair &r)
 {
-    double2 v;
+    typename PairOf<T>::type v;
     if (r.n == 2) {
-        v = *reinterpret_cast<const double2 *>(p + r.row);
+        v = *reinterpret_cast<const typename PairOf<T>::type *>(p + r.row);
     } else {
-        v.x = r.n == 1 ? p[r.row] : 0.0;
-        v.y = 0.0;
+        v.x = r.n == 1 ? p[r.row] : T(0);
+        v.y = T(0);
     }
     return v;
 }
-__device__ __forceinline__ void st2(double *__restrict__ p, const RowPair &r, double2 v)
+template <class T>
+__device__ __forceinline__ void st2(T *__restrict__ p, const RowPair &r, typename PairOf<T>::type v)
 {
     if (r.n == 2)
-        *reinterpret_cast<double2 *>(p + r.row) = v;
+        *reinterpret_cast<typename PairOf<T>::type *>(p + r.row) = v;
     else if (r.n == 1)
         p[r.row] = v.x;
 }
@@ -290,6 +359,34 @@ __device__ __forceinline__ void st2_stream(double *__restrict__ p, const RowPair
 }
 static_assert(ROWS_PER_THREAD == 2, "vector kernels are written for two rows per thread");
 
+// Position j of the send list goes to the neighbour whose block of the list holds it: its place in that neighbour's
+// receive segment for this rank (values of type T).
+template <class T>
+__device__ __forceinline__ T *halo_put_slot(const PeerHalo &P, int j)
+{
+    int i = 0;
+    while (i + 1 < P.wait.n_neigh && j >= P.send_off[i + 1]) ++i;
+    return P.segment<T>(i) + (j - P.send_off[i]);
+}
+// The signal behind a workgroup's puts: they are fenced at system scope, the workgroup takes a ticket, and the last of
+// the n_groups workgroups that put for this exchange stores the flags (and leaves the ticket at 0 for the next one).
+// *last: one LDS word.
+__device__ __forceinline__ void halo_signal_last(const PeerHalo &P, unsigned *ticket, unsigned n_groups, int *last)
+{
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        *last = atomicAdd(ticket, 1u) == n_groups - 1;
+        if (*last) *ticket = 0;
+    }
+    __syncthreads();
+    if (*last && (int)threadIdx.x < P.wait.n_neigh) {
+        __threadfence_system();
+        __hip_atomic_store(P.remote_flag[threadIdx.x], (unsigned long long)P.wait.seq, __ATOMIC_RELEASE,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 // Halo values of the SpMV that follows, put by the kernel that produces them: this chunk's send rows (v0, v1 = the
 // two rows of the thread) go straight into the neighbours' receive blocks -- through LDS, the row's owner holds it in
 // registers -- and the last such workgroup of the launch raises the flags.  Workgroup-uniform.
@@ -303,22 +400,9 @@ __device__ __forceinline__ void halo_put_chunk(const HaloPutFused &put, int chun
     __syncthreads();
     for (int k = s0 + threadIdx.x; k < s1; k += BLOCK) {
         const int j = put.send_pos[k];
-        int i = 0;
-        while (i + 1 < put.P.n_neigh && j >= put.P.send_off[i + 1]) ++i;
-        put.P.remote_recv[i][j - put.P.send_off[i]] = ps[put.send_idxs[j] - chunk * CHUNK_ROWS];
+        *halo_put_slot<double>(put.P, j) = ps[put.send_idxs[j] - chunk * CHUNK_ROWS];
     }
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        *last = atomicAdd(put.ticket, 1u) == (unsigned)put.n_put_chunks - 1;
-        if (*last) *put.ticket = 0;
-    }
-    __syncthreads();
-    if (*last && (int)threadIdx.x < put.P.n_neigh) {
-        __threadfence_system();
-        __hip_atomic_store(put.P.remote_flag[threadIdx.x], (unsigned long long)put.P.seq, __ATOMIC_RELEASE,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    halo_signal_last(put.P, put.ticket, (unsigned)put.n_put_chunks, last);
 }
 
 constexpr int FIN_VT = FIN_BLOCK / BLOCK;  // virtual finaliser threads per thread

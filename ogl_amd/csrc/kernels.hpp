@@ -115,10 +115,21 @@ enum SpmvMode { SPMV_PLAIN = 0, SPMV_RESIDUAL = 1 };
 // in stored order, which is what Ginkgo's advanced apply with alpha=-1, beta=1 evaluates).
 // dots.part != nullptr: also one partial of sum_i w_i*y_i (and y_i*y_i) per chunk of CHUNK_ROWS rows.
 // `gate` (may be nullptr): kernel returns immediately when gate->stop is set.
-struct SpmvDots {
-    const double *with = nullptr;  // w in sum_i w_i*y_i (CG: x itself; BiCGStab: rr or s)
-    double *part = nullptr;        // per-chunk partials of w.y, or nullptr
-    double *part_yy = nullptr;     // per-chunk partials of y.y (needs `part`), or nullptr
+// (T = float: the inner product of the mixed mode, whose partials are sums of products of the float64 casts)
+template <class T>
+struct SpmvDotsOf {
+    const T *with = nullptr;    // w in sum_i w_i*y_i (CG: x itself; BiCGStab: rr or s)
+    double *part = nullptr;     // per-chunk partials of w.y, or nullptr
+    double *part_yy = nullptr;  // per-chunk partials of y.y (needs `part`), or nullptr
+};
+using SpmvDots = SpmvDotsOf<double>;
+// What a waiter for halo exchange number `seq` needs (peer-put transport; PeerHalo below): lane i of a waiting workgroup
+// reads local_flag[i] until it carries `seq`, for at most timeout_ticks of the 100 MHz wall clock.
+struct HaloWait {
+    const unsigned long long *local_flag = nullptr;  // this rank's flags, one per neighbour
+    int32_t n_neigh = 0;
+    uint32_t seq = 0;
+    long long timeout_ticks = 0;
 };
 // Non-local part of the product inside the LOCAL kernel (peer-put transport): the workgroup of a chunk that
 // holds boundary rows waits for the neighbours' flags of this SpMV, then continues the accumulators of its
@@ -130,11 +141,8 @@ struct HaloFused {
     const int32_t *entry_ptrs = nullptr;
     const int32_t *cols = nullptr;
     const double *vals = nullptr;
-    const double *recv = nullptr;                    // this SpMV's receive block
-    const unsigned long long *local_flag = nullptr;  // this rank's flags, one per neighbour
-    int32_t n_neigh = 0;
-    uint32_t seq = 0;
-    long long timeout_ticks = 0;
+    const double *recv = nullptr;            // this SpMV's receive block
+    HaloWait wait;
     DevScalars *s = nullptr;                 // receives comm_error / stop when a neighbour does not show up
 };
 void launch_spmv(hipStream_t st, const DevCsr &A, int mode, const double *x, const double *b,
@@ -216,12 +224,6 @@ void launch_gather_coeffs_masked(hipStream_t st, int64_t n, const int32_t *map, 
 // the same into the value planes of a chunked layout (SellChunk), one workgroup per chunk
 void launch_gather_sell(hipStream_t st, int32_t n_chunks, const SellChunk *chunks, const int32_t *map,
                         const double *source, double *out);
-
-// y[row] (+/-)= sum_k vals[k] * recv[cols[k]] over the boundary rows, continuing y's accumulator.
-void launch_spmv_non_local(hipStream_t st, const DevHalo &H, int mode, const double *recv,
-                           double *y, const DevScalars *gate);
-void launch_pack(hipStream_t st, const DevHalo &H, const double *x, double *send,
-                 const DevScalars *gate);
 
 // coeffs[i] = source[ldu_mapping[i]]   (row_gather, HostMatrix.C:700-703)
 void launch_gather_coeffs(hipStream_t st, int32_t nnz, const int32_t *ldu_mapping,
@@ -696,21 +698,43 @@ void launch_peer_allreduce(hipStream_t st, const PeerArgs &pa, double *vals, int
 // Peer-put halo exchange (SURVEY.md §8e "pack x[send_idxs] then peer-to-peer put to each neighbour
 // over xGMI").  A rank's IPC allocation is [mailbox | control slots | arena]; every solver with
 // processor interfaces owns an arena block [flags 2 x n_neigh | recv parity 0 | recv parity 1].
-// SpMV number `seq` of a solver: k_pack_put stores x[send_idxs] straight into the neighbours' recv
-// segments of parity seq & 1, k_halo_signal then stores `seq` into their flag for this rank; the
-// local SpMV runs; k_halo_wait spins until every neighbour's flag carries `seq`; the non-local
-// kernel reads the recv block.  Two parities: a neighbour can be at most one SpMV ahead.
+// SpMV number `seq` of a solver, every step written once for 8-byte values (the double path) and 4-byte values (the inner
+// product of the mixed mode, which views the same receive blocks as floats):
+//   put    x[send_idxs] goes straight into the neighbours' recv segments of parity seq & 1, every workgroup fences its
+//          stores at system scope and takes a ticket, and the last one stores `seq` into the neighbours' flags for this
+//          rank: k_pack_put_signal -- or the kernel that produces x, for the chunks it owns (HaloPutFused below)
+//   local  the local SpMV runs while the values fly
+//   wait + non-local, one of
+//          inside the local kernel: the workgroup of a chunk with boundary rows polls this rank's flags until all
+//            carry `seq`, then continues those rows over their non-local entries (HaloFused; the default, doubles only)
+//          k_halo_finish, one workgroup per such chunk: the same, then the chunk's dot partials (haloFused 0, mixed mode)
+//          k_halo_wait, ONE workgroup; then k_spmv_non_local over the boundary rows and the boundary chunks' partials
+//            again (peerSafeWait: ranks that share a device)
+// Two parities: a neighbour can be at most one SpMV ahead.  The other transports pack into a send buffer of doubles
+// (k_pack), exchange it through Comm and run k_spmv_non_local on the arrived block.
 constexpr size_t PEER_CTRL_WORDS = (size_t)PEER_MAX_RANKS * 4;  // per source rank: epoch + 3 words
 constexpr size_t PEER_ARENA_OFF = PEER_BOX_WORDS + PEER_CTRL_WORDS;  // 8-byte words from the base
 constexpr int PEER_MAX_NEIGH = 16;
 struct PeerHalo {
-    int32_t n_neigh = 0;
-    uint32_t seq = 0;
-    long long timeout_ticks = PEER_DEFAULT_TIMEOUT_TICKS;
+    HaloWait wait{nullptr, 0, 0, PEER_DEFAULT_TIMEOUT_TICKS};
     int32_t send_off[PEER_MAX_NEIGH + 1] = {};             // send buffer blocks, by neighbour
-    double *remote_recv[PEER_MAX_NEIGH] = {};              // neighbour i's segment for this rank
+    void *remote_recv[PEER_MAX_NEIGH] = {};                // neighbour i's segment for this rank, values of one width
     unsigned long long *remote_flag[PEER_MAX_NEIGH] = {};  // neighbour i's flag for this rank
-    const unsigned long long *local_flag = nullptr;        // this rank's flags, one per neighbour
+    template <class T>
+    __host__ __device__ T *segment(int i) const { return static_cast<T *>(remote_recv[i]); }
+};
+// Whose exchange it is: the gate its kernels return on (may be nullptr) and the scalars that take the outcome of a wait
+// -- the wait's length, and comm_error with the stops when a neighbour does not show up within the time-out
+// (device_common.hpp: halo_gated, halo_wait_outcome).
+struct MixedScalars;
+struct HaloOwner {  // the double path
+    const DevScalars *gate = nullptr;
+    DevScalars *s = nullptr;
+};
+struct MixedHaloOwner {  // the inner product of the mixed mode: both stops in `m`, the stop of `s`
+    const MixedScalars *gate = nullptr;
+    MixedScalars *m = nullptr;
+    DevScalars *s = nullptr;
 };
 // launch_cg_step1x's `put` (chunk_sptr != nullptr): the workgroups whose chunks hold send rows store the p they
 // have just formed straight into the neighbours' receive blocks, and the last of them signals -- the pack kernel
@@ -723,20 +747,30 @@ struct HaloPutFused {
     unsigned *ticket = nullptr;
     int32_t n_put_chunks = 0;             // chunks that hold send rows
 };
-void launch_pack_put(hipStream_t st, const DevHalo &H, const PeerHalo &P, const double *x,
-                     const DevScalars *gate);
-void launch_halo_signal(hipStream_t st, const PeerHalo &P, const DevScalars *gate);
-// the same three steps in two launches: [pack + put + signal by the last workgroup] and, after the
-// local SpMV, [wait + y += A_non_local recv + dot partials of the chunks that hold boundary rows]
-// (one workgroup per such chunk; chunk_row_ptr = ranges of H.boundary_rows per listed chunk)
-void launch_pack_put_signal(hipStream_t st, const DevHalo &H, const PeerHalo &P, const double *x,
-                            const DevScalars *gate, unsigned *ticket);
-void launch_halo_finish(hipStream_t st, const DevHalo &H, int mode, int32_t n_rows,
-                        const int32_t *chunk_list, const int32_t *chunk_row_ptr, int32_t n_chunks_b,
-                        const double *recv, double *y, const SpmvDots &dots, const PeerHalo &P,
-                        const DevScalars *gate, DevScalars *s);
-// `s` receives comm_error / stop when a neighbour does not show up within the timeout
-void launch_halo_wait(hipStream_t st, const PeerHalo &P, const DevScalars *gate, DevScalars *s);
+// The launches of the steps above (kernels_comm.hip), instantiated for <double, HaloOwner> and <float, MixedHaloOwner>.
+// Every kernel returns at once past a stop of own.gate.  nl_vals: the non-local coefficients as T (DevHalo::vals or
+// their fp32 twin); H.vals itself is not read.
+// put + signal by the last workgroup (P made for values of sizeof(T): ogl_solver::next_exchange)
+template <class T, class Owner>
+void launch_pack_put_signal(hipStream_t st, const DevHalo &H, const PeerHalo &P, const T *x, const Owner &own,
+                            unsigned *ticket);
+// wait + y (+/-)= A_non_local recv + the dot partials of the chunks that hold boundary rows, over the finished y (one
+// workgroup per such chunk; chunk_row_ptr = ranges of H.boundary_rows per listed chunk); a time-out leaves y the local product
+template <class T, class Owner>
+void launch_halo_finish(hipStream_t st, const DevHalo &H, const T *nl_vals, int mode, int32_t n_rows,
+                        const int32_t *chunk_list, const int32_t *chunk_row_ptr, int32_t n_chunks_b, const T *recv, T *y,
+                        const SpmvDotsOf<T> &dots, const PeerHalo &P, const Owner &own);
+// the single waiting workgroup of a rank
+template <class Owner>
+void launch_halo_wait(hipStream_t st, const PeerHalo &P, const Owner &own);
+// y[row] (+/-)= sum_k nl_vals[k] * (T)recv[cols[k]] over the boundary rows, continuing y's accumulator; R = T (a receive
+// block of the peer mesh) or double (the block Comm::exchange filled, narrowed on read for T = float)
+template <class T, class R, class Owner>
+void launch_spmv_non_local(hipStream_t st, const DevHalo &H, const T *nl_vals, int mode, const R *recv, T *y,
+                           const Owner &own);
+// send[j] = (double)x[send_idxs[j]]: Comm::exchange carries doubles (exact both ways for T = float)
+template <class T, class Owner>
+void launch_pack(hipStream_t st, const DevHalo &H, const T *x, double *send, const Owner &own);
 // control message to another rank: dst[1..3] = w1..w3, then dst[0] = w0 (the epoch)
 void launch_peer_post(hipStream_t st, unsigned long long *dst, unsigned long long w0,
                       unsigned long long w1, unsigned long long w2, unsigned long long w3);
@@ -835,28 +869,11 @@ void launch_mixed_step1(hipStream_t st, int32_t n, float *p, const float *z, con
 // u += a p, r -= a q, z = r * inv_d; the partials of rho, tau
 void launch_mixed_step2(hipStream_t st, int32_t n, float *u, float *r, const float *p, const float *q, const float *inv_d,
                         float *z, double *part_rho, double *part_tau, MixedScalars *m);
-// The halo of the inner product on several ranks.  Every kernel returns at once past a stop of `gate` (may be nullptr);
-// a neighbour that does not show up within P.timeout_ticks raises comm_error and both stops in `m` and the stop of `s`.
-// Peer mesh: p32 at the send rows as 4-byte values into the neighbours' receive segments (P.remote_recv holds float
-// addresses: ogl_solver::peer_halo_args with f32), flags by the last workgroup through `ticket` ...
-void launch_mixed_put(hipStream_t st, const DevHalo &H, const PeerHalo &P, const float *x, const MixedScalars *gate,
-                      unsigned *ticket);
-// ... and after the local product one workgroup per boundary chunk: wait, q_i = q_i + a32nl_k recv32[col_k] in stored
-// order, the chunk's pi partial over the finished q (part != nullptr) ...
-void launch_mixed_halo_finish(hipStream_t st, const DevHalo &H, const float *nl_vals, int32_t n_rows,
-                              const int32_t *chunk_list, const int32_t *chunk_row_ptr, int32_t n_chunks_b, const float *recv,
-                              const float *x, float *y, double *part, const PeerHalo &P, const MixedScalars *gate,
-                              MixedScalars *m, DevScalars *s);
-// ... or (peerSafeWait) a single waiting workgroup, then launch_mixed_non_local and launch_mixed_pi_chunks
-void launch_mixed_halo_wait(hipStream_t st, const PeerHalo &P, const MixedScalars *gate, MixedScalars *m, DevScalars *s);
-// RCCL / host-buffer rungs: send[j] = (double)x[send_idxs[j]] for Comm::exchange (exact), narrowed again on arrival
-void launch_mixed_pack_wide(hipStream_t st, const DevHalo &H, const float *x, double *send, const MixedScalars *gate);
-// the non-local part over the boundary rows; exactly one of recv32 / recv64 (narrowed on read) is given
-void launch_mixed_non_local(hipStream_t st, const DevHalo &H, const float *nl_vals, const float *recv32, const double *recv64,
-                            float *y, const MixedScalars *gate);
-// the pi partials of the listed (boundary) chunks again, in the local kernels' tree
-void launch_mixed_pi_chunks(hipStream_t st, int32_t n, const float *x, const float *y, double *part,
-                            const MixedScalars *gate, const int32_t *chunk_list, int32_t n_list);
+// (The halo of the inner product on several ranks: the launches of the peer-put exchange above with <float, MixedHaloOwner>.)
+// launch_partials_dot_chunks for the inner product's operands: the pi partials of the listed (boundary) chunks, formed
+// again over the finished q in the local kernels' tree (k_mx_pi_chunks)
+void launch_partials_dot_chunks(hipStream_t st, int32_t n, const float *x, const float *y, double *part,
+                                const MixedScalars *gate, const int32_t *chunk_list, int32_t n_list);
 void launch_mixed_add(hipStream_t st, int32_t n, double *x, const float *u, const MixedScalars *m);
 // scatter: out[new_id[i]] = in[i]; gather: out[i] = in[new_id[i]]
 void launch_mixed_permute(hipStream_t st, int32_t n, const int32_t *new_id, const float *in, float *out, bool gather);

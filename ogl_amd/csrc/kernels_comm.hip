@@ -21,120 +21,55 @@ __global__ __launch_bounds__(64) void k_peer_allreduce(PeerArgs pa, double *vals
     }
 }
 
-// ---- peer-put halo exchange (PeerHalo, kernels.hpp) ----
-__global__ __launch_bounds__(BLOCK) void k_pack_put(int n_send, const int *__restrict__ send_idxs,
-                                                    PeerHalo P, const double *__restrict__ x,
-                                                    const DevScalars *gate)
-{
-    if (gate && gate->stop) return;
-    const int j = blockIdx.x * BLOCK + threadIdx.x;
-    if (j >= n_send) return;
-    int i = 0;
-    while (i + 1 < P.n_neigh && j >= P.send_off[i + 1]) ++i;
-    P.remote_recv[i][j - P.send_off[i]] = x[send_idxs[j]];
-    __threadfence_system();  // the put has left this GPU before the kernel (and its signal) completes
-}
-
-// pack + signal in one launch: the last workgroup to finish (atomic ticket) stores the flags, after
+// ---- halo exchange (PeerHalo, kernels.hpp); T: the values' type, Owner: whose exchange (device_common.hpp) ----
+// pack + put + signal in one launch: the last workgroup to finish (atomic ticket) stores the flags, after
 // every workgroup's puts have been fenced at system scope.
-__global__ __launch_bounds__(BLOCK) void k_pack_put_signal(int n_send,
-                                                           const int *__restrict__ send_idxs,
-                                                           PeerHalo P, const double *__restrict__ x,
-                                                           const DevScalars *gate, unsigned *ticket)
+template <class T, class Owner>
+__global__ __launch_bounds__(BLOCK) void k_pack_put_signal(int n_send, const int *__restrict__ send_idxs, PeerHalo P,
+                                                           const T *__restrict__ x, Owner own, unsigned *ticket)
 {
-    if (gate && gate->stop) return;
+    if (halo_gated(own)) return;
     const int j = blockIdx.x * BLOCK + threadIdx.x;
-    if (j < n_send) {
-        int i = 0;
-        while (i + 1 < P.n_neigh && j >= P.send_off[i + 1]) ++i;
-        P.remote_recv[i][j - P.send_off[i]] = x[send_idxs[j]];
-    }
-    __threadfence_system();
-    __syncthreads();
+    if (j < n_send) *halo_put_slot<T>(P, j) = x[send_idxs[j]];
     __shared__ int last;
-    if (threadIdx.x == 0) {
-        last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-        if (last) *ticket = 0;
-    }
-    __syncthreads();
-    if (last && (int)threadIdx.x < P.n_neigh) {
-        __threadfence_system();
-        __hip_atomic_store(P.remote_flag[threadIdx.x], (unsigned long long)P.seq, __ATOMIC_RELEASE,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    halo_signal_last(P, ticket, gridDim.x, &last);
 }
 
 // wait + "y += A_non_local recv" + the dot partials of the touched chunks in one launch: one
 // workgroup per chunk that holds boundary rows.  Same accumulation order as k_spmv_non_local and
-// the same per-chunk tree as k_partials, so nothing changes in the bits.
-template <int MODE, int NDOT>
-__global__ __launch_bounds__(BLOCK) void k_halo_finish(int n_rows,
+// the same per-chunk tree as k_partials (T = float: as the local kernels of the mixed mode, products of the
+// float64 casts), so nothing changes in the bits.
+// (W and own come first: behind the twelve other arguments the NDOT = 2 instantiations take 10 SGPRs more)
+template <int MODE, int NDOT, class T, class Owner>
+__global__ __launch_bounds__(BLOCK) void k_halo_finish(HaloWait W, Owner own, int n_rows,
                                                        const int *__restrict__ chunk_list,
                                                        const int *__restrict__ chunk_row_ptr,
                                                        const int *__restrict__ boundary_rows,
-                                                       const int *__restrict__ entry_ptrs,
-                                                       const int *__restrict__ cols,
-                                                       const double *__restrict__ vals,
-                                                       const double *recv, double *y,
-                                                       const double *w, double *part,
-                                                       double *part_yy, PeerHalo P,
-                                                       const DevScalars *gate, DevScalars *s)
+                                                       const int *__restrict__ entry_ptrs, const int *__restrict__ cols,
+                                                       const T *__restrict__ vals, const T *recv, T *y, const T *w,
+                                                       double *part, double *part_yy)
 {
     __shared__ double slot[N_WAVES];
-    __shared__ int timed_out;
-    __shared__ unsigned waited;
-    if (gate && gate->stop) return;
-    if (threadIdx.x == 0) {
-        timed_out = 0;
-        waited = 0;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < P.n_neigh) {
-        const long long t0 = wall_clock64();
-        for (;;) {
-            const unsigned long long f = __hip_atomic_load(P.local_flag + threadIdx.x, __ATOMIC_ACQUIRE,
-                                                           __HIP_MEMORY_SCOPE_SYSTEM);
-            if ((uint32_t)f == P.seq) break;
-            if (wall_clock64() - t0 > P.timeout_ticks) {
-                timed_out = 1;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        note_wait(&waited, t0);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) add_halo_wait(s, waited);
-    if (timed_out) {  // a neighbour is gone: end the solve (y stays the local product)
-        if (threadIdx.x == 0) {
-            s->comm_error = 1;
-            s->stop = 1;
-        }
-        return;
-    }
+    if (halo_gated(own)) return;
+    if (!halo_wait(W, own)) return;  // (y stays the local product)
     const int chunk = chunk_list[blockIdx.x];
     for (int i = chunk_row_ptr[blockIdx.x] + threadIdx.x; i < chunk_row_ptr[blockIdx.x + 1]; i += BLOCK) {
         const int row = boundary_rows[i];
-        double acc = y[row];
-        for (int k = entry_ptrs[i]; k < entry_ptrs[i + 1]; ++k) {
-            const double t = vals[k] * recv[cols[k]];
-            acc = (MODE == SPMV_RESIDUAL) ? acc - t : acc + t;
-        }
-        y[row] = acc;
+        y[row] = halo_row<MODE>(y[row], entry_ptrs[i], entry_ptrs[i + 1], cols, vals, recv);
     }
     if (NDOT >= 1) {
         __threadfence_block();
         __syncthreads();
         const RowPair rp = my_rows(chunk, n_rows);
-        const double2 vy = ld2(y, rp), vw = ld2(w, rp);
+        const auto vy = ld2(y, rp), vw = ld2(w, rp);
         double d = 0.0, d2 = 0.0;
         if (rp.n > 0) {
-            d += vw.x * vy.x;
-            d2 += vy.x * vy.x;
+            d += (double)vw.x * (double)vy.x;
+            d2 += (double)vy.x * (double)vy.x;
         }
         if (rp.n > 1) {
-            d += vw.y * vy.y;
-            d2 += vy.y * vy.y;
+            d += (double)vw.y * (double)vy.y;
+            d2 += (double)vy.y * (double)vy.y;
         }
         const double sm = block_sum(d, slot);
         if (threadIdx.x == 0) part[chunk] = sm;
@@ -145,46 +80,35 @@ __global__ __launch_bounds__(BLOCK) void k_halo_finish(int n_rows,
     }
 }
 
-__global__ __launch_bounds__(64) void k_halo_signal(PeerHalo P, const DevScalars *gate)
+// peerSafeWait: the single waiting workgroup of a rank
+template <class Owner>
+__global__ __launch_bounds__(64) void k_halo_wait(HaloWait W, Owner own)
 {
-    if (gate && gate->stop) return;
-    const int i = threadIdx.x;
-    if (i < P.n_neigh)
-        __hip_atomic_store(P.remote_flag[i], (unsigned long long)P.seq, __ATOMIC_RELEASE,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
+    if (halo_gated(own)) return;
+    (void)halo_wait(W, own);
 }
 
-__global__ __launch_bounds__(64) void k_halo_wait(PeerHalo P, const DevScalars *gate, DevScalars *s)
+// y[row] (+/-)= A_non_local(row,:) * recv, continuing the accumulator the local kernel stored.
+template <int MODE, class T, class R, class Owner>
+__global__ __launch_bounds__(BLOCK) void k_spmv_non_local(int n_boundary, const int *__restrict__ boundary_rows,
+                                                          const int *__restrict__ entry_ptrs,
+                                                          const int *__restrict__ cols, const T *__restrict__ vals,
+                                                          const R *__restrict__ recv, T *__restrict__ y, Owner own)
 {
-    __shared__ int timed_out;
-    __shared__ unsigned waited;
-    if (gate && gate->stop) return;
-    if (threadIdx.x == 0) {
-        timed_out = 0;
-        waited = 0;
-    }
-    __syncthreads();
-    const int i = threadIdx.x;
-    if (i < P.n_neigh) {
-        const long long t0 = wall_clock64();
-        for (;;) {
-            const unsigned long long w =
-                __hip_atomic_load(P.local_flag + i, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
-            if ((uint32_t)w == P.seq) break;
-            if (wall_clock64() - t0 > P.timeout_ticks) {
-                timed_out = 1;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        note_wait(&waited, t0);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) add_halo_wait(s, waited);
-    if (threadIdx.x == 0 && timed_out) {  // a neighbour is gone: end the solve
-        s->comm_error = 1;
-        s->stop = 1;
-    }
+    if (halo_gated(own)) return;
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_boundary) return;
+    const int row = boundary_rows[i];
+    y[row] = halo_row<MODE>(y[row], entry_ptrs[i], entry_ptrs[i + 1], cols, vals, recv);
+}
+
+template <class T, class Owner>
+__global__ __launch_bounds__(BLOCK) void k_pack(int n_send, const int *__restrict__ send_idxs, const T *__restrict__ x,
+                                                double *__restrict__ send, Owner own)
+{
+    if (halo_gated(own)) return;
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n_send) send[i] = (double)x[send_idxs[i]];
 }
 
 __global__ void k_peer_post(unsigned long long *dst, unsigned long long w0, unsigned long long w1,
@@ -208,33 +132,26 @@ void launch_peer_allreduce(hipStream_t st, const PeerArgs &pa, double *vals, int
     hipLaunchKernelGGL(k_peer_allreduce, dim3(1), dim3(64), 0, st, pa, vals, n, error);
 }
 
-void launch_pack_put(hipStream_t st, const DevHalo &H, const PeerHalo &P, const double *x,
-                     const DevScalars *gate)
+template <class T, class Owner>
+void launch_pack_put_signal(hipStream_t st, const DevHalo &H, const PeerHalo &P, const T *x, const Owner &own,
+                            unsigned *ticket)
 {
     if (H.n_send == 0) return;
-    hipLaunchKernelGGL(k_pack_put, dim3(blocks_for(H.n_send)), dim3(BLOCK), 0, st, H.n_send,
-                       H.send_idxs, P, x, gate);
+    hipLaunchKernelGGL((k_pack_put_signal<T, Owner>), dim3(blocks_for(H.n_send)), dim3(BLOCK), 0, st, H.n_send,
+                       H.send_idxs, P, x, own, ticket);
 }
 
-void launch_pack_put_signal(hipStream_t st, const DevHalo &H, const PeerHalo &P, const double *x,
-                            const DevScalars *gate, unsigned *ticket)
-{
-    if (H.n_send == 0) return;
-    hipLaunchKernelGGL(k_pack_put_signal, dim3(blocks_for(H.n_send)), dim3(BLOCK), 0, st, H.n_send,
-                       H.send_idxs, P, x, gate, ticket);
-}
-
-void launch_halo_finish(hipStream_t st, const DevHalo &H, int mode, int32_t n_rows,
-                        const int32_t *chunk_list, const int32_t *chunk_row_ptr, int32_t n_chunks_b,
-                        const double *recv, double *y, const SpmvDots &dots, const PeerHalo &P,
-                        const DevScalars *gate, DevScalars *s)
+template <class T, class Owner>
+void launch_halo_finish(hipStream_t st, const DevHalo &H, const T *nl_vals, int mode, int32_t n_rows,
+                        const int32_t *chunk_list, const int32_t *chunk_row_ptr, int32_t n_chunks_b, const T *recv, T *y,
+                        const SpmvDotsOf<T> &dots, const PeerHalo &P, const Owner &own)
 {
     if (n_chunks_b == 0) return;
     const dim3 grid(n_chunks_b), block(BLOCK);
-#define OGL_HF(MODE, NDOT)                                                                        \
-    hipLaunchKernelGGL((k_halo_finish<MODE, NDOT>), grid, block, 0, st, n_rows, chunk_list,       \
-                       chunk_row_ptr, H.boundary_rows, H.entry_ptrs, H.cols, H.vals, recv, y,     \
-                       dots.with, dots.part, dots.part_yy, P, gate, s)
+#define OGL_HF(MODE, NDOT)                                                                                       \
+    hipLaunchKernelGGL((k_halo_finish<MODE, NDOT, T, Owner>), grid, block, 0, st, P.wait, own, n_rows, chunk_list, \
+                       chunk_row_ptr, H.boundary_rows, H.entry_ptrs, H.cols, nl_vals, recv, y, dots.with, dots.part,   \
+                       dots.part_yy)
     if (mode == SPMV_RESIDUAL) {
         OGL_HF(SPMV_RESIDUAL, 0);
     } else if (dots.part && dots.part_yy) {
@@ -247,17 +164,52 @@ void launch_halo_finish(hipStream_t st, const DevHalo &H, int mode, int32_t n_ro
 #undef OGL_HF
 }
 
-void launch_halo_signal(hipStream_t st, const PeerHalo &P, const DevScalars *gate)
+template <class Owner>
+void launch_halo_wait(hipStream_t st, const PeerHalo &P, const Owner &own)
 {
-    if (P.n_neigh == 0) return;
-    hipLaunchKernelGGL(k_halo_signal, dim3(1), dim3(64), 0, st, P, gate);
+    if (P.wait.n_neigh == 0) return;
+    hipLaunchKernelGGL(k_halo_wait<Owner>, dim3(1), dim3(64), 0, st, P.wait, own);
 }
 
-void launch_halo_wait(hipStream_t st, const PeerHalo &P, const DevScalars *gate, DevScalars *s)
+template <class T, class R, class Owner>
+void launch_spmv_non_local(hipStream_t st, const DevHalo &H, const T *nl_vals, int mode, const R *recv, T *y,
+                           const Owner &own)
 {
-    if (P.n_neigh == 0) return;
-    hipLaunchKernelGGL(k_halo_wait, dim3(1), dim3(64), 0, st, P, gate, s);
+    if (H.n_boundary_rows == 0) return;
+    const dim3 grid(blocks_for(H.n_boundary_rows)), block(BLOCK);
+    if (mode == SPMV_RESIDUAL)
+        hipLaunchKernelGGL((k_spmv_non_local<SPMV_RESIDUAL, T, R, Owner>), grid, block, 0, st, H.n_boundary_rows,
+                           H.boundary_rows, H.entry_ptrs, H.cols, nl_vals, recv, y, own);
+    else
+        hipLaunchKernelGGL((k_spmv_non_local<SPMV_PLAIN, T, R, Owner>), grid, block, 0, st, H.n_boundary_rows,
+                           H.boundary_rows, H.entry_ptrs, H.cols, nl_vals, recv, y, own);
 }
+
+template <class T, class Owner>
+void launch_pack(hipStream_t st, const DevHalo &H, const T *x, double *send, const Owner &own)
+{
+    if (H.n_send == 0) return;
+    hipLaunchKernelGGL((k_pack<T, Owner>), dim3(blocks_for(H.n_send)), dim3(BLOCK), 0, st, H.n_send, H.send_idxs, x,
+                       send, own);
+}
+
+// the two owners of an exchange: the double path, and the inner product of the mixed mode (4-byte values on the peer mesh,
+// widened doubles through Comm::exchange).  One dispatcher serves both, so the float set holds three kernels that the
+// mixed mode never launches: its product is SPMV_PLAIN with at most one partial array.
+#define OGL_HALO_LAUNCHES(T, Owner)                                                                                    \
+    template void launch_pack_put_signal(hipStream_t, const DevHalo &, const PeerHalo &, const T *, const Owner &,     \
+                                         unsigned *);                                                                  \
+    template void launch_halo_finish(hipStream_t, const DevHalo &, const T *, int, int32_t, const int32_t *,           \
+                                     const int32_t *, int32_t, const T *, T *, const SpmvDotsOf<T> &, const PeerHalo &, \
+                                     const Owner &);                                                                   \
+    template void launch_halo_wait(hipStream_t, const PeerHalo &, const Owner &);                                      \
+    template void launch_spmv_non_local(hipStream_t, const DevHalo &, const T *, int, const T *, T *, const Owner &);  \
+    template void launch_pack(hipStream_t, const DevHalo &, const T *, double *, const Owner &);
+OGL_HALO_LAUNCHES(double, HaloOwner)
+OGL_HALO_LAUNCHES(float, MixedHaloOwner)
+template void launch_spmv_non_local(hipStream_t, const DevHalo &, const float *, int, const double *, float *,
+                                    const MixedHaloOwner &);
+#undef OGL_HALO_LAUNCHES
 
 void launch_peer_post(hipStream_t st, unsigned long long *dst, unsigned long long w0,
                       unsigned long long w1, unsigned long long w2, unsigned long long w3)

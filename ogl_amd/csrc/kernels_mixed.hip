@@ -13,25 +13,6 @@ namespace ogl {
 
 namespace {
 
-__device__ __forceinline__ float2 ld2f(const float *__restrict__ p, const RowPair &r)
-{
-    float2 v;
-    if (r.n == 2) {
-        v = *reinterpret_cast<const float2 *>(p + r.row);
-    } else {
-        v.x = r.n == 1 ? p[r.row] : 0.0f;
-        v.y = 0.0f;
-    }
-    return v;
-}
-__device__ __forceinline__ void st2f(float *__restrict__ p, const RowPair &r, float2 v)
-{
-    if (r.n == 2)
-        *reinterpret_cast<float2 *>(p + r.row) = v;
-    else if (r.n == 1)
-        p[r.row] = v.x;
-}
-__device__ __forceinline__ bool mx_gated(const MixedScalars *m) { return m && (m->outer_stop || m->inner_stop); }
 __device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }  // (false for NaN)
 
 // out[i] = fl32(map ? src[map[i]] (0 where map[i] < 0) : src[i]); *bad = the smallest i whose value is finite in fp64
@@ -67,13 +48,13 @@ struct MxOffsets {
 template <int EPI>
 __device__ __forceinline__ void mg_epilogue(const MgEpi &e, const RowPair &rp, const float2 &xd, const float2 &acc)
 {
-    const float2 bv = ld2f(e.b, rp);
+    const float2 bv = ld2(e.b, rp);
     float2 o;
     if (EPI == MX_EPI_RESIDUAL) {
         o.x = bv.x - acc.x;
         o.y = bv.y - acc.y;
     } else {
-        const float2 dv = ld2f(e.inv_d, rp);
+        const float2 dv = ld2(e.inv_d, rp);
         const float w = (float)MG_OMEGA;
         const float u0 = w * ((bv.x - acc.x) * dv.x), u1 = w * ((bv.y - acc.y) * dv.y);
         o.x = xd.x + u0;
@@ -85,7 +66,7 @@ __device__ __forceinline__ void mg_epilogue(const MgEpi &e, const RowPair &rp, c
         z.y = (double)o.y;
         st2(e.out64, rp, z);
     } else {
-        st2f(e.out, rp, o);
+        st2(e.out, rp, o);
     }
 }
 
@@ -112,7 +93,7 @@ __global__ __launch_bounds__(BLOCK) void k_mx_spmv_sym(int n_rows, int n_chunks,
     const float *own = planes + (long)chunk * (ND * CHUNK_ROWS) + t * ROWS_PER_THREAD;
 #pragma unroll
     for (int j = 0; j < ND; ++j) up[j] = *reinterpret_cast<const float2 *>(own + (long)j * CHUNK_ROWS);
-    const float2 xd = ld2f(x, rp);
+    const float2 xd = ld2(x, rp);
     // every load is issued whatever the mask says, at an index clamped into its array (the mask decides what is used)
     const int last = n_rows - 1, last_pair = last & ~1;  // (the vectors are allocated past n_rows)
     float2 lo[ND], xl[ND], xu[ND];
@@ -160,7 +141,7 @@ __global__ __launch_bounds__(BLOCK) void k_mx_spmv_sym(int n_rows, int n_chunks,
         mg_epilogue<EPI>(epi, rp, xd, acc);
         return;
     }
-    st2f(y, rp, acc);
+    st2(y, rp, acc);
     if (EPI == MX_EPI_PI && part) {
         double d = 0.0;
         if (rp.n > 0) d += (double)xd.x * (double)acc.x;
@@ -279,13 +260,13 @@ __global__ __launch_bounds__(BLOCK) void k_mx_start(int n, const double *__restr
     zero.x = zero.y = 0.0f;
     zv = rv;
     if (inv_d) {
-        const float2 dv = ld2f(inv_d, rp);
+        const float2 dv = ld2(inv_d, rp);
         zv.x = rv.x * dv.x;
         zv.y = rv.y * dv.y;
-        st2f(z, rp, zv);
+        st2(z, rp, zv);
     }
-    st2f(r32, rp, rv);
-    st2f(u, rp, zero);
+    st2(r32, rp, rv);
+    st2(u, rp, zero);
     double a = 0.0, b = 0.0;
     if (rp.n > 0) {
         a += (double)rv.x * (double)zv.x;
@@ -310,14 +291,14 @@ __global__ __launch_bounds__(BLOCK) void k_mx_step1(int n, float *__restrict__ p
     const int use_beta = m->use_beta;
     const float b32 = m->b32;
     const RowPair rp = my_rows(blockIdx.x, n);
-    float2 zv = ld2f(z, rp);
+    float2 zv = ld2(z, rp);
     if (use_beta) {
-        const float2 pv = ld2f(p, rp);
+        const float2 pv = ld2(p, rp);
         const float t0 = b32 * pv.x, t1 = b32 * pv.y;
         zv.x = zv.x + t0;
         zv.y = zv.y + t1;
     }
-    st2f(p, rp, zv);
+    st2(p, rp, zv);
 }
 
 // steps 4 and 5: u += a p, r -= a q, z = r * inv_d32; partials of rho = wide(r, z), tau = wide1(r)
@@ -332,21 +313,21 @@ __global__ __launch_bounds__(BLOCK) void k_mx_step2(int n, float *__restrict__ u
     const float a32 = m->a32;
     const int chunk = blockIdx.x;
     const RowPair rp = my_rows(chunk, n);
-    const float2 pv = ld2f(p, rp), qv = ld2f(q, rp);
-    float2 uv = ld2f(u, rp), rv = ld2f(r, rp);
+    const float2 pv = ld2(p, rp), qv = ld2(q, rp);
+    float2 uv = ld2(u, rp), rv = ld2(r, rp);
     const float up0 = a32 * pv.x, up1 = a32 * pv.y, rq0 = a32 * qv.x, rq1 = a32 * qv.y;
     uv.x = uv.x + up0;
     uv.y = uv.y + up1;
     rv.x = rv.x - rq0;
     rv.y = rv.y - rq1;
-    st2f(u, rp, uv);
-    st2f(r, rp, rv);
+    st2(u, rp, uv);
+    st2(r, rp, rv);
     float2 zv = rv;
     if (inv_d) {
-        const float2 dv = ld2f(inv_d, rp);
+        const float2 dv = ld2(inv_d, rp);
         zv.x = rv.x * dv.x;
         zv.y = rv.y * dv.y;
-        st2f(z, rp, zv);
+        st2(z, rp, zv);
     }
     double a = 0.0, b = 0.0;
     if (rp.n > 0) {
@@ -372,7 +353,7 @@ __global__ __launch_bounds__(BLOCK) void k_mx_add(int n, double *__restrict__ x,
     if (m->outer_stop || m->inner_nonfinite) return;
     const double S = m->S;
     const RowPair rp = my_rows(blockIdx.x, n);
-    const float2 uv = ld2f(u, rp);
+    const float2 uv = ld2(u, rp);
     double2 xv = ld2(x, rp);
     const double t0 = S * (double)uv.x, t1 = S * (double)uv.y;
     xv.x = xv.x + t0;
@@ -392,159 +373,17 @@ __global__ __launch_bounds__(BLOCK) void k_mx_permute(int n, const int *__restri
         out[new_id[i]] = in[i];
 }
 
-// Several ranks: a neighbour's values or a rank's sums did not arrive within the time-out -- the solve ends on every
-// kernel's gate and the host reports OGL_ERR_COMM
-__device__ __forceinline__ void mx_comm_failed(MixedScalars *m, DevScalars *s)
-{
-    m->comm_error = 1;
-    m->outer_stop = 1;
-    m->inner_stop = 1;
-    if (s) s->stop = 1;
-}
-
-// ------------------------------------------------------------------------------------------
-// the halo of the inner product on several ranks ("several ranks"): q = A32 p continues, for a
-// boundary row, acc = q_i; acc = acc + a32nl_k * recv32[col_k] over the row's non-local entries in stored order -- the
-// order of k_halo_finish and k_spmv_non_local on binary32 operands
-// ------------------------------------------------------------------------------------------
-// pack + put + signal, the fp32 form of k_pack_put_signal: P.remote_recv[] holds the float addresses of this rank's
-// segments in the neighbours' receive blocks (the arena block viewed as floats); same flags, same sequence
-__global__ __launch_bounds__(BLOCK) void k_mx_put_signal(int n_send, const int *__restrict__ send_idxs, PeerHalo P,
-                                                         const float *__restrict__ x, const MixedScalars *gate,
-                                                         unsigned *ticket)
-{
-    if (mx_gated(gate)) return;
-    const int j = blockIdx.x * BLOCK + threadIdx.x;
-    if (j < n_send) {
-        int i = 0;
-        while (i + 1 < P.n_neigh && j >= P.send_off[i + 1]) ++i;
-        reinterpret_cast<float *>(P.remote_recv[i])[j - P.send_off[i]] = x[send_idxs[j]];
-    }
-    __threadfence_system();
-    __syncthreads();
-    __shared__ int last;
-    if (threadIdx.x == 0) {
-        last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-        if (last) *ticket = 0;
-    }
-    __syncthreads();
-    if (last && (int)threadIdx.x < P.n_neigh) {
-        __threadfence_system();
-        __hip_atomic_store(P.remote_flag[threadIdx.x], (unsigned long long)P.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-
-// lanes 0 .. n_neigh - 1 wait for their neighbour's flag of exchange P.seq; true (to every thread) when all arrived.  The
-// wait goes into the solve's counters; a time-out raises comm_error and the stops.
-__device__ __forceinline__ bool mx_wait_flags(const PeerHalo &P, MixedScalars *m, DevScalars *s, int *timed_out, unsigned *waited)
-{
-    if (threadIdx.x == 0) {
-        *timed_out = 0;
-        *waited = 0;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < P.n_neigh) {
-        const long long t0 = wall_clock64();
-        for (;;) {
-            const unsigned long long f = __hip_atomic_load(P.local_flag + threadIdx.x, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
-            if ((uint32_t)f == P.seq) break;
-            if (wall_clock64() - t0 > P.timeout_ticks) {
-                *timed_out = 1;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        note_wait(waited, t0);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(&m->halo_wait_ticks, (unsigned long long)*waited);
-        atomicAdd(&m->halo_waits, 1u);
-        if (*timed_out) mx_comm_failed(m, s);
-    }
-    return *timed_out == 0;
-}
-
-// the pi partial of a chunk over the finished q, in the local kernels' tree
+// the pi partial of a chunk over the finished q, in the local kernels' tree (several ranks: the boundary chunks again, after
+// the halo kernels of kernels_comm.hip have continued q over the non-local entries)
 __device__ __forceinline__ void mx_pi_partial(int n_rows, int chunk, const float *x, const float *y, double *part, double *slot)
 {
     const RowPair rp = my_rows(chunk, n_rows);
-    const float2 xv = ld2f(x, rp), yv = ld2f(y, rp);
+    const float2 xv = ld2(x, rp), yv = ld2(y, rp);
     double d = 0.0;
     if (rp.n > 0) d += (double)xv.x * (double)yv.x;
     if (rp.n > 1) d += (double)xv.y * (double)yv.y;
     const double sum = block_sum(d, slot);
     if (threadIdx.x == 0) part[chunk] = sum;
-}
-
-// wait + non-local part + the pi partial of the chunk: one workgroup per chunk that holds boundary rows (a time-out
-// leaves y the local product)
-__global__ __launch_bounds__(BLOCK) void k_mx_halo_finish(int n_rows, const int *__restrict__ chunk_list,
-                                                          const int *__restrict__ chunk_row_ptr,
-                                                          const int *__restrict__ boundary_rows,
-                                                          const int *__restrict__ entry_ptrs, const int *__restrict__ cols,
-                                                          const float *__restrict__ vals, const float *recv, const float *x,
-                                                          float *y, double *part, PeerHalo P, const MixedScalars *gate,
-                                                          MixedScalars *m, DevScalars *s)
-{
-    __shared__ double slot[N_WAVES];
-    __shared__ int timed_out;
-    __shared__ unsigned waited;
-    if (mx_gated(gate)) return;
-    if (!mx_wait_flags(P, m, s, &timed_out, &waited)) return;
-    const int chunk = chunk_list[blockIdx.x];
-    for (int i = chunk_row_ptr[blockIdx.x] + threadIdx.x; i < chunk_row_ptr[blockIdx.x + 1]; i += BLOCK) {
-        const int row = boundary_rows[i];
-        float acc = y[row];
-        for (int k = entry_ptrs[i]; k < entry_ptrs[i + 1]; ++k) {
-            const float t = vals[k] * recv[cols[k]];
-            acc = acc + t;
-        }
-        y[row] = acc;
-    }
-    if (part) {
-        __threadfence_block();
-        __syncthreads();
-        mx_pi_partial(n_rows, chunk, x, y, part, slot);
-    }
-}
-
-// peerSafeWait: the single waiting workgroup of a rank
-__global__ __launch_bounds__(64) void k_mx_halo_wait(PeerHalo P, const MixedScalars *gate, MixedScalars *m, DevScalars *s)
-{
-    __shared__ int timed_out;
-    __shared__ unsigned waited;
-    if (mx_gated(gate)) return;
-    (void)mx_wait_flags(P, m, s, &timed_out, &waited);
-}
-
-// send[j] = (double)x[send_idxs[j]]: the RCCL / host-buffer rungs carry doubles (exact both ways)
-__global__ __launch_bounds__(BLOCK) void k_mx_pack_wide(int n_send, const int *__restrict__ send_idxs,
-                                                        const float *__restrict__ x, double *__restrict__ send,
-                                                        const MixedScalars *gate)
-{
-    if (mx_gated(gate)) return;
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n_send) send[i] = (double)x[send_idxs[i]];
-}
-
-// the non-local part of every boundary row; R = float (the receive block of the peer mesh) | double (narrowed on read)
-template <class R>
-__global__ __launch_bounds__(BLOCK) void k_mx_non_local(int n_boundary, const int *__restrict__ boundary_rows,
-                                                        const int *__restrict__ entry_ptrs, const int *__restrict__ cols,
-                                                        const float *__restrict__ vals, const R *recv, float *__restrict__ y,
-                                                        const MixedScalars *gate)
-{
-    if (mx_gated(gate)) return;
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n_boundary) return;
-    const int row = boundary_rows[i];
-    float acc = y[row];
-    for (int k = entry_ptrs[i]; k < entry_ptrs[i + 1]; ++k) {
-        const float t = vals[k] * (float)recv[cols[k]];
-        acc = acc + t;
-    }
-    y[row] = acc;
 }
 
 __global__ __launch_bounds__(BLOCK) void k_mx_pi_chunks(int n_rows, const int *__restrict__ chunk_list, const float *x,
@@ -875,50 +714,8 @@ void launch_mixed_step2(hipStream_t st, int32_t n, float *u, float *r, const flo
     hipLaunchKernelGGL(k_mx_step2, dim3(nc), dim3(BLOCK), 0, st, n, u, r, p, q, inv_d, z, part_rho, part_tau, m);
 }
 
-void launch_mixed_put(hipStream_t st, const DevHalo &H, const PeerHalo &P, const float *x, const MixedScalars *gate,
-                      unsigned *ticket)
-{
-    if (H.n_send == 0) return;
-    hipLaunchKernelGGL(k_mx_put_signal, dim3(blocks_for(H.n_send)), dim3(BLOCK), 0, st, H.n_send, H.send_idxs, P, x, gate, ticket);
-}
-
-void launch_mixed_halo_finish(hipStream_t st, const DevHalo &H, const float *nl_vals, int32_t n_rows,
-                              const int32_t *chunk_list, const int32_t *chunk_row_ptr, int32_t n_chunks_b, const float *recv,
-                              const float *x, float *y, double *part, const PeerHalo &P, const MixedScalars *gate,
-                              MixedScalars *m, DevScalars *s)
-{
-    if (n_chunks_b == 0) return;
-    hipLaunchKernelGGL(k_mx_halo_finish, dim3(n_chunks_b), dim3(BLOCK), 0, st, n_rows, chunk_list, chunk_row_ptr,
-                       H.boundary_rows, H.entry_ptrs, H.cols, nl_vals, recv, x, y, part, P, gate, m, s);
-}
-
-void launch_mixed_halo_wait(hipStream_t st, const PeerHalo &P, const MixedScalars *gate, MixedScalars *m, DevScalars *s)
-{
-    if (P.n_neigh == 0) return;
-    hipLaunchKernelGGL(k_mx_halo_wait, dim3(1), dim3(64), 0, st, P, gate, m, s);
-}
-
-void launch_mixed_pack_wide(hipStream_t st, const DevHalo &H, const float *x, double *send, const MixedScalars *gate)
-{
-    if (H.n_send == 0) return;
-    hipLaunchKernelGGL(k_mx_pack_wide, dim3(blocks_for(H.n_send)), dim3(BLOCK), 0, st, H.n_send, H.send_idxs, x, send, gate);
-}
-
-void launch_mixed_non_local(hipStream_t st, const DevHalo &H, const float *nl_vals, const float *recv32, const double *recv64,
-                            float *y, const MixedScalars *gate)
-{
-    if (H.n_boundary_rows == 0) return;
-    const dim3 grid(blocks_for(H.n_boundary_rows)), block(BLOCK);
-    if (recv32)
-        hipLaunchKernelGGL(k_mx_non_local<float>, grid, block, 0, st, H.n_boundary_rows, H.boundary_rows, H.entry_ptrs, H.cols,
-                           nl_vals, recv32, y, gate);
-    else
-        hipLaunchKernelGGL(k_mx_non_local<double>, grid, block, 0, st, H.n_boundary_rows, H.boundary_rows, H.entry_ptrs, H.cols,
-                           nl_vals, recv64, y, gate);
-}
-
-void launch_mixed_pi_chunks(hipStream_t st, int32_t n, const float *x, const float *y, double *part, const MixedScalars *gate,
-                            const int32_t *chunk_list, int32_t n_list)
+void launch_partials_dot_chunks(hipStream_t st, int32_t n, const float *x, const float *y, double *part,
+                                const MixedScalars *gate, const int32_t *chunk_list, int32_t n_list)
 {
     if (n_list == 0) return;
     hipLaunchKernelGGL(k_mx_pi_chunks, dim3(n_list), dim3(BLOCK), 0, st, n, chunk_list, x, y, part, gate);

@@ -240,38 +240,6 @@ __global__ __launch_bounds__(BLOCK) void k_spmv_stream21(
     }
 }
 
-// y[row] (+/-)= A_non_local(row,:) * recv, continuing the accumulator the local kernel stored.
-template <int MODE>
-__global__ __launch_bounds__(BLOCK) void k_spmv_non_local(int n_boundary,
-                                                          const int *__restrict__ boundary_rows,
-                                                          const int *__restrict__ entry_ptrs,
-                                                          const int *__restrict__ cols,
-                                                          const double *__restrict__ vals,
-                                                          const double *__restrict__ recv,
-                                                          double *__restrict__ y,
-                                                          const DevScalars *gate)
-{
-    if (gate && gate->stop) return;
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n_boundary) return;
-    const int row = boundary_rows[i];
-    double acc = y[row];
-    for (int k = entry_ptrs[i]; k < entry_ptrs[i + 1]; ++k) {
-        const double t = vals[k] * recv[cols[k]];
-        acc = (MODE == SPMV_RESIDUAL) ? acc - t : acc + t;
-    }
-    y[row] = acc;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_pack(int n_send, const int *__restrict__ send_idxs,
-                                                const double *__restrict__ x,
-                                                double *__restrict__ send, const DevScalars *gate)
-{
-    if (gate && gate->stop) return;
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n_send) send[i] = x[send_idxs[i]];
-}
-
 // ------------------------------------------------------------------------------------------
 // ELL SpMV (matrixFormat Ell).  Slot-major planes: every load is a 16-byte (values) / 8-byte
 // (columns) coalesced access over the chunk's rows, no LDS, no row pointers; a thread owns rows
@@ -447,28 +415,6 @@ void launch_spmv_ell(hipStream_t st, const DevEll &A, int mode, const double *x,
     }
 #undef OGL_ELL
 #undef OGL_ELL_K
-}
-
-void launch_spmv_non_local(hipStream_t st, const DevHalo &H, int mode, const double *recv,
-                           double *y, const DevScalars *gate)
-{
-    if (H.n_boundary_rows == 0) return;
-    const dim3 grid(blocks_for(H.n_boundary_rows)), block(BLOCK);
-    if (mode == SPMV_RESIDUAL)
-        hipLaunchKernelGGL((k_spmv_non_local<SPMV_RESIDUAL>), grid, block, 0, st,
-                           H.n_boundary_rows, H.boundary_rows, H.entry_ptrs, H.cols, H.vals, recv,
-                           y, gate);
-    else
-        hipLaunchKernelGGL((k_spmv_non_local<SPMV_PLAIN>), grid, block, 0, st, H.n_boundary_rows,
-                           H.boundary_rows, H.entry_ptrs, H.cols, H.vals, recv, y, gate);
-}
-
-void launch_pack(hipStream_t st, const DevHalo &H, const double *x, double *send,
-                 const DevScalars *gate)
-{
-    if (H.n_send == 0) return;
-    hipLaunchKernelGGL(k_pack, dim3(blocks_for(H.n_send)), dim3(BLOCK), 0, st, H.n_send,
-                       H.send_idxs, x, send, gate);
 }
 
 }  // namespace ogl

@@ -508,9 +508,18 @@ struct ogl_solver {
     uint64_t cg_graph_key = 0;  // hash of everything the captured launches bake in (launch_key.hpp)
     void drop_cg_graph();  // (every pattern / layout rebuild)
     int setup_peer_halo();
-    // f32: the receive segments viewed as floats (the mixed mode's 4-byte halo; remote_recv then holds float addresses)
-    ogl::PeerHalo peer_halo_args(uint32_t seq, bool f32 = false) const;
-    double *peer_recv(uint32_t seq) const;
+    // value_bytes: 8, or 4 for the mixed mode's halo (the receive blocks viewed as floats)
+    ogl::PeerHalo peer_halo_args(uint32_t seq, size_t value_bytes) const;
+    ogl::PeerHalo next_exchange(size_t value_bytes);  // the next number of halo_seq and its arguments
+    void *peer_recv_block(uint32_t seq) const;        // this rank's receive block of exchange `seq`
+    template <class T>
+    T *peer_recv(uint32_t seq) const { return static_cast<T *>(peer_recv_block(seq)); }
+    // a distributed product's halo before and after its local kernel, every transport but the fused peer-put
+    // (solver_transport.cpp; T = double with HaloOwner, float with MixedHaloOwner)
+    template <class T, class Owner>
+    int halo_begin(const T *x, const Owner &own, ogl::PeerHalo &ph);
+    template <class T, class Owner>
+    int halo_end(int mode, const ogl::PeerHalo &ph, const T *nl_vals, T *y, const ogl::SpmvDotsOf<T> &dots, const Owner &own);
     // halo part
     std::vector<int32_t> boundary_rows, boundary_ptrs;
     ogl::DevBuf<int32_t> d_boundary_rows, d_boundary_ptrs, d_nl_cols, d_send_idxs;
@@ -636,6 +645,8 @@ struct ogl_solver {
     void spmv_on(ogl::SpmvLayout l, int mode, const double *x, const double *b, double *y, const ogl::SpmvDots &dots,
                  const ogl::DevScalars *gate, const ogl::HaloFused &hf = ogl::HaloFused{});
     int finalize(int phase, ogl::FinArgs &a);
+    template <class Args, class Launch>
+    int split_finaliser(Args &a, double *sums, int n_sums, Launch launch);  // (solver_internal.hpp)
     int run_cg(ogl_perf *perf);
     int run_bicgstab(ogl_perf *perf);
     int run_krylov(ogl_perf *perf);
@@ -648,7 +659,7 @@ struct ogl_solver {
     int mixed_overflow(const ogl::MixedScalars &m);  // OGL_ERR_INVALID naming the row when a value overflowed binary32
     // q = A32 p: the local product, on several ranks between the halo's put (or pack + exchange) and its non-local part
     int mixed_spmv(const float *x, float *y, double *part, const ogl::MixedScalars *gate);
-    // a finaliser of the mode with its sums all-reduced over the ranks (the split of finalize)
+    // a finaliser of the mode with its sums all-reduced over the ranks (split_finaliser)
     int mixed_fin(int phase, ogl::MixedFinArgs &a);
     int run_mixed(ogl_perf *perf);
     // property orthoMethod (0 mgs | 1 cgs | 2 cgs2; GKOGMRES only, ignored elsewhere): its validation and the refusal on

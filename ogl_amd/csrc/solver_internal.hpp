@@ -34,3 +34,26 @@ struct EventPair {  // destroyed on every return path
 
 }  // namespace
 }  // namespace ogl
+
+// The three-way split of a finaliser over the transports, `launch()` enqueueing it with the arguments `a`: one launch
+// that reduces and runs the logic; on the peer mesh the same with the all-reduce inside it (peer_next); on the other
+// rungs a reducing launch, Comm::allreduce on the n_sums doubles it left at `sums`, a launch of the logic.
+template <class Args, class Launch>
+int ogl_solver::split_finaliser(Args &a, double *sums, int n_sums, Launch launch)
+{
+    a.peer = ogl::PeerArgs{};
+    a.do_reduce = a.do_logic = 1;
+    if (reg->comm->multi() && !reg->peer_ready) {
+        a.do_logic = 0;
+        launch();
+        OGL_TRY(reg->comm->allreduce(sums, n_sums, reg->stream));
+        a.do_reduce = 0;
+        a.do_logic = 1;
+        launch();
+        return OGL_OK;
+    }
+    if (reg->comm->multi()) a.peer = reg->peer_next();
+    launch();
+    a.peer = ogl::PeerArgs{};
+    return OGL_OK;
+}

@@ -20,8 +20,7 @@ HaloPutFused ogl_solver::begin_halo_put()
     HaloPutFused put;
     if (!(pat.non_local_nnz > 0 && peer_halo) || prop("haloFused", 1.0) == 0.0 || peer_safe_wait())
         return put;
-    if (++halo_seq == 0) ++halo_seq;
-    cur_halo = peer_halo_args(halo_seq);
+    cur_halo = next_exchange(sizeof(double));
     put.P = cur_halo;
     put.chunk_sptr = d_chunk_sptr.p;
     put.send_pos = d_send_pos.p;
@@ -40,11 +39,8 @@ HaloFused ogl_solver::halo_fused_args(const PeerHalo &ph) const
     hf.entry_ptrs = d_boundary_ptrs.p;
     hf.cols = d_nl_cols.p;
     hf.vals = d_nl_vals.p;
-    hf.recv = peer_recv(ph.seq);
-    hf.local_flag = ph.local_flag;
-    hf.n_neigh = ph.n_neigh;
-    hf.seq = ph.seq;
-    hf.timeout_ticks = ph.timeout_ticks;
+    hf.recv = peer_recv<double>(ph.wait.seq);
+    hf.wait = ph.wait;
     hf.s = d_scal.p;
     return hf;
 }
@@ -67,9 +63,11 @@ int ogl_solver::dist_spmv(int mode, const double *x, const double *b, double *y,
                           const SpmvDots &dots, const DevScalars *gate, bool prepacked)
 {
     hipStream_t st = reg->stream;
-    const bool has_halo = pat.non_local_nnz > 0;
-    const double *recv = d_recv.p;
-    PeerHalo ph;
+    if (pat.non_local_nnz == 0) {
+        spmv_on(spmv_layout, mode, x, b, y, dots, gate);
+        return OGL_OK;
+    }
+    const HaloOwner own{gate, d_scal.p};
     // peer-put transport: by default the non-local part is added inside the local kernel (HaloFused) -- a
     // distributed SpMV is then 2 launches (pack + put + signal | local + wait + non-local), 1 when the producer
     // of x has put the values itself; property haloFused 0 keeps the separate finish kernel (A/B)
@@ -77,96 +75,31 @@ int ogl_solver::dist_spmv(int mode, const double *x, const double *b, double *y,
     // report the same PCI bus id): no workgroup of the SpMV waits -- ONE workgroup of a
     // kernel of its own does, then the non-local part is added by kernels that find the values there.  Many waiting
     // workgroups of several ranks on one device can hold every slot the producers' put kernels need.
-    const bool safe = has_halo && peer_halo && peer_safe_wait();
-    const bool fuse = has_halo && peer_halo && !safe && prop("haloFused", 1.0) != 0.0;
-    HaloFused hf;
-    if (has_halo && peer_halo) {
-        // peer-put: the values go straight into the neighbours' receive blocks over xGMI, then the
-        // flags; they fly while the local SpMV below runs
-        if (prepacked && fuse) {
-            ph = cur_halo;
-        } else {
-            if (++halo_seq == 0) ++halo_seq;
-            ph = peer_halo_args(halo_seq);
-            launch_pack_put_signal(st, halo(), ph, x, gate, d_ticket.p);
+    if (peer_halo && !peer_safe_wait() && prop("haloFused", 1.0) != 0.0) {
+        PeerHalo ph = cur_halo;
+        if (!prepacked) {
+            ph = next_exchange(sizeof(double));
+            launch_pack_put_signal(st, halo(), ph, x, own, d_ticket.p);
         }
-        recv = peer_recv(ph.seq);
-        if (fuse) hf = halo_fused_args(ph);
-    } else if (has_halo) {
-        // pack on the compute stream, exchange on the communication stream: the neighbour copies
-        // fly while the local SpMV below runs; the non-local kernel waits for their arrival
-        if (!reg->comm_stream) {
-            OGL_HIP_CHECK(stream_create(&reg->comm_stream));
-            OGL_HIP_CHECK(ev_create(&reg->ev_packed, hipEventDisableTiming));
-            OGL_HIP_CHECK(ev_create(&reg->ev_received, hipEventDisableTiming));
-        }
-        launch_pack(st, halo(), x, d_send.p, gate);
-        OGL_HIP_CHECK(hipEventRecord(reg->ev_packed, st));
-        OGL_HIP_CHECK(hipStreamWaitEvent(reg->comm_stream, reg->ev_packed, 0));
-        OGL_TRY(reg->comm->exchange(d_send.p, d_recv.p, neighbours, counts, reg->comm_stream));
-        OGL_HIP_CHECK(hipEventRecord(reg->ev_received, reg->comm_stream));
+        spmv_on(spmv_layout, mode, x, b, y, dots, gate, halo_fused_args(ph));
+        return OGL_OK;
     }
-    // The fused dot partials of the local kernel are final for every chunk without boundary rows;
-    // the few chunks that hold boundary rows are redone after "y += A_non_local recv" (same
-    // per-chunk tree, so the sums are bit-identical to a dot over the finished y).
-    spmv_on(spmv_layout, mode, x, b, y, dots, gate, hf);
-    if (safe) {
-        launch_halo_wait(st, ph, gate, d_scal.p);
-        launch_spmv_non_local(st, halo(), mode, recv, y, gate);
-        if (dots.part)
-            launch_partials_dot_chunks(st, pat.n_rows, dots.with, y, dots.part, gate, d_boundary_chunks.p,
-                                       n_boundary_chunks);
-        if (dots.part_yy)
-            launch_partials_dot_chunks(st, pat.n_rows, y, y, dots.part_yy, gate, d_boundary_chunks.p,
-                                       n_boundary_chunks);
-    } else if (has_halo && peer_halo && !fuse) {
-        // wait for the neighbours' flags, add the non-local part, redo the touched chunks' partials
-        launch_halo_finish(st, halo(), mode, pat.n_rows, d_boundary_chunks.p, d_boundary_chunk_ptr.p,
-                           n_boundary_chunks, recv, y, dots, ph, gate, d_scal.p);
-    } else if (has_halo && !peer_halo) {
-        OGL_HIP_CHECK(hipStreamWaitEvent(st, reg->ev_received, 0));
-        launch_spmv_non_local(st, halo(), mode, recv, y, gate);
-        if (dots.part)
-            launch_partials_dot_chunks(st, pat.n_rows, dots.with, y, dots.part, gate,
-                                       d_boundary_chunks.p, n_boundary_chunks);
-        if (dots.part_yy)
-            launch_partials_dot_chunks(st, pat.n_rows, y, y, dots.part_yy, gate,
-                                       d_boundary_chunks.p, n_boundary_chunks);
-    }
-    return OGL_OK;
+    PeerHalo ph;
+    OGL_TRY(halo_begin(x, own, ph));
+    spmv_on(spmv_layout, mode, x, b, y, dots, gate);
+    return halo_end(mode, ph, d_nl_vals.p, y, dots, own);
 }
 
 int ogl_solver::finalize(int phase, FinArgs &a)
 {
-    hipStream_t st = reg->stream;
+    auto launch = [&] { launch_finalize(reg->stream, phase, d_scal.p, a); };
     if (a.n_sums == 0) {  // nothing to reduce: scalar logic only (identical on every rank)
         a.do_reduce = 0;
         a.do_logic = 1;
-        launch_finalize(st, phase, d_scal.p, a);
+        launch();
         return OGL_OK;
     }
-    if (!reg->comm->multi()) {
-        a.do_reduce = 1;
-        a.do_logic = 1;
-        launch_finalize(st, phase, d_scal.p, a);
-        return OGL_OK;
-    }
-    if (reg->peer_ready) {  // the all-reduce runs inside the finaliser (peer mailboxes over xGMI)
-        a.peer = reg->peer_next();
-        a.do_reduce = 1;
-        a.do_logic = 1;
-        launch_finalize(st, phase, d_scal.p, a);
-        a.peer = PeerArgs{};
-        return OGL_OK;
-    }
-    a.do_reduce = 1;
-    a.do_logic = 0;
-    launch_finalize(st, phase, d_scal.p, a);
-    OGL_TRY(reg->comm->allreduce(sums_ptr(d_scal.p), a.n_sums, st));
-    a.do_reduce = 0;
-    a.do_logic = 1;
-    launch_finalize(st, phase, d_scal.p, a);
-    return OGL_OK;
+    return split_finaliser(a, sums_ptr(d_scal.p), a.n_sums, launch);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -538,9 +471,8 @@ int ogl_solver::krylov_prepare(KrylovRun &k)
         OGL_HIP_CHECK(hipEventRecord(k.ev_chk[1], st));
     }
     if (k.merged_halo) {  // the z of the first merged turn (later ones: put by step_2r)
-        if (++halo_seq == 0) ++halo_seq;
-        cur_halo = peer_halo_args(halo_seq);
-        launch_pack_put_signal(st, halo(), cur_halo, k.z_kept ? k.z_kept : d_r.p, s, d_ticket.p);
+        cur_halo = next_exchange(sizeof(double));
+        launch_pack_put_signal(st, halo(), cur_halo, k.z_kept ? k.z_kept : d_r.p, HaloOwner{s}, d_ticket.p);
     }
 
     k.f1 = FinArgs{};  // one partial array

@@ -88,67 +88,20 @@ int ogl_solver::mixed_spmv(const float *x, float *y, double *part, const MixedSc
         local();
         return OGL_OK;
     }
-    MixedScalars *m = mixed.scal.p;
-    const DevHalo H = halo();
-    const float *nl = fp32_dev.nl_vals.p;
-    if (peer_halo) {
-        if (++halo_seq == 0) ++halo_seq;
-        const PeerHalo ph = peer_halo_args(halo_seq, /*f32=*/true);
-        const float *recv = reinterpret_cast<const float *>(peer_recv(ph.seq));
-        launch_mixed_put(st, H, ph, x, gate, d_ticket.p);
-        local();
-        if (peer_safe_wait()) {  // (ranks that share a device: no workgroup of a product waits, dist_spmv has the reason)
-            launch_mixed_halo_wait(st, ph, gate, m, d_scal.p);
-            launch_mixed_non_local(st, H, nl, recv, nullptr, y, gate);
-            if (part) launch_mixed_pi_chunks(st, pat.n_rows, x, y, part, gate, d_boundary_chunks.p, n_boundary_chunks);
-        } else {
-            launch_mixed_halo_finish(st, H, nl, pat.n_rows, d_boundary_chunks.p, d_boundary_chunk_ptr.p, n_boundary_chunks,
-                                     recv, x, y, part, ph, gate, m, d_scal.p);
-        }
-        return OGL_OK;
-    }
-    if (!reg->comm_stream) {
-        OGL_HIP_CHECK(stream_create(&reg->comm_stream));
-        OGL_HIP_CHECK(ev_create(&reg->ev_packed, hipEventDisableTiming));
-        OGL_HIP_CHECK(ev_create(&reg->ev_received, hipEventDisableTiming));
-    }
-    launch_mixed_pack_wide(st, H, x, d_send.p, gate);
-    OGL_HIP_CHECK(hipEventRecord(reg->ev_packed, st));
-    OGL_HIP_CHECK(hipStreamWaitEvent(reg->comm_stream, reg->ev_packed, 0));
-    OGL_TRY(reg->comm->exchange(d_send.p, d_recv.p, neighbours, counts, reg->comm_stream));
-    OGL_HIP_CHECK(hipEventRecord(reg->ev_received, reg->comm_stream));
+    const MixedHaloOwner own{gate, mixed.scal.p, d_scal.p};
+    PeerHalo ph;
+    OGL_TRY(halo_begin(x, own, ph));
     local();
-    OGL_HIP_CHECK(hipStreamWaitEvent(st, reg->ev_received, 0));
-    launch_mixed_non_local(st, H, nl, nullptr, d_recv.p, y, gate);
-    if (part) launch_mixed_pi_chunks(st, pat.n_rows, x, y, part, gate, d_boundary_chunks.p, n_boundary_chunks);
-    return OGL_OK;
+    return halo_end(SPMV_PLAIN, ph, fp32_dev.nl_vals.p, y, SpmvDotsOf<float>{x, part, nullptr}, own);
 }
 
-// A finaliser of the mode.  Several ranks: its sums are all-reduced between the reduction and the logic -- inside the launch
-// on the peer mesh, by Comm::allreduce between two launches on the other rungs (ogl_solver::finalize has the same split).
+// A finaliser of the mode.  Several ranks: its two sums, staged in MixedScalars::sums, are all-reduced between the
+// reduction and the logic by the split that ogl_solver::finalize has (split_finaliser, solver_internal.hpp).
 int ogl_solver::mixed_fin(int phase, MixedFinArgs &a)
 {
-    hipStream_t st = reg->stream;
     MixedScalars *m = mixed.scal.p;
-    a.peer = PeerArgs{};
-    a.do_reduce = a.do_logic = 1;
-    if (!reg->comm->multi()) {
-        launch_mixed_fin(st, phase, m, d_scal.p, a);
-        return OGL_OK;
-    }
-    if (reg->peer_ready) {
-        a.peer = reg->peer_next();
-        launch_mixed_fin(st, phase, m, d_scal.p, a);
-        a.peer = PeerArgs{};
-        return OGL_OK;
-    }
-    a.do_logic = 0;
-    launch_mixed_fin(st, phase, m, d_scal.p, a);
-    OGL_TRY(reg->comm->allreduce(reinterpret_cast<double *>(reinterpret_cast<char *>(m) + offsetof(MixedScalars, sums)), 2, st));
-    a.do_reduce = 0;
-    a.do_logic = 1;
-    launch_mixed_fin(st, phase, m, d_scal.p, a);
-    return OGL_OK;
+    double *sums = reinterpret_cast<double *>(reinterpret_cast<char *>(m) + offsetof(MixedScalars, sums));
+    return split_finaliser(a, sums, 2, [&] { launch_mixed_fin(reg->stream, phase, m, d_scal.p, a); });
 }
 
 // The device row that holds position `position` of fp32_dev's value array (the planes' twin or the CSR values; behind

@@ -239,15 +239,16 @@ int ogl_solver::setup_peer_halo()
     return OGL_OK;
 }
 
-PeerHalo ogl_solver::peer_halo_args(uint32_t seq, bool f32) const
+// value_bytes: the width of a halo value (8: doubles; 4: the mixed mode views the same receive blocks as floats)
+PeerHalo ogl_solver::peer_halo_args(uint32_t seq, size_t value_bytes) const
 {
     const ogl_registry &R = *reg;
     const int nn = (int)neighbours.size();
     const unsigned par = seq & 1u;
     PeerHalo P;
-    P.n_neigh = nn;
-    P.seq = seq;
-    P.timeout_ticks = R.peer.timeout_ticks;
+    P.wait.n_neigh = nn;
+    P.wait.seq = seq;
+    P.wait.timeout_ticks = R.peer.timeout_ticks;
     int32_t off = 0;
     for (int i = 0; i < nn; ++i) {
         P.send_off[i] = off;
@@ -256,20 +257,83 @@ PeerHalo ogl_solver::peer_halo_args(uint32_t seq, bool f32) const
         unsigned long long *base = R.peer.box[neighbours[i]] + PEER_ARENA_OFF + nb.block;
         P.remote_flag[i] = base + (size_t)par * nb.n_neigh + nb.my_index;
         unsigned long long *block = base + 2 * (size_t)nb.n_neigh + (size_t)par * nb.n_halo;
-        P.remote_recv[i] = f32 ? reinterpret_cast<double *>(reinterpret_cast<float *>(block) + nb.my_seg)
-                               : reinterpret_cast<double *>(block + nb.my_seg);
+        P.remote_recv[i] = reinterpret_cast<char *>(block) + (size_t)nb.my_seg * value_bytes;
     }
     P.send_off[nn] = off;
-    P.local_flag = R.peer_local + PEER_ARENA_OFF + peer_block + (size_t)par * nn;
+    P.wait.local_flag = R.peer_local + PEER_ARENA_OFF + peer_block + (size_t)par * nn;
     return P;
 }
 
-double *ogl_solver::peer_recv(uint32_t seq) const
+// the exchange that starts now: the next number of this solver's sequence (never 0: the flags start zeroed)
+PeerHalo ogl_solver::next_exchange(size_t value_bytes)
+{
+    if (++halo_seq == 0) ++halo_seq;
+    return peer_halo_args(halo_seq, value_bytes);
+}
+
+void *ogl_solver::peer_recv_block(uint32_t seq) const
 {
     const size_t nn = neighbours.size();
-    return reinterpret_cast<double *>(reg->peer_local + PEER_ARENA_OFF + peer_block + 2 * nn +
-                                      (size_t)(seq & 1u) * (size_t)pat.non_local_nnz);
+    return reg->peer_local + PEER_ARENA_OFF + peer_block + 2 * nn + (size_t)(seq & 1u) * (size_t)pat.non_local_nnz;
 }
+
+// The halo of a distributed product around its local kernel, for the double path and for the inner product of the mixed
+// mode (T = float).  Before it: the values at the send rows leave -- straight into the neighbours' receive blocks with
+// the flags behind them (peer mesh, exchange `ph`), or packed as doubles on the compute stream and exchanged on the
+// communication stream -- and fly while the local kernel runs.
+template <class T, class Owner>
+int ogl_solver::halo_begin(const T *x, const Owner &own, PeerHalo &ph)
+{
+    hipStream_t st = reg->stream;
+    if (peer_halo) {
+        ph = next_exchange(sizeof(T));
+        launch_pack_put_signal(st, halo(), ph, x, own, d_ticket.p);
+        return OGL_OK;
+    }
+    if (!reg->comm_stream) {
+        OGL_HIP_CHECK(stream_create(&reg->comm_stream));
+        OGL_HIP_CHECK(ev_create(&reg->ev_packed, hipEventDisableTiming));
+        OGL_HIP_CHECK(ev_create(&reg->ev_received, hipEventDisableTiming));
+    }
+    launch_pack(st, halo(), x, d_send.p, own);
+    OGL_HIP_CHECK(hipEventRecord(reg->ev_packed, st));
+    OGL_HIP_CHECK(hipStreamWaitEvent(reg->comm_stream, reg->ev_packed, 0));
+    OGL_TRY(reg->comm->exchange(d_send.p, d_recv.p, neighbours, counts, reg->comm_stream));
+    OGL_HIP_CHECK(hipEventRecord(reg->ev_received, reg->comm_stream));
+    return OGL_OK;
+}
+
+// After it: y continues over the non-local entries once the values are there.  The fused dot partials of the local
+// kernel are final for every chunk without boundary rows; the few chunks that hold boundary rows are redone over the
+// finished y (same per-chunk tree, so the sums are bit-identical to a dot over the finished y) -- by the finish kernel
+// itself, else by a launch per partial array.
+template <class T, class Owner>
+int ogl_solver::halo_end(int mode, const PeerHalo &ph, const T *nl_vals, T *y, const SpmvDotsOf<T> &dots, const Owner &own)
+{
+    hipStream_t st = reg->stream;
+    if (peer_halo && !peer_safe_wait()) {
+        launch_halo_finish(st, halo(), nl_vals, mode, pat.n_rows, d_boundary_chunks.p, d_boundary_chunk_ptr.p,
+                           n_boundary_chunks, peer_recv<T>(ph.wait.seq), y, dots, ph, own);
+        return OGL_OK;
+    }
+    if (peer_halo) {  // (ranks that share a device: no workgroup of a product waits, dist_spmv has the reason)
+        launch_halo_wait(st, ph, own);
+        launch_spmv_non_local(st, halo(), nl_vals, mode, peer_recv<T>(ph.wait.seq), y, own);
+    } else {
+        OGL_HIP_CHECK(hipStreamWaitEvent(st, reg->ev_received, 0));
+        launch_spmv_non_local(st, halo(), nl_vals, mode, d_recv.p, y, own);
+    }
+    if (dots.part)
+        launch_partials_dot_chunks(st, pat.n_rows, dots.with, y, dots.part, own.gate, d_boundary_chunks.p, n_boundary_chunks);
+    if (dots.part_yy)
+        launch_partials_dot_chunks(st, pat.n_rows, y, y, dots.part_yy, own.gate, d_boundary_chunks.p, n_boundary_chunks);
+    return OGL_OK;
+}
+template int ogl_solver::halo_begin(const double *, const HaloOwner &, PeerHalo &);
+template int ogl_solver::halo_begin(const float *, const MixedHaloOwner &, PeerHalo &);
+template int ogl_solver::halo_end(int, const PeerHalo &, const double *, double *, const SpmvDots &, const HaloOwner &);
+template int ogl_solver::halo_end(int, const PeerHalo &, const float *, float *, const SpmvDotsOf<float> &,
+                                  const MixedHaloOwner &);
 
 // one waiting workgroup per rank instead of every boundary workgroup of the SpMV: asked for (property), or because
 // peer_connect found two ranks on one device
