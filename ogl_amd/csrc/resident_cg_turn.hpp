@@ -131,7 +131,9 @@ __device__ __forceinline__ RowPair turn_rows(int chunk, int n)
 }
 
 // the rows phase R has asked for ahead of the slot at work: r, 1 / d (its only use in the turn) and, where q is in
-// memory, q
+// memory, q.  All three go past the caches: nothing reads r between phase R of one turn and phase R of the next -- z stays
+// on chip -- and its 16 N bytes would pass through the Infinity Cache between the two uses of p that can share a line there,
+// phase S's gather and phase H's read ("Streams of the resident turn")
 template <bool Q_HELD>
 struct TurnFront {
     double2 r[TURN_AHEAD], d[TURN_AHEAD], q[TURN_AHEAD];
@@ -144,7 +146,7 @@ template <class Src>
 __device__ __forceinline__ void turn_ask(const Src &src, const TurnArgs &a, TurnFront<Src::Q_HELD> &f, int i, int d)
 {
     const RowPair rp = turn_rows(src.chunk_of(i), a.n);
-    f.r[d] = ld2(a.r, rp);
+    f.r[d] = ld2_stream(a.r, rp);
     if constexpr (!Src::Q_HELD) f.q[d] = ld2_stream(src.q, rp);
     f.d[d].x = f.d[d].y = 1.0;
     if (a.inv_diag) f.d[d] = ld2_stream(a.inv_diag, rp);
@@ -196,7 +198,7 @@ __device__ __forceinline__ void turn_phase_r(const Src &src, const TurnArgs &a, 
             const double t = ts.rho / beta;
             vr.x -= t * vq.x;
             vr.y -= t * vq.y;
-            st2(a.r, rp, vr);
+            st2_stream(a.r, rp, vr);
         }
         double2 vz = vr;
         if (a.inv_diag) {
@@ -296,7 +298,16 @@ __device__ __forceinline__ void turn_phase_h(const Src &src, const TurnArgs &a, 
         const int chunk = src.chunk_of(i);
         if (chunk < 0) continue;
         const RowPair rp = my_rows(chunk, a.n);
-        double2 vp = ld2(a.p, rp);
+        // with two p buffers this is the buffer's last read for a long while: past the caches.  A deferring head reads
+        // b[1], which is next read as p_pend a whole turn away; a head that updates x reads b[0], which is never read
+        // again -- the next launch overwrites it as its p_out.  In place the store below goes to the same line, which the
+        // next launch gathers: plain.  (p_pend in update_x is plain for that reason too: it is b[1], read only by the
+        // head whose p_out is b[1])
+        double2 vp;
+        if constexpr (K > 1)
+            vp = ld2_stream(a.p, rp);
+        else
+            vp = ld2(a.p, rp);
         if (!ts.defers && i >= n_early) update_x(rp, vp, K);
         // a deferring head that ends the solve: what is pending goes in now
         if (ts.defers && stop) update_x(rp, vp, ts.phase);
