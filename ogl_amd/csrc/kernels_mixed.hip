@@ -8,6 +8,7 @@
 #include <climits>
 
 #include "device_common.hpp"
+#include "sym_walk.hpp"
 
 namespace ogl {
 
@@ -35,12 +36,10 @@ __global__ __launch_bounds__(BLOCK) void k_mx_refresh(long n, const int *__restr
 }
 
 // ------------------------------------------------------------------------------------------
-// the inner SpMV on the fp32 twin of the half storage (k_spmv_sym's loads and order of additions: furthest lower entry
-// first, diagonal, upper entries -- ascending columns, every row from 0.0f) with the partial of pi = wide(p, q)
+// the inner SpMV on the fp32 twin of the half storage: k_spmv_sym's row walk itself, instantiated for float (sym_rows,
+// sym_walk.hpp: the same loads without the streaming ones, the sum in ascending columns, every row from 0.0f) with the
+// partial of pi = wide(p, q)
 // ------------------------------------------------------------------------------------------
-struct MxOffsets {
-    int d[SYM_MAX_OFFSETS];
-};
 // EPI (MxEpilogue): what follows the product.  MX_EPI_PI: the inner solve's y and partial.  The others serve the fine level
 // of Multigrid's cycle in single precision: gated by the Krylov loop's stop flag, they write y = A x
 // (_PLAIN), the sweep x + omega32 ((b - A x) inv_d) (_SWEEP; _SWEEP64: as doubles) or the residual b - A x (_RESIDUAL) --
@@ -71,7 +70,7 @@ __device__ __forceinline__ void mg_epilogue(const MgEpi &e, const RowPair &rp, c
 }
 
 template <int ND, bool FAST, int EPI>
-__global__ __launch_bounds__(BLOCK) void k_mx_spmv_sym(int n_rows, int n_chunks, MxOffsets off,
+__global__ __launch_bounds__(BLOCK) void k_mx_spmv_sym(int n_rows, int n_chunks, SymOffsets off,
                                                        const uint8_t *__restrict__ mask, const float *__restrict__ planes,
                                                        const float *__restrict__ x, float *__restrict__ y,
                                                        double *__restrict__ part, const MixedScalars *gate,
@@ -86,57 +85,8 @@ __global__ __launch_bounds__(BLOCK) void k_mx_spmv_sym(int n_rows, int n_chunks,
     const int chunk = block_order ? block_order[blockIdx.x] : xcd_chunk(blockIdx.x);
     if (chunk < 0 || chunk >= n_chunks) return;
     const RowPair rp = my_rows(chunk, n_rows);
-    const int t = threadIdx.x, row = rp.row;
-    const unsigned mm = *reinterpret_cast<const unsigned short *>(mask + row);
-    const unsigned m0 = mm & 0xffu, m1 = mm >> 8;
-    float2 up[ND];
-    const float *own = planes + (long)chunk * (ND * CHUNK_ROWS) + t * ROWS_PER_THREAD;
-#pragma unroll
-    for (int j = 0; j < ND; ++j) up[j] = *reinterpret_cast<const float2 *>(own + (long)j * CHUNK_ROWS);
-    const float2 xd = ld2(x, rp);
-    // every load is issued whatever the mask says, at an index clamped into its array (the mask decides what is used)
-    const int last = n_rows - 1, last_pair = last & ~1;  // (the vectors are allocated past n_rows)
-    float2 lo[ND], xl[ND], xu[ND];
-#pragma unroll
-    for (int j = 1; j < ND; ++j) {
-        const int r0 = max(row - off.d[j], 0), r1 = max(row + 1 - off.d[j], 0);
-        const long a0 = (long)(r0 >> 9) * (ND * CHUNK_ROWS) + (long)j * CHUNK_ROWS + (r0 & (CHUNK_ROWS - 1));
-        const long a1 = (long)(r1 >> 9) * (ND * CHUNK_ROWS) + (long)j * CHUNK_ROWS + (r1 & (CHUNK_ROWS - 1));
-        if (FAST && j >= 2) {  // even distance: an aligned pair of one chunk's plane
-            lo[j] = *reinterpret_cast<const float2 *>(planes + a0);
-            xl[j] = *reinterpret_cast<const float2 *>(x + min(max(row - off.d[j], 0), last_pair));
-            xu[j] = *reinterpret_cast<const float2 *>(x + min(row + off.d[j], last_pair));
-        } else if (FAST) {     // d = 1: A(row + 1, row) is this lane's own upper entry of row
-            lo[j].x = planes[a0];
-            lo[j].y = up[1].x;
-            xl[j].x = x[min(max(row - 1, 0), last)];
-            xl[j].y = xd.x;
-            xu[j].x = xd.y;
-            xu[j].y = x[min(row + 2, last)];
-        } else {
-            lo[j].x = planes[a0];
-            lo[j].y = planes[a1];
-            xl[j].x = x[min(max(row - off.d[j], 0), last)];
-            xl[j].y = x[min(max(row + 1 - off.d[j], 0), last)];
-            xu[j].x = x[min(row + off.d[j], last)];
-            xu[j].y = x[min(row + 1 + off.d[j], last)];
-        }
-    }
-    static_assert(CHUNK_ROWS == 512, "row >> 9 above");
-    float2 acc;
-    acc.x = acc.y = 0.0f;
-#pragma unroll
-    for (int j = ND - 1; j >= 1; --j) {
-        if ((m0 >> (ND - 1 - j)) & 1u) acc.x = acc.x + lo[j].x * xl[j].x;
-        if ((m1 >> (ND - 1 - j)) & 1u) acc.y = acc.y + lo[j].y * xl[j].y;
-    }
-    if ((m0 >> (ND - 1)) & 1u) acc.x = acc.x + up[0].x * xd.x;
-    if ((m1 >> (ND - 1)) & 1u) acc.y = acc.y + up[0].y * xd.y;
-#pragma unroll
-    for (int j = 1; j < ND; ++j) {
-        if ((m0 >> (ND - 1 + j)) & 1u) acc.x = acc.x + up[j].x * xu[j].x;
-        if ((m1 >> (ND - 1 + j)) & 1u) acc.y = acc.y + up[j].y * xu[j].y;
-    }
+    float2 xd;
+    const float2 acc = sym_rows<SPMV_PLAIN, float, ND, FAST, false>(chunk, rp, n_rows, off, mask, planes, x, nullptr, xd);
     if (EPI > MX_EPI_PLAIN) {
         mg_epilogue<EPI>(epi, rp, xd, acc);
         return;
@@ -604,27 +554,10 @@ static void mx_launch_sym(hipStream_t st, const DevSym &A, const float *planes, 
     if (A.n_rows == 0) return;
     const int nc = (int)n_chunks(A.n_rows);
     const dim3 grid(A.block_order ? A.n_blocks : xcd_grid(nc)), block(BLOCK);
-    MxOffsets off;
-    for (int j = 0; j < SYM_MAX_OFFSETS; ++j) off.d[j] = A.d[j];
-    bool fast = A.nd >= 2 && A.d[1] == 1;
-    for (int j = 2; j < A.nd; ++j) fast = fast && (A.d[j] % 2 == 0);
-#define OGL_MX_SYM(ND)                                                                                                  \
-    do {                                                                                                                \
-        if (fast)                                                                                                       \
-            hipLaunchKernelGGL((k_mx_spmv_sym<ND, true, EPI>), grid, block, 0, st, A.n_rows, nc, off, A.mask, planes, x, \
-                               y, part, gate, A.block_order, e);                                                        \
-        else                                                                                                            \
-            hipLaunchKernelGGL((k_mx_spmv_sym<ND, false, EPI>), grid, block, 0, st, A.n_rows, nc, off, A.mask, planes,  \
-                               x, y, part, gate, A.block_order, e);                                                     \
-    } while (0)
-    if (A.nd == 2)
-        OGL_MX_SYM(2);
-    else if (A.nd == 3)
-        OGL_MX_SYM(3);
-    else
-        OGL_MX_SYM(4);
-    static_assert(SYM_MAX_OFFSETS == 4, "instantiations above");
-#undef OGL_MX_SYM
+    sym_dispatch(A, [&](const SymOffsets &off, auto nd, auto fast, auto) {
+        hipLaunchKernelGGL((k_mx_spmv_sym<decltype(nd)::value, decltype(fast)::value, EPI>), grid, block, 0, st, A.n_rows, nc,
+                           off, A.mask, planes, x, y, part, gate, A.block_order, e);
+    });
 }
 
 template <int EPI>

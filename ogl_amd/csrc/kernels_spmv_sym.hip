@@ -1,145 +1,15 @@
 // kernels_spmv_sym.hip -- half-storage SpMV of banded symmetric patterns and the GKOCG turn kernels built on it
-// (geometry, reduction tree and the -ffp-contract=off rule: device_common.hpp)
+// (geometry, reduction tree and the -ffp-contract=off rule: device_common.hpp; the layout and its row walk -- planes,
+// twins, gathers, the sum in ascending column order -- and the ladder over ND, FAST, STREAM: sym_walk.hpp)
 #include <algorithm>
 
 #include "device_common.hpp"
 #include "resident_cg_turn.hpp"
+#include "sym_walk.hpp"
 
 namespace ogl {
 
 namespace {
-
-// ------------------------------------------------------------------------------------------
-// Half storage of a symmetric matrix on a banded pattern (SymLayout, host_matrix.hpp).  ND planes per
-// chunk: plane j holds A(r, r + d[j]), d[0] = 0.  A lower entry A(r, r - d[j]) is read where its twin
-// lives: plane j of row r - d[j] -- a coalesced strip of values that some workgroup reads (or has read) as
-// upper entries, so DRAM delivers every coefficient once; the second reader finds it in L2 / the Infinity
-// Cache.  8 ND + 1 bytes per row instead of 8.1 per stored entry: measured 115 us against 139 us for the
-// pattern-coded full storage on the 216^3 matrix (tools/sym_tune.hip, profiles/spmv_tune_r02.txt).  Rows are
-// summed in ascending column order -- furthest lower entry first, diagonal, upper entries -- so y and the
-// fused dot partials have the same bits as k_spmv_sell / k_spmv_stream.
-// ------------------------------------------------------------------------------------------
-struct SymOffsets {
-    int d[SYM_MAX_OFFSETS];
-};
-// the distances of a layout as a kernel argument; *fast: d[1] == 1 and the further distances even -- the straight-line
-// pair-load instantiations (FAST, below)
-SymOffsets sym_offsets(const DevSym &A, bool *fast)
-{
-    SymOffsets off;
-    for (int j = 0; j < SYM_MAX_OFFSETS; ++j) off.d[j] = A.d[j];
-    *fast = A.nd >= 2 && A.d[1] == 1;
-    for (int j = 2; j < A.nd; ++j) *fast = *fast && (A.d[j] % 2 == 0);
-    return off;
-}
-// FAST: d[1] == 1 and every further distance even (a box with an even line length) -- known at compile
-// time, so the kernel stays straight-line code (a run-time test of the parity splits the loads into basic
-// blocks that wait for each other: 130 us instead of 113, tools/sym_tune.hip var1/var2).  Then the two rows
-// of a lane are an aligned pair in every strip: x and the lower values of the even distances come as one
-// 16-byte load per pair, the d = 1 neighbours from the diagonal pair and the lane's own plane-1 value.
-// STREAM (planes + vectors larger than the Infinity Cache): the planes that are read exactly once per launch are
-// streamed past the caches -- the diagonal always, and with FAST also plane 1, whose second reader (the d = 1
-// lower entry of the next row) is the neighbouring lane: a lane shuffle instead of a load.
-//
-// sym_rows: the rows of one chunk -- every load, the mask, the sums in ascending column order -- shared by k_spmv_sym and
-// the held-q turn (k_cg_turn_held_q below).  Returns the pair's sums; xd_out: x at the two rows themselves.
-template <int MODE, int ND, bool FAST, bool STREAM>
-__device__ __forceinline__ double2 sym_rows(int chunk, const RowPair &rp, int n_rows, const SymOffsets &off,
-                                            const uint8_t *__restrict__ mask, const double *__restrict__ planes,
-                                            const double *__restrict__ x, const double *__restrict__ b,
-                                            double2 &xd_out)
-{
-    const int t = threadIdx.x;
-    const int row = rp.row;
-    // which of the 2 ND - 1 entries the two rows have: bit (ND-1-j) = the one at -d[j], bit (ND-1+j) = at +d[j]
-    const unsigned mm = *reinterpret_cast<const unsigned short *>(mask + row);
-    const unsigned m0 = mm & 0xffu, m1 = mm >> 8;
-    double2 acc;
-    acc.x = acc.y = 0.0;
-    if (MODE == SPMV_RESIDUAL) acc = ld2(b, rp);
-    // own planes: diagonal and upper entries of the two rows
-    double2 up[ND];
-    const double *own = planes + (long)chunk * (ND * CHUNK_ROWS) + t * ROWS_PER_THREAD;
-#pragma unroll
-    for (int j = 0; j < ND; ++j)
-        up[j] = (STREAM && (j == 0 || (FAST && j == 1))) ? ld_pair_stream(own + (long)j * CHUNK_ROWS)
-                                                         : *reinterpret_cast<const double2 *>(own + (long)j * CHUNK_ROWS);
-    const double2 xd = xd_out = ld2(x, rp);
-    // lower entries: plane j at rows row - d[j], row + 1 - d[j].  Every load is issued whatever the mask says, at an
-    // index clamped into its array (the mask decides below what is used): the loads do not wait for the mask
-    const int last = n_rows - 1, last_pair = last & ~1;  // (a pair load at the last even row: the vectors are allocated two past n_rows)
-    double2 lo[ND];
-#pragma unroll
-    for (int j = 1; j < ND; ++j) {
-        const int r0 = max(row - off.d[j], 0), r1 = max(row + 1 - off.d[j], 0);
-        const long a0 = (long)(r0 >> 9) * (ND * CHUNK_ROWS) + (long)j * CHUNK_ROWS + (r0 & (CHUNK_ROWS - 1));
-        const long a1 = (long)(r1 >> 9) * (ND * CHUNK_ROWS) + (long)j * CHUNK_ROWS + (r1 & (CHUNK_ROWS - 1));
-        if (FAST && j >= 2) {  // even distance: rows r0, r0 + 1 are an aligned pair of one chunk's plane
-            lo[j] = *reinterpret_cast<const double2 *>(planes + a0);
-        } else if (FAST) {     // d = 1: A(row + 1, row) is this lane's own upper entry of row
-            if (STREAM) {      // A(row, row - 1) is the previous lane's second plane-1 value (lane 0: from memory)
-                lo[j].x = __shfl_up(up[1].y, 1, WAVE);
-                if ((t & (WAVE - 1)) == 0) lo[j].x = planes[a0];
-            } else {
-                lo[j].x = planes[a0];
-            }
-            lo[j].y = up[1].x;
-        } else {
-            lo[j].x = planes[a0];
-            lo[j].y = planes[a1];
-        }
-    }
-    static_assert(CHUNK_ROWS == 512, "row >> 9 above");
-    double2 xl[ND], xu[ND];
-#pragma unroll
-    for (int j = 1; j < ND; ++j) {
-        if (FAST && j >= 2) {
-            xl[j] = *reinterpret_cast<const double2 *>(x + min(max(row - off.d[j], 0), last_pair));
-            xu[j] = *reinterpret_cast<const double2 *>(x + min(row + off.d[j], last_pair));
-        } else if (FAST) {     // the neighbours of a pair at distance 1: the pair itself + one on each side
-            xl[j].x = x[min(max(row - 1, 0), last)];
-            xl[j].y = xd.x;
-            xu[j].x = xd.y;
-            xu[j].y = x[min(row + 2, last)];
-        } else {
-            xl[j].x = x[min(max(row - off.d[j], 0), last)];
-            xl[j].y = x[min(max(row + 1 - off.d[j], 0), last)];
-            xu[j].x = x[min(row + off.d[j], last)];
-            xu[j].y = x[min(row + 1 + off.d[j], last)];
-        }
-    }
-#pragma unroll
-    for (int j = ND - 1; j >= 1; --j) {  // ascending columns: the furthest lower entry first
-        if ((m0 >> (ND - 1 - j)) & 1u) {
-            const double p = lo[j].x * xl[j].x;
-            acc.x = (MODE == SPMV_RESIDUAL) ? acc.x - p : acc.x + p;
-        }
-        if ((m1 >> (ND - 1 - j)) & 1u) {
-            const double p = lo[j].y * xl[j].y;
-            acc.y = (MODE == SPMV_RESIDUAL) ? acc.y - p : acc.y + p;
-        }
-    }
-    if ((m0 >> (ND - 1)) & 1u) {
-        const double p = up[0].x * xd.x;
-        acc.x = (MODE == SPMV_RESIDUAL) ? acc.x - p : acc.x + p;
-    }
-    if ((m1 >> (ND - 1)) & 1u) {
-        const double p = up[0].y * xd.y;
-        acc.y = (MODE == SPMV_RESIDUAL) ? acc.y - p : acc.y + p;
-    }
-#pragma unroll
-    for (int j = 1; j < ND; ++j) {
-        if ((m0 >> (ND - 1 + j)) & 1u) {
-            const double p = up[j].x * xu[j].x;
-            acc.x = (MODE == SPMV_RESIDUAL) ? acc.x - p : acc.x + p;
-        }
-        if ((m1 >> (ND - 1 + j)) & 1u) {
-            const double p = up[j].y * xu[j].y;
-            acc.y = (MODE == SPMV_RESIDUAL) ? acc.y - p : acc.y + p;
-        }
-    }
-    return acc;
-}
 
 template <int MODE, int NDOT, int ND, bool FAST, bool STREAM>
 __global__ __launch_bounds__(BLOCK) void k_spmv_sym(int n_rows, int n_chunks, SymOffsets off,
@@ -159,7 +29,7 @@ __global__ __launch_bounds__(BLOCK) void k_spmv_sym(int n_rows, int n_chunks, Sy
     if (chunk < 0 || chunk >= n_chunks) return;
     const RowPair rp = my_rows(chunk, n_rows);
     double2 xd;
-    double2 acc = sym_rows<MODE, ND, FAST, STREAM>(chunk, rp, n_rows, off, mask, planes, x, b, xd);
+    double2 acc = sym_rows<MODE, double, ND, FAST, STREAM>(chunk, rp, n_rows, off, mask, planes, x, b, xd);
     if (hf.chunk_bptr) halo_fused_add<MODE>(hf, chunk, acc.x, acc.y, ys);
     st2(y, rp, acc);
     if (NDOT >= 1) {
@@ -199,68 +69,20 @@ template <int ND>
 struct TurnSymRegs {
     double2 vd[2], vl[2][ND], vu[2][ND], up[ND], lo[ND];
 };
-// Every load is issued without waiting for the mask (mask -> gathers would be two round trips, and a small system
-// is all latency), at an index clamped into the vector; the mask decides later what is used.
+// The walk's loads (sym_walk.hpp), the vectors first, then the matrix; none waits for the mask -- a small system is all latency
 template <int ND, bool FAST, bool STREAM>
 __device__ __forceinline__ void turn_sym_load(TurnSymRegs<ND> &R, int chunk, const RowPair &rp, int n_rows,
                                               const SymOffsets &off, const double *__restrict__ planes,
                                               const double *__restrict__ p_in, const double *__restrict__ z)
 {
-    const int row = rp.row;
-    const double *src[2] = {p_in, z};
-    const int last = n_rows - 1, last_pair = last & ~1;  // (a pair load at the last even row: the vectors are allocated two past n_rows)
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        const double *__restrict__ v = src[a];
-        R.vd[a] = ld2(v, rp);
-#pragma unroll
-        for (int j = 1; j < ND; ++j) {
-            if (FAST && j >= 2) {
-                R.vl[a][j] = *reinterpret_cast<const double2 *>(v + min(max(row - off.d[j], 0), last_pair));
-                R.vu[a][j] = *reinterpret_cast<const double2 *>(v + min(row + off.d[j], last_pair));
-            } else if (FAST) {
-                R.vl[a][j].x = v[min(max(row - 1, 0), last)];
-                R.vl[a][j].y = R.vd[a].x;
-                R.vu[a][j].x = R.vd[a].y;
-                R.vu[a][j].y = v[min(row + 2, last)];
-            } else {
-                R.vl[a][j].x = v[min(max(row - off.d[j], 0), last)];
-                R.vl[a][j].y = v[min(max(row + 1 - off.d[j], 0), last)];
-                R.vu[a][j].x = v[min(row + off.d[j], last)];
-                R.vu[a][j].y = v[min(row + 1 + off.d[j], last)];
-            }
-        }
-    }
-    // the matrix, as k_spmv_sym reads it (STREAM: the planes read once per launch go past the caches)
-    const double *own = planes + (long)chunk * (ND * CHUNK_ROWS) + threadIdx.x * ROWS_PER_THREAD;
-#pragma unroll
-    for (int j = 0; j < ND; ++j)
-        R.up[j] = (STREAM && (j == 0 || (FAST && j == 1))) ? ld_pair_stream(own + (long)j * CHUNK_ROWS)
-                                                           : *reinterpret_cast<const double2 *>(own + (long)j * CHUNK_ROWS);
-#pragma unroll
-    for (int j = 1; j < ND; ++j) {
-        const int r0 = max(row - off.d[j], 0), r1 = max(row + 1 - off.d[j], 0);
-        const long a0 = (long)(r0 >> 9) * (ND * CHUNK_ROWS) + (long)j * CHUNK_ROWS + (r0 & (CHUNK_ROWS - 1));
-        const long a1 = (long)(r1 >> 9) * (ND * CHUNK_ROWS) + (long)j * CHUNK_ROWS + (r1 & (CHUNK_ROWS - 1));
-        if (FAST && j >= 2) {
-            R.lo[j] = *reinterpret_cast<const double2 *>(planes + a0);
-        } else if (FAST) {
-            if (STREAM) {  // A(row, row - 1) is the previous lane's second plane-1 value (lane 0: from memory)
-                const double prev = __shfl_up(R.up[1].y, 1, WAVE);
-                R.lo[j].x = prev;
-                if ((threadIdx.x & (WAVE - 1)) == 0) R.lo[j].x = planes[a0];
-            } else {
-                R.lo[j].x = planes[a0];
-            }
-            R.lo[j].y = R.up[1].x;
-        } else {
-            R.lo[j].x = planes[a0];
-            R.lo[j].y = planes[a1];
-        }
-    }
+    R.vd[0] = ld2(p_in, rp);
+    sym_gather<double, ND, FAST>(R.vl[0], R.vu[0], R.vd[0], rp.row, n_rows, off, p_in);
+    R.vd[1] = ld2(z, rp);
+    sym_gather<double, ND, FAST>(R.vl[1], R.vu[1], R.vd[1], rp.row, n_rows, off, z);
+    sym_own_planes<double, ND, FAST, STREAM>(R.up, chunk, planes);
+    sym_twin_planes<double, ND, FAST, STREAM>(R.lo, R.up, rp.row, off, planes);
 }
-// p_new = z + tmp p for the own rows (-> xd) and for every gathered column, then the two row sums in ascending
-// column order (k_spmv_sym's)
+// p_new = z + tmp p for the own rows (-> xd) and for every gathered column, then the walk's two row sums
 template <int ND>
 __device__ __forceinline__ double2 turn_sym_rows(const TurnSymRegs<ND> &R, unsigned m0, unsigned m1, double tmp,
                                                  double2 &xd)
@@ -277,19 +99,7 @@ __device__ __forceinline__ double2 turn_sym_rows(const TurnSymRegs<ND> &R, unsig
     }
     double2 acc;
     acc.x = acc.y = 0.0;
-#pragma unroll
-    for (int j = ND - 1; j >= 1; --j) {  // ascending columns: the furthest lower entry first
-        if ((m0 >> (ND - 1 - j)) & 1u) acc.x = acc.x + R.lo[j].x * xl[j].x;
-        if ((m1 >> (ND - 1 - j)) & 1u) acc.y = acc.y + R.lo[j].y * xl[j].y;
-    }
-    if ((m0 >> (ND - 1)) & 1u) acc.x = acc.x + R.up[0].x * xd.x;
-    if ((m1 >> (ND - 1)) & 1u) acc.y = acc.y + R.up[0].y * xd.y;
-#pragma unroll
-    for (int j = 1; j < ND; ++j) {
-        if ((m0 >> (ND - 1 + j)) & 1u) acc.x = acc.x + R.up[j].x * xu[j].x;
-        if ((m1 >> (ND - 1 + j)) & 1u) acc.y = acc.y + R.up[j].y * xu[j].y;
-    }
-    return acc;
+    return sym_sum<SPMV_PLAIN, double, ND>(m0, m1, R.up, R.lo, xd, xl, xu, acc);
 }
 
 // LEAD (more than FUSED_FIN_MAX_CHUNKS chunks): the first 32 workgroups of the launch are the finaliser's wavefronts, every
@@ -575,7 +385,7 @@ __global__ __launch_bounds__(BLOCK, B) void k_cg_turn_held_q(int n, int n_chunks
         }
         const RowPair rp = my_rows(chunk, n);
         double2 xd;
-        double2 vq = sym_rows<SPMV_PLAIN, ND, FAST, true>(chunk, rp, n, off, mask, planes, p, nullptr, xd);
+        double2 vq = sym_rows<SPMV_PLAIN, double, ND, FAST, true>(chunk, rp, n, off, mask, planes, p, nullptr, xd);
         if (rp.n < 2) vq.y = 0.0;  // (rows past the end: what ld2_stream(q) gives the two-launch turn)
         if (rp.n < 1) vq.x = 0.0;
         z.put(i, vq);
@@ -609,44 +419,23 @@ void launch_spmv_sym(hipStream_t st, const DevSym &A, int mode, const double *x,
     if (A.n_rows == 0) return;
     const int nc = (int)n_chunks(A.n_rows);
     const dim3 grid(A.block_order ? A.n_blocks : xcd_grid(nc)), block(BLOCK);
-    bool fast;
-    const SymOffsets off = sym_offsets(A, &fast);
-#define OGL_SYM_K(MODE, NDOT, ND, FAST, STREAM)                                                                          \
-    hipLaunchKernelGGL((k_spmv_sym<MODE, NDOT, ND, FAST, STREAM>), grid, block, 0, st, A.n_rows, nc, off, A.mask, A.planes, \
-                       x, b, y, dots.with, dots.part, dots.part_yy, gate, A.block_order, hf)
-#define OGL_SYM_ND(MODE, NDOT, ND)                   \
-    do {                                             \
-        if (fast && A.stream)                        \
-            OGL_SYM_K(MODE, NDOT, ND, true, true);   \
-        else if (fast)                               \
-            OGL_SYM_K(MODE, NDOT, ND, true, false);  \
-        else if (A.stream)                           \
-            OGL_SYM_K(MODE, NDOT, ND, false, true);  \
-        else                                         \
-            OGL_SYM_K(MODE, NDOT, ND, false, false); \
-    } while (0)
-#define OGL_SYM(MODE, NDOT)                    \
-    do {                                       \
-        if (A.nd == 2)                         \
-            OGL_SYM_ND(MODE, NDOT, 2);         \
-        else if (A.nd == 3)                    \
-            OGL_SYM_ND(MODE, NDOT, 3);         \
-        else                                   \
-            OGL_SYM_ND(MODE, NDOT, 4);         \
-    } while (0)
-    static_assert(SYM_MAX_OFFSETS == 4, "instantiations above");
-    if (mode == SPMV_RESIDUAL) {
-        OGL_SYM(SPMV_RESIDUAL, 0);
-    } else if (dots.part && dots.part_yy) {
-        OGL_SYM(SPMV_PLAIN, 2);
-    } else if (dots.part) {
-        OGL_SYM(SPMV_PLAIN, 1);
-    } else {
-        OGL_SYM(SPMV_PLAIN, 0);
-    }
-#undef OGL_SYM
-#undef OGL_SYM_ND
-#undef OGL_SYM_K
+    sym_dispatch(A, [&](const SymOffsets &off, auto nd, auto fast, auto stream) {
+        auto go = [&](auto m, auto ndot) {
+            hipLaunchKernelGGL((k_spmv_sym<decltype(m)::value, decltype(ndot)::value, decltype(nd)::value,
+                                           decltype(fast)::value, decltype(stream)::value>),
+                               grid, block, 0, st, A.n_rows, nc, off, A.mask, A.planes, x, b, y, dots.with, dots.part,
+                               dots.part_yy, gate, A.block_order, hf);
+        };
+        using Plain = std::integral_constant<int, SPMV_PLAIN>;
+        if (mode == SPMV_RESIDUAL)
+            go(std::integral_constant<int, SPMV_RESIDUAL>{}, std::integral_constant<int, 0>{});
+        else if (dots.part && dots.part_yy)
+            go(Plain{}, std::integral_constant<int, 2>{});
+        else if (dots.part)
+            go(Plain{}, std::integral_constant<int, 1>{});
+        else
+            go(Plain{}, std::integral_constant<int, 0>{});
+    });
 }
 
 void launch_cg_turn_sym(hipStream_t st, const DevSym &A, const double *p_in, double *p_out, double *x, const double *z,
@@ -657,34 +446,17 @@ void launch_cg_turn_sym(hipStream_t st, const DevSym &A, const double *p_in, dou
     const int nc = (int)n_chunks(A.n_rows);
     const dim3 grid(A.block_order ? A.n_blocks : xcd_grid(nc)), block(BLOCK);
     const bool led = lead.box && nc >= 3 * FIN_WAVES;
-    bool fast;
-    const SymOffsets off = sym_offsets(A, &fast);
-#define OGL_TURN_K(ND, FAST)                                                                                                  \
-    do {                                                                                                                      \
-        if (led)                                                                                                              \
-            hipLaunchKernelGGL((k_cg_turn_sym<ND, FAST, true>), grid, block, 0, st, A.n_rows, nc, off, A.mask, A.planes, p_in, \
-                               p_out, x, z, q, part_beta, sin, sout, part_rho, part_norm, nc, history, first, A.block_order,  \
-                               lead);                                                                                         \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((k_cg_turn_sym<ND, FAST, false>), grid, block, 0, st, A.n_rows, nc, off, A.mask, A.planes,     \
-                               p_in, p_out, x, z, q, part_beta, sin, sout, part_rho, part_norm, nc, history, first,           \
-                               A.block_order, LeadBox{});                                                                     \
-    } while (0)
-#define OGL_TURN_ND(ND)              \
-    do {                             \
-        if (fast)                    \
-            OGL_TURN_K(ND, true);    \
-        else                         \
-            OGL_TURN_K(ND, false);   \
-    } while (0)
-    if (A.nd == 2)
-        OGL_TURN_ND(2);
-    else if (A.nd == 3)
-        OGL_TURN_ND(3);
-    else
-        OGL_TURN_ND(4);
-#undef OGL_TURN_ND
-#undef OGL_TURN_K
+    sym_dispatch(A, [&](const SymOffsets &off, auto nd, auto fast, auto) {
+        auto go = [&](auto is_led, const LeadBox &box) {
+            hipLaunchKernelGGL((k_cg_turn_sym<decltype(nd)::value, decltype(fast)::value, decltype(is_led)::value>), grid,
+                               block, 0, st, A.n_rows, nc, off, A.mask, A.planes, p_in, p_out, x, z, q, part_beta, sin, sout,
+                               part_rho, part_norm, nc, history, first, A.block_order, box);
+        };
+        if (led)
+            go(std::true_type{}, lead);
+        else
+            go(std::false_type{}, LeadBox{});
+    });
 }
 
 void launch_cg_turn_sym_big(hipStream_t st, const DevSym &A, const double *p_in, double *p_out, double *x,
@@ -694,38 +466,18 @@ void launch_cg_turn_sym_big(hipStream_t st, const DevSym &A, const double *p_in,
     if (A.n_rows == 0) return;
     const int nc = (int)n_chunks(A.n_rows);
     const dim3 grid(A.block_order ? A.n_blocks : xcd_grid(nc)), block(BLOCK);
-    bool fast;
-    const SymOffsets off = sym_offsets(A, &fast);
-#define OGL_TURN_K(ND, FAST, STREAM)                                                                                \
-    do {                                                                                                            \
-        if (hf.chunk_bptr)                                                                                          \
-            hipLaunchKernelGGL((k_cg_turn_sym_big<ND, FAST, STREAM, true>), grid, block, 0, st, A.n_rows, nc, off,  \
-                               A.mask, A.planes, p_in, p_out, x, z, q, part_beta, s, A.block_order, hf, p_halo_in,  \
-                               p_halo_out);                                                                         \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_cg_turn_sym_big<ND, FAST, STREAM, false>), grid, block, 0, st, A.n_rows, nc, off, \
-                               A.mask, A.planes, p_in, p_out, x, z, q, part_beta, s, A.block_order, HaloFused{},    \
-                               nullptr, nullptr);                                                                   \
-    } while (0)
-#define OGL_TURN_ND(ND)                     \
-    do {                                    \
-        if (fast && A.stream)               \
-            OGL_TURN_K(ND, true, true);     \
-        else if (fast)                      \
-            OGL_TURN_K(ND, true, false);    \
-        else if (A.stream)                  \
-            OGL_TURN_K(ND, false, true);    \
-        else                                \
-            OGL_TURN_K(ND, false, false);   \
-    } while (0)
-    if (A.nd == 2)
-        OGL_TURN_ND(2);
-    else if (A.nd == 3)
-        OGL_TURN_ND(3);
-    else
-        OGL_TURN_ND(4);
-#undef OGL_TURN_ND
-#undef OGL_TURN_K
+    sym_dispatch(A, [&](const SymOffsets &off, auto nd, auto fast, auto stream) {
+        auto go = [&](auto halo, const HaloFused &h, const double *ph_in, double *ph_out) {
+            hipLaunchKernelGGL((k_cg_turn_sym_big<decltype(nd)::value, decltype(fast)::value, decltype(stream)::value,
+                                                  decltype(halo)::value>),
+                               grid, block, 0, st, A.n_rows, nc, off, A.mask, A.planes, p_in, p_out, x, z, q, part_beta, s,
+                               A.block_order, h, ph_in, ph_out);
+        };
+        if (hf.chunk_bptr)
+            go(std::true_type{}, hf, p_halo_in, p_halo_out);
+        else
+            go(std::false_type{}, HaloFused{}, nullptr, nullptr);
+    });
 }
 
 // The held-q turn: ND as launch_spmv_sym has them, FAST both, the streaming loads only, p in place or two buffers
@@ -767,45 +519,26 @@ void launch_cg_turn_held_q(hipStream_t st, const DevSym &A, double *r, const dou
     if (A.n_rows == 0) return;
     const int nc = (int)n_chunks(A.n_rows);
     const dim3 grid(hz.grid), block(BLOCK);
-    bool fast;
-    const SymOffsets off = sym_offsets(A, &fast);
-#define OGL_HELD_Q_K(K, ND, FAST)                                                                                        \
-    do {                                                                                                                 \
-        if (hq.static_slots < HQ_STATIC)                                                                                 \
-            OGL_HELD_Q_KD(K, ND, FAST, true);                                                                            \
-        else                                                                                                             \
-            OGL_HELD_Q_KD(K, ND, FAST, false);                                                                           \
-    } while (0)
-#define OGL_HELD_Q_KD(K, ND, FAST, DRAW)                                                                                 \
-    hipLaunchKernelGGL((OGL_HELD_Q(K, ND, FAST, DRAW)), grid, block, 0, st, A.n_rows, nc, hq.n_pos, off, A.mask, A.planes,     \
-                       A.block_order, r, inv_diag, p, K == 2 ? p_out : p, x, s, hz.tagged, history, lead,                \
-                       K == 2 ? (const double *)ring.b[1] : nullptr, K == 2 ? ring.phase : 0, hz.early_slots,            \
-                       hq.static_slots, hq.drawers, hq.heads, hq.parity)
-#define OGL_HELD_Q_ND(K, ND)              \
-    do {                                  \
-        if (fast)                         \
-            OGL_HELD_Q_K(K, ND, true);    \
-        else                              \
-            OGL_HELD_Q_K(K, ND, false);   \
-    } while (0)
-#define OGL_HELD_Q_RING(ND)         \
-    do {                            \
-        if (ring.k == 2)            \
-            OGL_HELD_Q_ND(2, ND);   \
-        else                        \
-            OGL_HELD_Q_ND(0, ND);   \
-    } while (0)
-    static_assert(SYM_MAX_OFFSETS == 4, "instantiations above");
-    if (A.nd == 2)
-        OGL_HELD_Q_RING(2);
-    else if (A.nd == 3)
-        OGL_HELD_Q_RING(3);
-    else
-        OGL_HELD_Q_RING(4);
-#undef OGL_HELD_Q_RING
-#undef OGL_HELD_Q_ND
-#undef OGL_HELD_Q_KD
-#undef OGL_HELD_Q_K
+    sym_dispatch(A, [&](const SymOffsets &off, auto nd, auto fast, auto) {
+        auto go = [&](auto k, auto draw) {
+            constexpr int K = decltype(k)::value;
+            hipLaunchKernelGGL((OGL_HELD_Q(K, decltype(nd)::value, decltype(fast)::value, decltype(draw)::value)), grid, block,
+                               0, st, A.n_rows, nc, hq.n_pos, off, A.mask, A.planes, A.block_order, r, inv_diag, p,
+                               K == 2 ? p_out : p, x, s, hz.tagged, history, lead,
+                               K == 2 ? (const double *)ring.b[1] : nullptr, K == 2 ? ring.phase : 0, hz.early_slots,
+                               hq.static_slots, hq.drawers, hq.heads, hq.parity);
+        };
+        auto with_k = [&](auto k) {
+            if (hq.static_slots < HQ_STATIC)
+                go(k, std::true_type{});
+            else
+                go(k, std::false_type{});
+        };
+        if (ring.k == 2)
+            with_k(std::integral_constant<int, 2>{});
+        else
+            with_k(std::integral_constant<int, 0>{});
+    });
 }
 #undef OGL_HELD_Q_EACH
 #undef OGL_HELD_Q

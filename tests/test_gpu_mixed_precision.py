@@ -40,6 +40,12 @@ SPMV_CASES = {
     "10x9x7": (lambda: synthetic.poisson_block(10, 9, 7), HALF),
     "6x6x6": (lambda: synthetic.poisson_block(6, 6, 6), HALF),
     "11x10x10": (lambda: synthetic.poisson_block(11, 10, 10), HALF),   # 1100 rows: three chunks
+    # the float instantiations of the shared half-storage walk with two and three planes, and a long line
+    "1031x1x1": (lambda: synthetic.poisson_block(1031, 1, 1), HALF),   # two planes, pair loads: three chunks, the last partial
+    "64x9x1": (lambda: synthetic.poisson_block(64, 9, 1), HALF),       # three planes, pair loads: 576 rows, two chunks
+    "33x31x1": (lambda: synthetic.poisson_block(33, 31, 1), HALF),     # three planes, odd line length (plain loads): 1023 rows
+    "127x1x1": (lambda: synthetic.poisson_block(127, 1, 1), HALF),     # two planes: fewer rows than one chunk
+    "258x2x2": (lambda: synthetic.poisson_block(258, 2, 2), HALF),     # four planes: a line longer than a wavefront's 128 rows
     "voronoi600": (lambda: synthetic.voronoi_case(600), CSR),
     "asymmetric": (lambda: synthetic.poisson_block(10, 9, 7, symmetric=False, off_upper=-0.9, off_lower=-1.1), CSR),
 }
