@@ -28,6 +28,8 @@ MG_CYCLE_PRECISION = {"double": 0, "single": 1}
 _MG_WORDS = {"cycle": MG_CYCLE, "aggregation": MG_AGGREGATION, "cyclePrecision": MG_CYCLE_PRECISION}
 # keyword orthoMethod of GKOGMRES: it travels as a property, as a number
 ORTHO_METHOD = {"mgs": 0, "cgs": 1, "cgs2": 2}
+# keyword basisPrecision of GKOGMRES: likewise
+BASIS_PRECISION = {"double": 0, "single": 1}
 FORMAT_COO, FORMAT_CSR, FORMAT_ELL = 0, 1, 2
 RENUMBER_OFF, RENUMBER_ON, RENUMBER_AUTO = 0, 1, 2
 IFACE_PROCESSOR, IFACE_CYCLIC = 0, 1
@@ -388,6 +390,11 @@ class Solver:
     def set_ortho_method(self, word):
         """The keyword orthoMethod ('mgs' | 'cgs' | 'cgs2': GKOGMRES' Gram-Schmidt step) for the next solves."""
         self.set_property("orthoMethod", float(ORTHO_METHOD[word]))
+        return self
+
+    def set_basis_precision(self, word):
+        """The keyword basisPrecision ('double' | 'single': how GKOGMRES stores its Krylov basis) for the next solves."""
+        self.set_property("basisPrecision", float(BASIS_PRECISION[word]))
         return self
 
     def apply_preconditioner(self, r):

@@ -319,6 +319,15 @@ __device__ __forceinline__ void st2(T *__restrict__ p, const RowPair &r, typenam
     else if (r.n == 1)
         p[r.row] = v.x;
 }
+// a pair as doubles: a pair of floats widened exactly (a stored fp32 Krylov basis, property basisPrecision single)
+__device__ __forceinline__ double2 widen2(const double2 &v) { return v; }
+__device__ __forceinline__ double2 widen2(const float2 &v)
+{
+    double2 r;
+    r.x = (double)v.x;
+    r.y = (double)v.y;
+    return r;
+}
 // the same for data that is not touched again this turn (streamed past the caches, so that the vectors the
 // next kernel needs stay in the Infinity Cache; +2.5 % turn rate at 216^3 for the x update alone)
 __device__ __forceinline__ double2 ld2_stream(const double *__restrict__ p, const RowPair &r)

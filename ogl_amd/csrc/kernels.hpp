@@ -631,17 +631,36 @@ void launch_gmres_mgs(hipStream_t st, int32_t n, double *w, const double *vprev,
 // multidot: the partials of w . V_j, j < k.  fin_h (one workgroup per j, k_finalize's tree): h[j] = sum of row j, and
 // h_col[j] = h[j] (add: h_col[j] + h[j]).  block_update: w -= sum_j h[j] V_j, j ascending; then the partials of w . w into
 // part_norm, or (part_dots != nullptr) those of w . V_j on the new w into part_dots.
+// (a `const float *V`: the basis stored in fp32, property basisPrecision single -- DESIGN.md section 7e; each entry is
+//  widened exactly where it is loaded and the arithmetic is the double one)
 void launch_gmres_multidot(hipStream_t st, int32_t n, const double *w, const double *V, int64_t ld, int32_t k, double *part,
+                           const DevScalars *gate);
+void launch_gmres_multidot(hipStream_t st, int32_t n, const double *w, const float *V, int64_t ld, int32_t k, double *part,
                            const DevScalars *gate);
 void launch_gmres_fin_h(hipStream_t st, int32_t n, const DevScalars *gate, const double *part, int32_t k, double *h,
                         double *h_col, bool add);
 void launch_gmres_block_update(hipStream_t st, int32_t n, double *w, const double *V, int64_t ld, int32_t k, const double *h,
+                               double *part_norm, double *part_dots, const DevScalars *gate);
+void launch_gmres_block_update(hipStream_t st, int32_t n, double *w, const float *V, int64_t ld, int32_t k, const double *h,
                                double *part_norm, double *part_dots, const DevScalars *gate);
 // t_i = sum_{j < it} V_j[i] * y[j] ; with `before` != nullptr the sum is stored there, otherwise
 // x_i += t_i * inv_diag_i (inv_diag == nullptr: x_i += t_i)
 void launch_gmres_update_x(hipStream_t st, int32_t n, const double *V, int64_t ld, const double *y,
                            int32_t it, const double *inv_diag, double *x, double *before,
                            const DevScalars *gate);
+void launch_gmres_update_x(hipStream_t st, int32_t n, const float *V, int64_t ld, const double *y, int32_t it,
+                           const double *inv_diag, double *x, double *before, const DevScalars *gate);
+// basisPrecision single, the head of a turn: v_out = fl32(in / *denom) as floats and w = wide(v_out) (inv_diag != nullptr:
+// times inv_diag), in place of launch_gmres_scale / launch_gmres_scale_mul
+void launch_gmres_head_f32(hipStream_t st, int32_t n, float *v_out, const double *in, const double *denom,
+                           const double *inv_diag, double *w, const DevScalars *gate);
+// The Krylov basis a GKOGMRES solve works on: one of the two is set (launch_key.hpp hashes it)
+struct GmresBasis {
+    const double *V = nullptr;  // basisPrecision double
+    const float *Vf = nullptr;  // basisPrecision single
+    int64_t ld = 0;             // leading dimension, in elements of the stored type
+    int32_t single = 0, pad_ = 0;
+};
 // out = in * inv_diag (scalar Jacobi apply), x += a
 void launch_mul(hipStream_t st, int32_t n, double *out, const double *in, const double *inv_diag,
                 const DevScalars *gate);

@@ -8,6 +8,8 @@
 // One workgroup per 512-row chunk, thread t owns rows 2t and 2t + 1; every per-(j, chunk) partial is block_sum's value, so
 // the bits are those of k_gmres_mgs' dot product.  No kernel waits for another workgroup: the launches of a turn are ordered
 // by the stream.  Every kernel is gated on DevScalars::stop.
+// The basis type B is a template parameter (property basisPrecision: DESIGN.md section 7e): a basis stored as floats is
+// loaded 8 bytes per vector and lane and widened exactly; every product, sum and tree is the double one.
 #include "device_common.hpp"
 
 namespace ogl {
@@ -40,20 +42,28 @@ __device__ __forceinline__ void slots_to_part(int j0, int cnt, double *slot, dou
     }
     __syncthreads();
 }
-__device__ __forceinline__ void chunk_dots(const double *__restrict__ V, long ld, int j0, int cnt, const double2 &vw,
+// The held kernel uses a vector's pair twice, in the update and in the dot products.  A pair of floats passes through here
+// between the two, so that the second use widens it again: otherwise the compiler keeps the doubles of the first use, 4
+// VGPRs per vector as for a double basis, instead of the 2 that the floats take.
+__device__ __forceinline__ void keep_stored(double2 &) {}
+__device__ __forceinline__ void keep_stored(float2 &v) { asm volatile("" : "+v"(v.x), "+v"(v.y)); }
+
+template <class B>
+__device__ __forceinline__ void chunk_dots(const B *__restrict__ V, long ld, int j0, int cnt, const double2 &vw,
                                            const RowPair &rp, double *slot, double *__restrict__ part, int n_part, int chunk)
 {
-    double2 v[GS_BATCH];
+    typename PairOf<B>::type v[GS_BATCH];
 #pragma unroll
     for (int b = 0; b < GS_BATCH; ++b)
         if (b < cnt) v[b] = ld2(V + (size_t)(j0 + b) * ld, rp);
 #pragma unroll
     for (int b = 0; b < GS_BATCH; ++b)
-        if (b < cnt) dot_to_slot(v[b], b, vw, rp, slot);
+        if (b < cnt) dot_to_slot(widen2(v[b]), b, vw, rp, slot);
     slots_to_part(j0, cnt, slot, part, n_part, chunk);
 }
 
-__global__ __launch_bounds__(BLOCK) void k_gmres_multidot(int n, const double *__restrict__ w, const double *__restrict__ V,
+template <class B>
+__global__ __launch_bounds__(BLOCK) void k_gmres_multidot(int n, const double *__restrict__ w, const B *__restrict__ V,
                                                           long ld, int k, double *__restrict__ part, int n_part,
                                                           const DevScalars *gate)
 {
@@ -88,8 +98,8 @@ __global__ __launch_bounds__(FIN_BLOCK) void k_gmres_fin_h(const DevScalars *gat
 // read a second time, last read first.  Measured, that second reading costs as much as the first (the rows are not found
 // in the L2 of the XCD: DESIGN.md section 7d), so this instantiation runs only beyond GS_HELD_MAX basis vectors; up to there
 // k_gmres_block_update_held keeps the rows in registers.
-template <bool NORM, bool DOTS>
-__global__ __launch_bounds__(BLOCK) void k_gmres_block_update(int n, double *__restrict__ w, const double *__restrict__ V,
+template <bool NORM, bool DOTS, class B>
+__global__ __launch_bounds__(BLOCK) void k_gmres_block_update(int n, double *__restrict__ w, const B *__restrict__ V,
                                                               long ld, int k, const double *__restrict__ h,
                                                               double *__restrict__ part_out, int n_part,
                                                               const DevScalars *gate)
@@ -101,7 +111,7 @@ __global__ __launch_bounds__(BLOCK) void k_gmres_block_update(int n, double *__r
     double2 t = ld2(w, rp);
     for (int j0 = 0; j0 < k; j0 += GS_BATCH) {
         const int cnt = min(GS_BATCH, k - j0);
-        double2 v[GS_BATCH];
+        typename PairOf<B>::type v[GS_BATCH];
         double hj[GS_BATCH];
 #pragma unroll
         for (int b = 0; b < GS_BATCH; ++b)
@@ -112,8 +122,9 @@ __global__ __launch_bounds__(BLOCK) void k_gmres_block_update(int n, double *__r
 #pragma unroll
         for (int b = 0; b < GS_BATCH; ++b)
             if (b < cnt) {
-                t.x -= hj[b] * v[b].x;
-                t.y -= hj[b] * v[b].y;
+                const double2 vb = widen2(v[b]);
+                t.x -= hj[b] * vb.x;
+                t.y -= hj[b] * vb.y;
             }
     }
     st2(w, rp, t);
@@ -132,10 +143,11 @@ __global__ __launch_bounds__(BLOCK) void k_gmres_block_update(int n, double *__r
 }
 
 // The update with cgs2's second-round partials for up to KMAX basis vectors: a thread keeps its two rows of every V_j in
-// registers (4 VGPRs per vector) from the update to the dot products, so V is read once.  All loads are issued before the
-// first use; the arithmetic and the trees are those of k_gmres_block_update<false, true>.
-template <int KMAX>
-__global__ __launch_bounds__(BLOCK) void k_gmres_block_update_held(int n, double *__restrict__ w, const double *__restrict__ V,
+// registers (4 VGPRs per vector; a float basis: the floats, 2 VGPRs per vector, widened at each use) from the update to the
+// dot products, so V is read once.  All loads are issued before the first use; the arithmetic and the trees are those of
+// k_gmres_block_update<false, true>.
+template <int KMAX, class B>
+__global__ __launch_bounds__(BLOCK) void k_gmres_block_update_held(int n, double *__restrict__ w, const B *__restrict__ V,
                                                                    long ld, int k, const double *__restrict__ h,
                                                                    double *__restrict__ part_out, int n_part,
                                                                    const DevScalars *gate)
@@ -146,7 +158,7 @@ __global__ __launch_bounds__(BLOCK) void k_gmres_block_update_held(int n, double
     const int chunk = blockIdx.x;
     const RowPair rp = my_rows(chunk, n);
     double2 t = ld2(w, rp);
-    double2 v[KMAX];
+    typename PairOf<B>::type v[KMAX];
 #pragma unroll
     for (int j = 0; j < KMAX; ++j)
         if (j < k) v[j] = ld2(V + (size_t)j * ld, rp);
@@ -154,29 +166,68 @@ __global__ __launch_bounds__(BLOCK) void k_gmres_block_update_held(int n, double
     for (int j = 0; j < KMAX; ++j)
         if (j < k) {
             const double hj = h[j];
-            t.x -= hj * v[j].x;
-            t.y -= hj * v[j].y;
+            const double2 vj = widen2(v[j]);
+            t.x -= hj * vj.x;
+            t.y -= hj * vj.y;
         }
     st2(w, rp, t);
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j)
+        if (j < k) keep_stored(v[j]);
 #pragma unroll
     for (int j0 = 0; j0 < KMAX; j0 += GS_BATCH)
         if (j0 < k) {
 #pragma unroll
             for (int b = 0; b < GS_BATCH; ++b)
-                if (j0 + b < k) dot_to_slot(v[j0 + b], b, t, rp, slot);
+                if (j0 + b < k) dot_to_slot(widen2(v[j0 + b]), b, t, rp, slot);
             slots_to_part(j0, min(GS_BATCH, k - j0), slot, part_out, n_part, chunk);
         }
 }
 constexpr int GS_HELD_MAX = 32;  // basis vectors a thread holds (krylovDim 30 and one more); beyond: the second reading
+
+
+template <class B>
+void multidot(hipStream_t st, int32_t n, const double *w, const B *V, int64_t ld, int32_t k, double *part, const DevScalars *gate)
+{
+    const int nc = (int)n_chunks(n);
+    if (nc == 0 || k <= 0) return;
+    hipLaunchKernelGGL(k_gmres_multidot<B>, dim3(nc), dim3(BLOCK), 0, st, n, w, V, (long)ld, k, part, nc, gate);
+}
+
+template <class B>
+void block_update(hipStream_t st, int32_t n, double *w, const B *V, int64_t ld, int32_t k, const double *h, double *part_norm,
+                  double *part_dots, const DevScalars *gate)
+{
+    const int nc = (int)n_chunks(n);
+    if (nc == 0 || k <= 0) return;
+    if (part_dots && k <= GS_BATCH)
+        hipLaunchKernelGGL((k_gmres_block_update_held<GS_BATCH, B>), dim3(nc), dim3(BLOCK), 0, st, n, w, V, (long)ld, k, h,
+                           part_dots, nc, gate);
+    else if (part_dots && k <= 2 * GS_BATCH)
+        hipLaunchKernelGGL((k_gmres_block_update_held<2 * GS_BATCH, B>), dim3(nc), dim3(BLOCK), 0, st, n, w, V, (long)ld, k, h,
+                           part_dots, nc, gate);
+    else if (part_dots && k <= GS_HELD_MAX)
+        hipLaunchKernelGGL((k_gmres_block_update_held<GS_HELD_MAX, B>), dim3(nc), dim3(BLOCK), 0, st, n, w, V, (long)ld, k, h,
+                           part_dots, nc, gate);
+    else if (part_dots)
+        hipLaunchKernelGGL((k_gmres_block_update<false, true, B>), dim3(nc), dim3(BLOCK), 0, st, n, w, V, (long)ld, k, h,
+                           part_dots, nc, gate);
+    else
+        hipLaunchKernelGGL((k_gmres_block_update<true, false, B>), dim3(nc), dim3(BLOCK), 0, st, n, w, V, (long)ld, k, h,
+                           part_norm, nc, gate);
+}
 
 }  // namespace
 
 void launch_gmres_multidot(hipStream_t st, int32_t n, const double *w, const double *V, int64_t ld, int32_t k, double *part,
                            const DevScalars *gate)
 {
-    const int nc = (int)n_chunks(n);
-    if (nc == 0 || k <= 0) return;
-    hipLaunchKernelGGL(k_gmres_multidot, dim3(nc), dim3(BLOCK), 0, st, n, w, V, (long)ld, k, part, nc, gate);
+    multidot(st, n, w, V, ld, k, part, gate);
+}
+void launch_gmres_multidot(hipStream_t st, int32_t n, const double *w, const float *V, int64_t ld, int32_t k, double *part,
+                           const DevScalars *gate)
+{
+    multidot(st, n, w, V, ld, k, part, gate);
 }
 
 void launch_gmres_fin_h(hipStream_t st, int32_t n, const DevScalars *gate, const double *part, int32_t k, double *h,
@@ -193,23 +244,12 @@ void launch_gmres_fin_h(hipStream_t st, int32_t n, const DevScalars *gate, const
 void launch_gmres_block_update(hipStream_t st, int32_t n, double *w, const double *V, int64_t ld, int32_t k, const double *h,
                                double *part_norm, double *part_dots, const DevScalars *gate)
 {
-    const int nc = (int)n_chunks(n);
-    if (nc == 0 || k <= 0) return;
-    if (part_dots && k <= GS_BATCH)
-        hipLaunchKernelGGL(k_gmres_block_update_held<GS_BATCH>, dim3(nc), dim3(BLOCK), 0, st, n, w, V, (long)ld, k, h,
-                           part_dots, nc, gate);
-    else if (part_dots && k <= 2 * GS_BATCH)
-        hipLaunchKernelGGL(k_gmres_block_update_held<2 * GS_BATCH>, dim3(nc), dim3(BLOCK), 0, st, n, w, V, (long)ld, k, h,
-                           part_dots, nc, gate);
-    else if (part_dots && k <= GS_HELD_MAX)
-        hipLaunchKernelGGL(k_gmres_block_update_held<GS_HELD_MAX>, dim3(nc), dim3(BLOCK), 0, st, n, w, V, (long)ld, k, h,
-                           part_dots, nc, gate);
-    else if (part_dots)
-        hipLaunchKernelGGL((k_gmres_block_update<false, true>), dim3(nc), dim3(BLOCK), 0, st, n, w, V, (long)ld, k, h,
-                           part_dots, nc, gate);
-    else
-        hipLaunchKernelGGL((k_gmres_block_update<true, false>), dim3(nc), dim3(BLOCK), 0, st, n, w, V, (long)ld, k, h,
-                           part_norm, nc, gate);
+    block_update(st, n, w, V, ld, k, h, part_norm, part_dots, gate);
+}
+void launch_gmres_block_update(hipStream_t st, int32_t n, double *w, const float *V, int64_t ld, int32_t k, const double *h,
+                               double *part_norm, double *part_dots, const DevScalars *gate)
+{
+    block_update(st, n, w, V, ld, k, h, part_norm, part_dots, gate);
 }
 
 }  // namespace ogl

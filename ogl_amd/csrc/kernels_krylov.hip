@@ -1159,7 +1159,34 @@ __global__ __launch_bounds__(BLOCK) void k_gmres_mgs_fold(int n, double *__restr
     if (threadIdx.x == 0) part_out[chunk] = s0;
 }
 
-__global__ __launch_bounds__(BLOCK) void k_gmres_update_x(int n, const double *__restrict__ V,
+// basisPrecision single, the head of turn `it`: V_it = fl32(in / *denom) stored as floats, and
+// w = wide(V_it) (scalar Jacobi: times the inverse diagonal), the input of the SpMV or of the preconditioner.  `in` is the
+// fp64 residual (it == 0) or the fp64 working vector of the turn before; 8 N bytes read, 12 N written.
+__global__ __launch_bounds__(BLOCK) void k_gmres_head_f32(int n, float *__restrict__ v_out, const double *__restrict__ in,
+                                                          const double *__restrict__ denom,
+                                                          const double *__restrict__ inv_diag, double *__restrict__ w,
+                                                          const DevScalars *gate)
+{
+    if (gate && gate->stop) return;
+    const double d = *denom;
+    const RowPair rp = my_rows(blockIdx.x, n);
+    const double2 v = ld2(in, rp);
+    double2 vi;
+    if (inv_diag) vi = ld2(inv_diag, rp);
+    float2 f;
+    f.x = (float)(v.x / d);  // (one rounding to binary32, nearest-even)
+    f.y = (float)(v.y / d);
+    st2(v_out, rp, f);
+    double2 u = widen2(f);
+    if (inv_diag) {
+        u.x = u.x * vi.x;
+        u.y = u.y * vi.y;
+    }
+    st2(w, rp, u);
+}
+
+template <class B>
+__global__ __launch_bounds__(BLOCK) void k_gmres_update_x(int n, const B *__restrict__ V,
                                                           long ld, const double *__restrict__ y,
                                                           int it, const double *__restrict__ inv_diag,
                                                           double *__restrict__ x,
@@ -1173,7 +1200,7 @@ __global__ __launch_bounds__(BLOCK) void k_gmres_update_x(int n, const double *_
     sum.y = 0.0;
     for (int j = 0; j < it; ++j) {
         const double yj = y[j];
-        const double2 v = ld2(V + (size_t)j * ld, rp);
+        const double2 v = widen2(ld2(V + (size_t)j * ld, rp));
         sum.x += v.x * yj;
         sum.y += v.y * yj;
     }
@@ -1715,8 +1742,24 @@ void launch_gmres_update_x(hipStream_t st, int32_t n, const double *V, int64_t l
 {
     const int nc = (int)n_chunks(n);
     if (nc == 0) return;
-    hipLaunchKernelGGL(k_gmres_update_x, dim3(nc), dim3(BLOCK), 0, st, n, V, (long)ld, y, it,
+    hipLaunchKernelGGL(k_gmres_update_x<double>, dim3(nc), dim3(BLOCK), 0, st, n, V, (long)ld, y, it,
                        inv_diag, x, before, gate);
+}
+void launch_gmres_update_x(hipStream_t st, int32_t n, const float *V, int64_t ld, const double *y, int32_t it,
+                           const double *inv_diag, double *x, double *before, const DevScalars *gate)
+{
+    const int nc = (int)n_chunks(n);
+    if (nc == 0) return;
+    hipLaunchKernelGGL(k_gmres_update_x<float>, dim3(nc), dim3(BLOCK), 0, st, n, V, (long)ld, y, it,
+                       inv_diag, x, before, gate);
+}
+
+void launch_gmres_head_f32(hipStream_t st, int32_t n, float *v_out, const double *in, const double *denom,
+                           const double *inv_diag, double *w, const DevScalars *gate)
+{
+    const int nc = (int)n_chunks(n);
+    if (nc == 0) return;
+    hipLaunchKernelGGL(k_gmres_head_f32, dim3(nc), dim3(BLOCK), 0, st, n, v_out, in, denom, inv_diag, w, gate);
 }
 
 void launch_mul(hipStream_t st, int32_t n, double *out, const double *in, const double *inv_diag,

@@ -70,6 +70,8 @@ inline void visit(KeyHasher &h, const HeldQ &a)
 {
     h(a.on), h(a.n_pos), h(a.static_slots), h(a.drawers), h(a.heads), h(a.parity);
 }
+OGL_VIEW_FIELDS(GmresBasis, 32);
+inline void visit(KeyHasher &h, const GmresBasis &a) { h(a.V), h(a.Vf), h(a.ld), h(a.single); }
 
 #undef OGL_VIEW_FIELDS
 

@@ -537,6 +537,7 @@ struct ogl_solver {
     ogl::DevBuf<double> d_bj_tmp0, d_bj_tmp1;  // block Jacobi through a permutation, staged apply: in / out in the caller's order
     ogl::DevBuf<double> d_v, d_s, d_t, d_y, d_z, d_rr;  // BiCGStab
     ogl::DevBuf<double> d_V, d_gm;                      // GMRES: Krylov bases, dense state
+    ogl::DevBuf<float> d_Vf;  // the basis stored in fp32 (property basisPrecision single): sized in krylov_prepare by such a solve only
     // orthoMethod cgs | cgs2: (m + 1) x n_chunks partials of a round's dot products and its m + 1 coefficients; sized in
     // krylov_prepare, never for mgs (a solve on mgs leaves them as they are)
     ogl::DevBuf<double> d_gs_part, d_gs_h;
@@ -665,6 +666,8 @@ struct ogl_solver {
     // property orthoMethod (0 mgs | 1 cgs | 2 cgs2; GKOGMRES only, ignored elsewhere): its validation and the refusal on
     // several ranks (OGL_ERR_INVALID / _UNSUPPORTED)
     int ortho_requested(int *method);
+    // property basisPrecision (0 double | 1 single; GKOGMRES only, ignored elsewhere): its validation and the refusal with mgs
+    int basis_requested(bool *single);
     int spmv_f32(const float *x, float *y);
     // run_krylov = plan -> prepare -> loop -> finish; one function per solver x turn shape (solver.cpp)
     struct KrylovRun;
@@ -676,6 +679,7 @@ struct ogl_solver {
     int gmres_restart(KrylovRun &k, const ogl::DevScalars *gate);
     int gmres_update_x(KrylovRun &k, int cols, const ogl::DevScalars *gate);
     int turn_gmres(KrylovRun &k, int enq, int pe);
+    int turn_gmres_f32_basis(KrylovRun &k, int it, int pe);
     int time_ortho_kernels(KrylovRun &k);  // (property orthoTimedLaunches: measurements only)
     int turn_cg_generic(KrylovRun &k, int enq, int pe);
     int turn_cg_generic_led(KrylovRun &k, int enq, int pe);

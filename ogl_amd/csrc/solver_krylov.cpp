@@ -128,6 +128,12 @@ struct ogl_solver::KrylovRun {
     int m = 0;        // Krylov dimension of GKOGMRES
     int ortho = 0;    // GKOGMRES: 0 modified Gram-Schmidt, 1 | 2 classical Gram-Schmidt in block form, one | two rounds
     int64_t ldv = 0;  // leading dimension of the Krylov bases
+    // basisPrecision single: the basis is stored as floats (d_Vf, leading dimension ldvf, every vector 16-byte aligned) and
+    // the turn's working vector lives in nx_buf, fp64, not in a basis slot
+    bool basis_single = false;
+    int64_t ldvf = 0;
+    double *nx_buf = nullptr;
+    GmresBasis basis{};
     double n_global = 0.0;
     size_t n_halo = 0;
     double *p0 = nullptr, *p1 = nullptr, *ph = nullptr;  // p of even / odd turns (merged turn), old p at the halo columns
@@ -189,6 +195,24 @@ int ogl_solver::ortho_requested(int *method)
     return OGL_OK;
 }
 
+// Property basisPrecision: how GKOGMRES stores its Krylov basis: 0 double, 1 single -- every store
+// into the basis rounded to binary32, every operation on it in double.  It has kernels in block form only (orthoMethod
+// cgs | cgs2); with mgs it is refused, not run on a double basis in silence.  GKOCG and GKOBiCGStab ignore the keyword.
+int ogl_solver::basis_requested(bool *single)
+{
+    *single = false;
+    if (cfg.solver != OGL_SOLVER_GMRES) return OGL_OK;
+    const double v = prop("basisPrecision", 0.0);
+    if (v != 0.0 && v != 1.0) return fail(OGL_ERR_INVALID, "basisPrecision %g is neither 0 (double) nor 1 (single)", v);
+    int ortho = 0;
+    OGL_TRY(ortho_requested(&ortho));
+    if (v == 1.0 && ortho == 0)
+        return fail(OGL_ERR_UNSUPPORTED, "basisPrecision single needs orthoMethod cgs or cgs2: orthoMethod mgs has no kernels "
+                    "for a basis stored in fp32");
+    *single = v == 1.0;
+    return OGL_OK;
+}
+
 int ogl_solver::run_krylov(ogl_perf *perf)
 {
     bool mixed_on = false;  // (property mixedPrecision: solver_mixed.cpp)
@@ -245,6 +269,8 @@ int ogl_solver::krylov_plan(KrylovRun &k)
     //  bytes, and the wait for the leaders costs it what the finaliser launch did: 216^3 GMRES(30) 1068 against 1047 us per turn)
     OGL_TRY(ortho_requested(&k.ortho));  // (the block forms of Gram-Schmidt have no links to fold a finaliser into)
     props["orthoMethodInUse"] = (double)k.ortho;
+    OGL_TRY(basis_requested(&k.basis_single));
+    k.ldvf = ((int64_t)n + 3) & ~(int64_t)3;
     k.gmres_fold = gmres && !k.ortho && (small || (lead_any && prop("gmresLead", 0.0) != 0.0)) && prop("gmresFold", 1.0) != 0.0;
     // launches of a single-rank turn, averaged over a full cycle: the SpMV's one, the scaling's one and the Gram-Schmidt step
     // with the column's finaliser -- it + 3 folded links or 2 it + 4 launches at column `it`, 4 | 6 in block form (the
@@ -377,7 +403,18 @@ int ogl_solver::krylov_prepare(KrylovRun &k)
             OGL_TRY(d_z.alloc(nv, st));
         }
     } else if (gmres) {
-        OGL_TRY(d_V.alloc((size_t)(m + 1) * (size_t)k.ldv, st));
+        // (only the basis of the precision this solve runs is sized; the other one, if an earlier solve left one, is kept)
+        if (k.basis_single)
+            OGL_TRY(d_Vf.alloc((size_t)(m + 1) * (size_t)k.ldvf, st));
+        else
+            OGL_TRY(d_V.alloc((size_t)(m + 1) * (size_t)k.ldv, st));
+        k.nx_buf = d_q.p;  // (q is GKOCG's; here it is free once the norm factor is formed)
+        k.basis.single = k.basis_single ? 1 : 0;
+        k.basis.V = k.basis_single ? nullptr : d_V.p;
+        k.basis.Vf = k.basis_single ? d_Vf.p : nullptr;
+        k.basis.ld = k.basis_single ? k.ldvf : k.ldv;
+        props["basisPrecisionInUse"] = k.basis_single ? 1.0 : 0.0;
+        props["basisBytes"] = k.basis_single ? (double)(d_Vf.n * sizeof(float)) : (double)(d_V.n * sizeof(double));
         OGL_TRY(d_gm.alloc(gmres_state_len(m), st));
         OGL_HIP_CHECK(hipMemsetAsync(d_gm.p, 0, gmres_state_len(m) * sizeof(double), st));
         if (generic) OGL_TRY(d_z.alloc((size_t)n + 2, st));
@@ -500,7 +537,8 @@ int ogl_solver::gmres_restart(KrylovRun &k, const DevScalars *gate)
     k.fg.check_after = gate ? 0 : 1;
     OGL_TRY(finalize(FIN_GMRES_RESTART, k.fg));
     k.fg.check_after = 0;
-    if (!k.gmres_scale_late()) launch_gmres_scale(k.st, k.n, d_V.p, d_r.p, k.beta_ptr, gate);
+    // (basisPrecision single: V_0 = fl32(r / rn) is stored by the head of the turn that follows)
+    if (!k.basis_single && !k.gmres_scale_late()) launch_gmres_scale(k.st, k.n, d_V.p, d_r.p, k.beta_ptr, gate);
     return OGL_OK;
 }
 
@@ -511,12 +549,15 @@ int ogl_solver::gmres_update_x(KrylovRun &k, int cols, const DevScalars *gate)
     k.fg.n_sums = 0;
     k.fg.turn = cols;
     OGL_TRY(finalize(FIN_GMRES_SOLVE, k.fg));
+    double *const before = k.generic ? d_w.p : nullptr;
+    const double *const diag = k.generic ? nullptr : precond;
+    if (k.basis_single)
+        launch_gmres_update_x(k.st, k.n, d_Vf.p, k.ldvf, k.gm_y, cols, diag, d_x.p, before, gate);
+    else
+        launch_gmres_update_x(k.st, k.n, d_V.p, k.ldv, k.gm_y, cols, diag, d_x.p, before, gate);
     if (k.generic) {
-        launch_gmres_update_x(k.st, k.n, d_V.p, k.ldv, k.gm_y, cols, nullptr, d_x.p, d_w.p, gate);
         apply_preconditioner(d_w.p, d_z.p, gate);
         launch_add(k.st, k.n, d_x.p, d_z.p, gate);
-    } else {
-        launch_gmres_update_x(k.st, k.n, d_V.p, k.ldv, k.gm_y, cols, precond, d_x.p, nullptr, gate);
     }
     return OGL_OK;
 }
@@ -539,6 +580,7 @@ int ogl_solver::turn_gmres(KrylovRun &k, int enq, int pe)
         OGL_TRY(gmres_restart(k, s));
     }
     const int it = enq % m;
+    if (k.basis_single) return turn_gmres_f32_basis(k, it, pe);
     double *v_it = d_V.p + (size_t)it * ldv, *nx = d_V.p + (size_t)(it + 1) * ldv;
     const double *w = v_it;  // identity preconditioner: w aliases V_it
     if (k.generic) {
@@ -600,6 +642,43 @@ int ogl_solver::turn_gmres(KrylovRun &k, int enq, int pe)
     return OGL_OK;
 }
 
+// The Arnoldi step of turn_gmres on a basis stored in fp32 (property basisPrecision single, orthoMethod cgs | cgs2): the
+// head stores V_it = fl32((r | the last turn's nx) / its norm) and hands wide(V_it) on; nx stays fp64 in its own buffer.
+int ogl_solver::turn_gmres_f32_basis(KrylovRun &k, int it, int pe)
+{
+    hipStream_t st = k.st;
+    const int n = k.n;
+    const int64_t ld = k.ldvf;
+    DevScalars *s = k.s;
+    FinArgs &fg = k.fg;
+    double *nx = k.nx_buf;
+    float *v_it = d_Vf.p + (size_t)it * ld;
+    const double *w = d_w.p;
+    if (k.generic) {  // (z is free during a turn: the x update alone uses it)
+        launch_gmres_head_f32(st, n, v_it, it == 0 ? d_r.p : nx, k.beta_ptr, nullptr, d_z.p, s);
+        apply_preconditioner(d_z.p, d_w.p, s);
+    } else {
+        launch_gmres_head_f32(st, n, v_it, it == 0 ? d_r.p : nx, k.beta_ptr, precond, d_w.p, s);
+    }
+    if (pe >= 0) OGL_HIP_CHECK(hipEventRecord(prof_ev[2 * pe], st));
+    OGL_TRY(dist_spmv(SPMV_PLAIN, w, nullptr, nx, SpmvDots{}, s));
+    if (pe >= 0) OGL_HIP_CHECK(hipEventRecord(prof_ev[2 * pe + 1], st));
+    fg.turn = it;
+    fg.n_sums = 1;
+    const int nv = it + 1;
+    launch_gmres_multidot(st, n, nx, d_Vf.p, ld, nv, d_gs_part.p, s);
+    launch_gmres_fin_h(st, n, s, d_gs_part.p, nv, d_gs_h.p, k.gm_h(0, it), false);
+    if (k.ortho == 2) {
+        launch_gmres_block_update(st, n, nx, d_Vf.p, ld, nv, d_gs_h.p, nullptr, d_gs_part.p, s);
+        launch_gmres_fin_h(st, n, s, d_gs_part.p, nv, d_gs_h.p, k.gm_h(0, it), true);
+    }
+    launch_gmres_block_update(st, n, nx, d_Vf.p, ld, nv, d_gs_h.p, d_part0.p, nullptr, s);
+    fg.check_after = 1;
+    OGL_TRY(finalize(FIN_GMRES_COL, fg));  // ||nx||, Givens, residual-norm recurrence, the next turn's check
+    fg.check_after = 0;
+    return OGL_OK;
+}
+
 // Property orthoTimedLaunches > 0 (measurements only; after a solve on orthoMethod cgs | cgs2, on its buffers): that many
 // launches of every kernel of the block form at columns it = 0, 15 and 29 (as far as krylovDim goes), timed with HIP
 // events -> orthoMultidotUs_<it>, orthoFinHUs_<it>, orthoUpdateUs_<it> (with the w . w partials), orthoUpdateDotsUs_<it>
@@ -616,15 +695,17 @@ int ogl_solver::time_ortho_kernels(KrylovRun &k)
     for (const int it : {0, 15, 29}) {
         if (it >= k.m) break;
         const int nv = it + 1;
-        double *w = d_V.p + (size_t)nv * k.ldv, *col = k.gm_h(0, it);
+        double *w = k.basis_single ? k.nx_buf : d_V.p + (size_t)nv * k.ldv, *col = k.gm_h(0, it);
         const char *names[4] = {"orthoMultidotUs_", "orthoFinHUs_", "orthoUpdateUs_", "orthoUpdateDotsUs_"};
         for (int which = 0; which < 4; ++which) {
             for (int i = -1; i < timed; ++i) {  // (i == -1: warm-up)
                 if (i == 0) OGL_HIP_CHECK(hipEventRecord(ev[0], st));
-                if (which == 0) launch_gmres_multidot(st, k.n, w, d_V.p, k.ldv, nv, d_gs_part.p, nullptr);
+                double *const pn = which == 2 ? d_part0.p : nullptr, *const pd = which == 3 ? d_gs_part.p : nullptr;
                 if (which == 1) launch_gmres_fin_h(st, k.n, nullptr, d_gs_part.p, nv, d_gs_h.p, col, false);
-                if (which == 2) launch_gmres_block_update(st, k.n, w, d_V.p, k.ldv, nv, d_gs_h.p, d_part0.p, nullptr, nullptr);
-                if (which == 3) launch_gmres_block_update(st, k.n, w, d_V.p, k.ldv, nv, d_gs_h.p, nullptr, d_gs_part.p, nullptr);
+                if (which == 0 && k.basis_single) launch_gmres_multidot(st, k.n, w, d_Vf.p, k.ldvf, nv, d_gs_part.p, nullptr);
+                if (which == 0 && !k.basis_single) launch_gmres_multidot(st, k.n, w, d_V.p, k.ldv, nv, d_gs_part.p, nullptr);
+                if (which >= 2 && k.basis_single) launch_gmres_block_update(st, k.n, w, d_Vf.p, k.ldvf, nv, d_gs_h.p, pn, pd, nullptr);
+                if (which >= 2 && !k.basis_single) launch_gmres_block_update(st, k.n, w, d_V.p, k.ldv, nv, d_gs_h.p, pn, pd, nullptr);
             }
             OGL_HIP_CHECK(hipEventRecord(ev[1], st));
             if (which == 1) OGL_HIP_CHECK(hipMemsetAsync(d_gs_h.p, 0, d_gs_h.n * sizeof(double), st));
@@ -1075,6 +1156,7 @@ int ogl_solver::krylov_loop(KrylovRun &k)
         visit(kh, k.lead);
         visit(kh, k.hz);
         visit(kh, k.hq);
+        visit(kh, k.basis);  // (GKOGMRES turns are not captured today; the basis a captured one would bake in is in the key)
         const uint64_t key = kh.h;
         if (!cg_graph || key != cg_graph_key) {
             if (cg_graph) {
@@ -1244,6 +1326,8 @@ int ogl_solver::apply_resident(ogl_perf *perf)
     OGL_TRY(mixed_requested(&mixed_on));
     int ortho = 0;
     OGL_TRY(ortho_requested(&ortho));
+    bool basis_single = false;
+    OGL_TRY(basis_requested(&basis_single));
     {
         TraceRange trace_pc("init_preconditioner", field);
         OGL_TRY(init_preconditioner());
