@@ -73,8 +73,15 @@ typedef enum {
      * coefficient or inverse diagonal of a level that is finite in fp64 and not in binary32).  smootherSweeps (2; 1 ... 4
      * sweeps before and after the coarse correction on every level) and correctionScale (1.0; the factor on every
      * prolongated correction, finite and inside (0, 2)): any other value is OGL_ERR_INVALID naming keyword and value; both
-     * belong to the solver that applies the hierarchy, like coarseVisits and cyclePrecision.  Read-only after a solve:
-     * mgLevels, mgRows<l>, mgNnz<l>, mgPasses<l>, mgVisits<l>, mgOperatorComplexity, mgCyclePrecisionInUse (0 | 1). */
+     * belong to the solver that applies the hierarchy, like coarseVisits and cyclePrecision.  aggregateCaching (0; a whole
+     * number in [0, 1000000], anything else OGL_ERR_INVALID): after a full generation that many generations of the same
+     * object for the same pattern, aggregation, aggregatePasses, maxLevels and minCoarseRows keep its aggregates and coarse
+     * patterns and recompute only the values (bit for bit what a full generation gives with those aggregates), without a
+     * device-to-host read; 0 is the generation as it always was.  Read-only after a solve:
+     * mgLevels, mgRows<l>, mgNnz<l>, mgPasses<l>, mgVisits<l>, mgOperatorComplexity, mgCyclePrecisionInUse (0 | 1),
+     * mgAggregatesReused (1: the generation behind the hierarchy in use was such a refresh; 0 otherwise, also where a
+     * stored hierarchy was applied as it is), mgAggregateCachingLeft, mgKeptBytes (device bytes of the kept maps) and
+     * mgGenerateHostReads (device-to-host reads of the last generation: 0 for a refresh). */
     OGL_PRECOND_MULTIGRID = 7
 } ogl_precond_kind;
 

@@ -21,7 +21,7 @@ PRECOND_IC, PRECOND_ILU, PRECOND_IRILU = 4, 5, 6
 PRECOND_MULTIGRID = 7
 # keywords of the Multigrid sub-dictionary (Preconditioner.H:297-317): they travel as properties; cycle as a number
 MG_KEYWORDS = ("maxLevels", "minCoarseRows", "coarseSolverIters", "cycle", "zeroGuess", "aggregation", "aggregatePasses",
-               "coarseVisits", "cyclePrecision", "smootherSweeps", "correctionScale")
+               "aggregateCaching", "coarseVisits", "cyclePrecision", "smootherSweeps", "correctionScale")
 MG_CYCLE = {"v": 0, "w": 1, "f": 2}
 MG_AGGREGATION = {"pgm": 0, "hashed": 1}
 MG_CYCLE_PRECISION = {"double": 0, "single": 1}

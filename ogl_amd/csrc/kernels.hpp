@@ -403,13 +403,24 @@ void launch_mg_keys(hipStream_t st, const MgCsr &A, const int32_t *cidx, unsigne
 void launch_mg_head_flag(hipStream_t st, int32_t m, const unsigned long long *keys, int32_t *flag);
 void launch_mg_compact(hipStream_t st, int32_t m, int32_t nc, const unsigned long long *keys, const double *vals,
                        const int32_t *pos, int32_t *row_ptrs, int32_t *cols, double *out);
-// scan and stable radix sorts (hipcub); mg_temp_bytes: scratch that serves all three on a level of n rows, nnz entries
+// keyword aggregateCaching ("kept aggregates").  A full generation keeps of every pass src -- the
+// position in the pass's source matrix of the entry sorted to p, from sorting (key, index) pairs (mg_sort_entry_index of
+// launch_mg_iota's identity) -- and ptr, the start of every coarse entry's run (launch_mg_run_ptr from the head flags and
+// their scan).  launch_mg_regalerkin: vals_out[o] = the sum of vals_in[src[q]], q in [ptr[o], ptr[o + 1]), left to right
+// from the first term -- k_mg_compact's sums without its sort; stream: src and ptr are loaded past the caches.
+void launch_mg_iota(hipStream_t st, int32_t m, int32_t *idx);
+void launch_mg_run_ptr(hipStream_t st, int32_t m, const int32_t *flag, const int32_t *pos, int32_t *ptr);
+void launch_mg_regalerkin(hipStream_t st, int32_t mc, const int32_t *ptr, const int32_t *src, const double *vals_in,
+                          double *vals_out, bool stream);
+// scan and stable radix sorts (hipcub); mg_temp_bytes: scratch that serves all of them on a level of n rows, nnz entries
 size_t mg_temp_bytes(int32_t n, int32_t nnz);
 hipError_t mg_inclusive_sum(hipStream_t st, void *temp, size_t temp_bytes, const int32_t *in, int32_t *out, int32_t n);
 hipError_t mg_sort_rows(hipStream_t st, void *temp, size_t temp_bytes, const int32_t *keys, int32_t *keys_out,
                         const int32_t *rows, int32_t *rows_out, int32_t n);
 hipError_t mg_sort_entries(hipStream_t st, void *temp, size_t temp_bytes, const unsigned long long *keys,
                            unsigned long long *keys_out, const double *vals, double *vals_out, int32_t m);
+hipError_t mg_sort_entry_index(hipStream_t st, void *temp, size_t temp_bytes, const unsigned long long *keys,
+                               unsigned long long *keys_out, const int32_t *idx, int32_t *idx_out, int32_t m);
 // apply.  The launchers of the cycle's kernels are templates over the operand type T, instantiated for double and for float
 // (keyword cyclePrecision single, DESIGN.md section 7b, "the cycle in single precision": the same kernels on binary32
 // operands with binary32 operations; the scalars of the coarsest CG stay doubles, formed from wide sums -- products of the

@@ -221,6 +221,43 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_compact(int m, int nc, const un
     if (p == 0 || (int)(keys[p - 1] >> 32) != I) row_ptrs[I] = o;
 }
 
+// ---- keyword aggregateCaching ("kept aggregates"): what a full generation leaves of a pass besides
+//      its matrix, and the refresh of the pass's values from it ----
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_iota(int m, int32_t *__restrict__ idx)
+{
+    const int p = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (p < m) idx[p] = p;
+}
+
+// ptr[o] = the sorted position at which the run of coarse entry o starts (the inverse of the scan `pos` of the head flags),
+// ptr[mc] = m
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_run_ptr(int m, const int32_t *__restrict__ flag, const int32_t *__restrict__ pos,
+                                                         int32_t *__restrict__ ptr)
+{
+    const int p = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (p >= m) return;
+    if (flag[p]) ptr[pos[p] - 1] = p;
+    if (p == m - 1) ptr[pos[p]] = m;
+}
+
+// One coarse entry per thread: the entries of the pass's source matrix that k_mg_compact summed into it, in that kernel's
+// order and with its rule (the sum starts from the first term, every addition rounds once).  src[q]: position in the
+// source matrix of the entry sorted to q.  STREAM: src and ptr, read once, go past the caches.
+template <bool STREAM>
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_regalerkin(int mc, const int32_t *__restrict__ ptr,
+                                                            const int32_t *__restrict__ src,
+                                                            const double *__restrict__ vals_in, double *__restrict__ vals_out)
+{
+    const int o = blockIdx.x * MG_BLOCK + threadIdx.x;
+    if (o >= mc) return;
+    const auto once = [](const int32_t *p) { return STREAM ? __builtin_nontemporal_load(p) : *p; };
+    int q = once(ptr + o);
+    const int end = once(ptr + o + 1);
+    double acc = vals_in[once(src + q)];
+    for (++q; q < end; ++q) acc = acc + vals_in[once(src + q)];
+    vals_out[o] = acc;
+}
+
 // ------------------------------------------------------------------------------------------
 // apply
 // ------------------------------------------------------------------------------------------
@@ -665,15 +702,32 @@ void launch_mg_compact(hipStream_t st, int32_t m, int32_t nc, const unsigned lon
     MG_LAUNCH(k_mg_compact, m, m, nc, keys, vals, pos, row_ptrs, cols, out);
 }
 
+void launch_mg_iota(hipStream_t st, int32_t m, int32_t *idx) { MG_LAUNCH(k_mg_iota, m, m, idx); }
+void launch_mg_run_ptr(hipStream_t st, int32_t m, const int32_t *flag, const int32_t *pos, int32_t *ptr)
+{
+    MG_LAUNCH(k_mg_run_ptr, m, m, flag, pos, ptr);
+}
+void launch_mg_regalerkin(hipStream_t st, int32_t mc, const int32_t *ptr, const int32_t *src, const double *vals_in,
+                          double *vals_out, bool stream)
+{
+    if (stream)
+        MG_LAUNCH(k_mg_regalerkin<true>, mc, mc, ptr, src, vals_in, vals_out);
+    else
+        MG_LAUNCH(k_mg_regalerkin<false>, mc, mc, ptr, src, vals_in, vals_out);
+}
+
 size_t mg_temp_bytes(int32_t n, int32_t nnz)
 {
-    size_t a = 0, b = 0, c = 0;
+    size_t a = 0, b = 0, c = 0, d = 0;
     (void)hipcub::DeviceScan::InclusiveSum(nullptr, a, (const int32_t *)nullptr, (int32_t *)nullptr, std::max(n, nnz));
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const int32_t *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr,
                                              (int32_t *)nullptr, n);
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, c, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
                                              (const double *)nullptr, (double *)nullptr, nnz);
-    return std::max(a, std::max(b, c)) + 256;
+    // (mg_sort_entry_index: the same keys with the narrower payload)
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, d, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                             (const int32_t *)nullptr, (int32_t *)nullptr, nnz);
+    return std::max(std::max(a, b), std::max(c, d)) + 256;
 }
 hipError_t mg_inclusive_sum(hipStream_t st, void *temp, size_t temp_bytes, const int32_t *in, int32_t *out, int32_t n)
 {
@@ -688,6 +742,11 @@ hipError_t mg_sort_entries(hipStream_t st, void *temp, size_t temp_bytes, const 
                            unsigned long long *keys_out, const double *vals, double *vals_out, int32_t m)
 {
     return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys, keys_out, vals, vals_out, m, 0, 64, st);
+}
+hipError_t mg_sort_entry_index(hipStream_t st, void *temp, size_t temp_bytes, const unsigned long long *keys,
+                               unsigned long long *keys_out, const int32_t *idx, int32_t *idx_out, int32_t m)
+{
+    return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys, keys_out, idx, idx_out, m, 0, 64, st);
 }
 
 // ---- the cycle's kernels: one launcher per kernel template, instantiated for double and float below.  Only the kernel

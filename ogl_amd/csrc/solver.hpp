@@ -39,6 +39,17 @@ struct MgLevel {
     DevBuf<int32_t> row_ptrs, cols;
     DevBuf<int32_t> agg, agg_ptr, agg_rows;    // fine-to-coarse map, members per coarse row (ascending)
     DevBuf<double> part;                       // the per-chunk partials of the coarsest CG's sums (doubles in either precision)
+    // keyword aggregateCaching: per pass that made the next level, what a refresh of its values reads (kernels.hpp,
+    // launch_mg_regalerkin) -- src over the pass's source entries, ptr over its kept_nnz coarse entries (+ 1).  Left by a
+    // full generation that was asked to; they only grow.
+    DevBuf<int32_t> kept_src[MG_MAX_PASSES], kept_ptr[MG_MAX_PASSES];
+    int32_t kept_nnz[MG_MAX_PASSES] = {};
+    size_t kept_bytes() const
+    {
+        size_t bytes = 0;
+        for (int p = 0; p < MG_MAX_PASSES; ++p) bytes += (kept_src[p].cap + kept_ptr[p].cap) * sizeof(int32_t);
+        return bytes;
+    }
     // dbl: what the generation makes.  flt (keyword cyclePrecision single): the binary32 twin -- values
     // and 1 / d rounded from dbl's, on the same index arrays -- and the level's vectors in binary32.  Built by the first
     // apply in single precision of a generated hierarchy (MultigridPart::twin_of); they only grow.
@@ -251,11 +262,36 @@ struct MultigridPart {
     uint64_t generated = 0;
     mutable uint64_t twin_of = 0;
     mutable DevBuf<int32_t> bad;
+    // keyword aggregateCaching: what the aggregates of this object were made for (valid: by a full generation that ran to
+    // its end and kept the levels' maps), and how many generations may still refresh the values under them.  host_reads:
+    // the device-to-host reads of the last generation.
+    struct KeptFor {
+        bool valid = false;
+        uint64_t pat_id = 0;
+        int32_t rows = 0, nnz = 0;
+        bool own = false, hashed = false;
+        int passes = 0, max_levels = 0;
+        double min_coarse = 0.0;
+        bool operator==(const KeptFor &o) const
+        {
+            return valid == o.valid && pat_id == o.pat_id && rows == o.rows && nnz == o.nnz && own == o.own &&
+                   hashed == o.hashed && passes == o.passes && max_levels == o.max_levels && min_coarse == o.min_coarse;
+        }
+    } kept_for;
+    int kept_left = 0, host_reads = 0;
+    size_t kept_bytes() const
+    {
+        size_t bytes = 0;
+        for (const auto &L : levels) bytes += L->kept_bytes();
+        return bytes;
+    }
     void release()
     {
         levels.clear();
         n_levels = 0;
         twin_of = 0;
+        kept_for = KeptFor{};
+        kept_left = 0;
         bad.release();
         scal.release();
         for (DevBuf<int32_t> *b : {&map0, &s, &flag, &incl, &cidx, &rows, &sorted, &left, &pass_agg, &pass_row_ptrs[0],
@@ -544,7 +580,12 @@ struct ogl_solver {
     ogl::DevBuf<double> d_isai_tmp;                     // ISAI(spd): W r before W^T
     ogl::DevBuf<double> d_fac_tmp[3];  // IC / ILU / IRILU: vectors in the caller's order, IRILU's iterates
     // Multigrid: generation of the hierarchy (per-round and per-level sizes are the only host round trips) and one V-cycle
+    // (keyword aggregateCaching: generate_multigrid is a refresh -- the values under the aggregates P holds, no host round
+    //  trip -- where P's record allows it, else the full generation)
     int generate_multigrid(ogl::PrecondData &P);
+    int generate_multigrid_full(ogl::PrecondData &P, const ogl::MultigridPart::KeptFor &asking, int keep);
+    int refresh_multigrid(ogl::PrecondData &P);
+    void publish_multigrid(const ogl::MultigridPart &M);  // the read-only properties that describe a generated hierarchy
     int mg_caller_numbered_level0(ogl::PrecondData &P);  // a renumbered device copy: level 0's pattern in the caller's numbering
     void apply_multigrid(const double *in, double *out, const ogl::DevScalars *gate, double *dot_part);
     // the matrix a level really is: level 0 that keeps none of its own is the system matrix's CSR arrays (double; in single

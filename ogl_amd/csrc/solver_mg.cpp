@@ -24,8 +24,10 @@ int grow(DevBuf<T> &b, size_t count, hipStream_t st)
     return b.alloc(std::max<size_t>(1, count + count / 8), st);
 }
 
-int read_i32(const int32_t *dev, int32_t *host, hipStream_t st)
+// (every device-to-host read of a generation goes through here and is counted: property mgGenerateHostReads)
+int read_i32(MultigridPart &M, const int32_t *dev, int32_t *host, hipStream_t st)
 {
+    ++M.host_reads;
     OGL_HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     OGL_HIP_CHECK(hipStreamSynchronize(st));
     return OGL_OK;
@@ -67,6 +69,9 @@ int ogl_solver::check_multigrid_keywords()
     if (aggregation != 0.0 && aggregation != 1.0)
         return fail(OGL_ERR_INVALID, "preconditioner Multigrid: aggregation %g is neither 0 (pgm) nor 1 (hashed)", aggregation);
     OGL_TRY(check_whole("aggregatePasses", prop("aggregatePasses", 1.0), 1, MG_MAX_PASSES));
+    OGL_TRY(check_whole("aggregateCaching", prop("aggregateCaching", 0.0), 0, 1000000));
+    // (read-only: 1 once this solve's generation turns out to be a refresh -- not where a stored hierarchy is applied as it is)
+    props["mgAggregatesReused"] = 0.0;
     OGL_TRY(check_whole("coarseVisits", prop("coarseVisits", 1.0), 1, MG_MAX_COARSE_VISITS));
     const double precision = prop("cyclePrecision", 0.0);
     if (precision != 0.0 && precision != 1.0)
@@ -90,6 +95,9 @@ int ogl_solver::prepare_multigrid_apply()
     mg_scale = prop("correctionScale", 1.0);
     props["smootherSweeps"] = (double)mg_sweeps;
     props["correctionScale"] = mg_scale;
+    // (read-only, of the hierarchy in use: the maps kept for keyword aggregateCaching and the refreshes it has left)
+    props["mgKeptBytes"] = (double)M.kept_bytes();
+    props["mgAggregateCachingLeft"] = (double)(M.kept_for.valid ? M.kept_left : 0);
     std::vector<double> visits((size_t)M.n_levels, 1.0);
     double total = 0.0;
     for (int l = 0; l < M.n_levels; ++l) {
@@ -232,7 +240,7 @@ int mg_aggregate(hipStream_t st, MultigridPart &M, const MgCsr &A, bool hashed, 
         launch_mg_strongest(st, A, M.diag.p, agg, 0, hashed, M.s.p);
         launch_mg_match(st, n, M.s.p, agg, M.left.p);
         int32_t left = 0;
-        OGL_TRY(read_i32(M.left.p, &left, st));
+        OGL_TRY(read_i32(M, M.left.p, &left, st));
         if (left == 0 || left == prev_left || (double)left < 0.05 * (double)n) break;
         prev_left = left;
     }
@@ -240,24 +248,40 @@ int mg_aggregate(hipStream_t st, MultigridPart &M, const MgCsr &A, bool hashed, 
     launch_mg_join(st, n, M.s.p, agg);
     launch_mg_root_flag(st, n, agg, M.flag.p);
     OGL_HIP_CHECK(mg_inclusive_sum(st, M.temp.p, temp_bytes, M.flag.p, M.incl.p, n));
-    OGL_TRY(read_i32(M.incl.p + (n - 1), nc, st));
+    OGL_TRY(read_i32(M, M.incl.p + (n - 1), nc, st));
     if (*nc < n) launch_mg_coarse_index(st, n, agg, M.incl.p, M.cidx.p, M.rows.p);
     return OGL_OK;
 }
 
 // A_c = the Galerkin product of A under the coarse indices in M.cidx (nc of them), into dst: a stable sort of the entries
-// by (agg(i), agg(j)), one entry per run, summed in sorted order.  *out: A_c.
-int mg_galerkin(hipStream_t st, MultigridPart &M, const MgCsr A, int32_t nc, size_t temp_bytes, const MgCsrBufs &dst, MgCsr *out)
+// by (agg(i), agg(j)), one entry per run, summed in sorted order.  *out: A_c.  keep (keyword aggregateCaching): the level
+// whose pass `pass` this is, to be left the maps of a later refresh -- the sort then carries every entry's position
+// (the same stable sort of the same keys: the same order) and the values are gathered behind it; nullptr: today's launches.
+int mg_galerkin(hipStream_t st, MultigridPart &M, const MgCsr A, int32_t nc, size_t temp_bytes, const MgCsrBufs &dst, MgCsr *out,
+                MgLevel *keep, int pass)
 {
     const int32_t m = A.nnz;
     launch_mg_keys(st, A, M.cidx.p, M.keys.p);
-    OGL_HIP_CHECK(mg_sort_entries(st, M.temp.p, temp_bytes, M.keys.p, M.keys_sorted.p, A.vals, M.vals_sorted.p, m));
+    if (keep) {
+        DevBuf<int32_t> &src = keep->kept_src[pass];
+        OGL_TRY(grow(src, (size_t)m, st));
+        launch_mg_iota(st, m, M.sorted.p);  // (M.sorted: free until the level's member lists)
+        OGL_HIP_CHECK(mg_sort_entry_index(st, M.temp.p, temp_bytes, M.keys.p, M.keys_sorted.p, M.sorted.p, src.p, m));
+        launch_gather_coeffs(st, m, src.p, A.vals, M.vals_sorted.p);
+    } else {
+        OGL_HIP_CHECK(mg_sort_entries(st, M.temp.p, temp_bytes, M.keys.p, M.keys_sorted.p, A.vals, M.vals_sorted.p, m));
+    }
     launch_mg_head_flag(st, m, M.keys_sorted.p, M.flag.p);
     OGL_HIP_CHECK(mg_inclusive_sum(st, M.temp.p, temp_bytes, M.flag.p, M.incl.p, m));
     int32_t mc = 0;
-    OGL_TRY(read_i32(M.incl.p + (m - 1), &mc, st));
+    OGL_TRY(read_i32(M, M.incl.p + (m - 1), &mc, st));
     OGL_TRY(dst.reserve(nc, mc, st));
     launch_mg_compact(st, m, nc, M.keys_sorted.p, M.vals_sorted.p, M.incl.p, dst.row_ptrs.p, dst.cols.p, dst.vals.p);
+    if (keep) {
+        OGL_TRY(grow(keep->kept_ptr[pass], (size_t)mc + 1, st));
+        launch_mg_run_ptr(st, m, M.flag.p, M.incl.p, keep->kept_ptr[pass].p);
+        keep->kept_nnz[pass] = mc;
+    }
     *out = dst.view(nc, mc);
     return OGL_OK;
 }
@@ -305,15 +329,95 @@ int ogl_solver::mg_caller_numbered_level0(PrecondData &P)
     return OGL_OK;
 }
 
+// Keyword aggregateCaching N ("kept aggregates"): an object whose aggregates were made for what this
+// solver asks for has its values refreshed under them, N times between two full generations.  Which object that is stays
+// init_preconditioner's rule.
 int ogl_solver::generate_multigrid(PrecondData &P)
 {
-    hipStream_t st = reg->stream;
-    const int max_levels = (int)prop("maxLevels", 9.0);
-    const int32_t min_coarse = (int32_t)prop("minCoarseRows", 10.0);
-    const bool hashed = prop("aggregation", 0.0) == 1.0;
-    const int max_passes = (int)prop("aggregatePasses", 1.0);
     MultigridPart &M = P.mg;
+    const int keep = (int)prop("aggregateCaching", 0.0);
+    MultigridPart::KeptFor asking;
+    asking.valid = true;
+    asking.pat_id = pat_id;
+    asking.rows = pat.n_rows;
+    asking.nnz = pat.local_nnz;
+    asking.own = pat.renumbered();
+    asking.hashed = prop("aggregation", 0.0) == 1.0;
+    asking.passes = (int)prop("aggregatePasses", 1.0);
+    asking.max_levels = (int)prop("maxLevels", 9.0);
+    asking.min_coarse = prop("minCoarseRows", 10.0);
     M.cg_iters = (int)prop("coarseSolverIters", 4.0);
+    M.host_reads = 0;
+    const bool refresh = keep > 0 && M.kept_left > 0 && M.kept_for == asking;
+    if (refresh) {
+        --M.kept_left;
+        OGL_TRY(refresh_multigrid(P));
+    } else {
+        OGL_TRY(generate_multigrid_full(P, asking, keep));
+    }
+    publish_multigrid(M);
+    props["mgAggregatesReused"] = refresh ? 1.0 : 0.0;
+    props["mgGenerateHostReads"] = (double)M.host_reads;
+    ++M.generated;  // (the levels' binary32 twin, if there is one, is that of the generation before)
+    return OGL_OK;
+}
+
+// Only the values: level 0's through map0 on a renumbered device copy, every pass's from its source's through the kept
+// maps -- the last pass of a level into the kept level, the ones before it into the scratch values the full generation used
+// -- and 1 / d of every level.  Stream-ordered launches, nothing read back.
+int ogl_solver::refresh_multigrid(PrecondData &P)
+{
+    hipStream_t st = reg->stream;
+    MultigridPart &M = P.mg;
+    MgLevel &L0 = *M.levels[0];
+    if (L0.own) {
+        OGL_TRY(mg_caller_numbered_level0(P));
+        launch_gather_coeffs(st, L0.nnz, M.map0.p, csr(false).vals, L0.dbl.vals.p);
+    }
+    // (property mgKeepStream 1, measurements: the maps loaded past the caches)
+    const bool stream = prop("mgKeepStream", 0.0) != 0.0;
+    for (int l = 0; l < M.n_levels; ++l) {
+        MgLevel &L = *M.levels[(size_t)l];
+        const MgCsr A = mg_matrix<double>(L);
+        launch_mg_diag(st, A, M.diag.p, L.dbl.inv_d.p);
+        if (l + 1 == M.n_levels) break;
+        MgLevel &C = *M.levels[(size_t)l + 1];
+        const double *from = A.vals;
+        for (int pass = 0; pass < L.passes; ++pass) {
+            double *to = pass + 1 == L.passes ? C.dbl.vals.p : M.pass_vals[pass & 1].p;
+            launch_mg_regalerkin(st, L.kept_nnz[pass], L.kept_ptr[pass].p, L.kept_src[pass].p, from, to, stream);
+            from = to;
+        }
+    }
+    return OGL_OK;
+}
+
+void ogl_solver::publish_multigrid(const MultigridPart &M)
+{
+    // what the hierarchy looks like (mgLevels counts the matrices, the fine one included)
+    props["mgLevels"] = (double)M.n_levels;
+    double total = 0.0;
+    for (int k = 0; k < M.n_levels; ++k) {
+        props["mgRows" + std::to_string(k)] = (double)M.levels[(size_t)k]->n;
+        props["mgNnz" + std::to_string(k)] = (double)M.levels[(size_t)k]->nnz;
+        total += (double)M.levels[(size_t)k]->nnz;
+        // (passes that made level k + 1; read-only)
+        if (k + 1 < M.n_levels) props["mgPasses" + std::to_string(k)] = (double)M.levels[(size_t)k]->passes;
+    }
+    props["mgOperatorComplexity"] = M.levels[0]->nnz > 0 ? total / (double)M.levels[0]->nnz : 1.0;
+}
+
+// The record is invalid from the start of a full generation to its end, so one that fails half-way leaves nothing to
+// reuse; keep == 0 keeps nothing and leaves it invalid.
+int ogl_solver::generate_multigrid_full(PrecondData &P, const MultigridPart::KeptFor &asking, int keep)
+{
+    hipStream_t st = reg->stream;
+    const int max_levels = asking.max_levels;
+    const int32_t min_coarse = (int32_t)asking.min_coarse;
+    const bool hashed = asking.hashed;
+    const int max_passes = asking.passes;
+    MultigridPart &M = P.mg;
+    M.kept_for.valid = false;
     OGL_TRY(grow(M.scal, 1, st));
     OGL_TRY(grow(M.left, 1, st));
     if (M.levels.empty()) M.levels.emplace_back(new MgLevel);
@@ -376,7 +480,7 @@ int ogl_solver::generate_multigrid(PrecondData &P)
             // (the level's last pass writes the kept level's own arrays; one that may be followed by another, scratch)
             in_place = pass + 1 == max_passes || nc <= min_coarse || nc < 2;
             const MgCsrBufs scratch{M.pass_row_ptrs[pass & 1], M.pass_cols[pass & 1], M.pass_vals[pass & 1]};
-            OGL_TRY(mg_galerkin(st, M, pa, nc, temp_bytes, in_place ? kept : scratch, &pa));
+            OGL_TRY(mg_galerkin(st, M, pa, nc, temp_bytes, in_place ? kept : scratch, &pa, keep > 0 ? &L : nullptr, L.passes));
             ++L.passes;
             if (in_place) break;
         }
@@ -399,18 +503,10 @@ int ogl_solver::generate_multigrid(PrecondData &P)
     OGL_TRY(grow(last.dbl.r, (size_t)last.n + 2, st));
     OGL_TRY(grow(last.dbl.p, (size_t)last.n + 2, st));
     OGL_TRY(grow(last.part, n_chunks(last.n) + 1, st));
-    // what the hierarchy looks like (mgLevels counts the matrices, the fine one included)
-    props["mgLevels"] = (double)M.n_levels;
-    double total = 0.0;
-    for (int k = 0; k < M.n_levels; ++k) {
-        props["mgRows" + std::to_string(k)] = (double)M.levels[(size_t)k]->n;
-        props["mgNnz" + std::to_string(k)] = (double)M.levels[(size_t)k]->nnz;
-        total += (double)M.levels[(size_t)k]->nnz;
-        // (passes that made level k + 1; read-only)
-        if (k + 1 < M.n_levels) props["mgPasses" + std::to_string(k)] = (double)M.levels[(size_t)k]->passes;
+    if (keep > 0) {
+        M.kept_for = asking;
+        M.kept_left = keep;
     }
-    props["mgOperatorComplexity"] = M.levels[0]->nnz > 0 ? total / (double)M.levels[0]->nnz : 1.0;
-    ++M.generated;  // (the levels' binary32 twin, if there is one, is that of the generation before)
     return OGL_OK;
 }
 
