@@ -372,6 +372,20 @@ int ogl_solver_spmv(ogl_solver *s, const ogl_scalar *x, ogl_scalar *y);
  * precision).  Several ranks: the distributed product -- boundary rows continue over their non-local entries in stored
  * order on the neighbours' single-precision x -- and the call is collective: every rank calls it. */
 int ogl_solver_spmv_f32(ogl_solver *s, const float *x, float *y);
+/* The initial guess from the last solutions (keyword / property guessProjection K, 0 .. 8, default 0 = off; DESIGN.md
+ * section 7f).  A field keeps the steps x_final - x0 of its last K solves.  A solve with k >= 1 of them stored replaces
+ * its guess x0 by x0 + sum_j alpha_j d_j -- alpha minimises |b - A (x0 + D alpha)|_2 on this solve's coefficients -- and
+ * then runs exactly as the same solve called with that guess: initial residual, relTol and the counts refer to it.  Every
+ * solver, preconditioner, layout, renumbering and the mixed mode on one rank; several ranks with K > 0 fail the solve
+ * with OGL_ERR_UNSUPPORTED, a K that is no integer in 0 .. 8 with OGL_ERR_INVALID.  The ring survives coefficient changes
+ * and is cleared by a new sparsity pattern, a change of K and a write of 1 to the property guessProjectionReset.  After a
+ * solve the properties guessProjectionOffered (k), guessProjectionKept (columns the projection kept), guessProjectionStored
+ * (vectors in the ring now), guessProjectionNormBefore (sum |b - A x0| at the caller's guess) and guessProjectionLaunches
+ * describe it.
+ * set: replaces the ring by k vectors of n_rows each, contiguous, oldest first, in the caller's cell order (k = 0 clears;
+ * k > K is OGL_ERR_INVALID).  get: the stored vectors into out (room for `capacity` vectors), their number into *k. */
+int ogl_solver_set_guess_history(ogl_solver *s, const ogl_scalar *vectors, int32_t k);
+int ogl_solver_get_guess_history(ogl_solver *s, ogl_scalar *out, int32_t capacity, int32_t *k);
 /* z = M^-1 r with the preconditioner of the last solve (r, z: host vectors of n_rows in the caller's cell order; the
  * local operator only).  OGL_ERR_STATE before the first solve. */
 int ogl_solver_apply_preconditioner(ogl_solver *s, const ogl_scalar *r, ogl_scalar *z);

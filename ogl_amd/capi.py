@@ -100,6 +100,7 @@ EXPORTED_SYMBOLS = [
     "ogl_solver_get_property",
     "ogl_solver_set_property", "ogl_solver_apply_resident", "ogl_solver_upload_solution",
     "ogl_solver_upload_rhs", "ogl_solver_download_solution", "ogl_solver_spmv", "ogl_solver_spmv_f32", "ogl_solver_apply_preconditioner",
+    "ogl_solver_set_guess_history", "ogl_solver_get_guess_history",
     "ogl_solver_mg_level_dims", "ogl_solver_get_mg_level",
     "ogl_solver_time_spmv", "ogl_solver_reduce", "ogl_reduction_chunk_rows",
     "ogl_solver_matrix_dims", "ogl_solver_get_local_matrix", "ogl_solver_get_non_local_matrix",
@@ -396,6 +397,27 @@ class Solver:
         """The keyword basisPrecision ('double' | 'single': how GKOGMRES stores its Krylov basis) for the next solves."""
         self.set_property("basisPrecision", float(BASIS_PRECISION[word]))
         return self
+
+    def set_guess_projection(self, K):
+        """The keyword guessProjection (0 .. 8 stored steps of the last solves the initial guess is projected on; 0: off)
+        for the next solves."""
+        self.set_property("guessProjection", float(K))
+        return self
+
+    def set_guess_history(self, vectors):
+        """Replaces the ring of stored steps: a sequence of vectors in the caller's cell order, oldest first (empty:
+        clears it)."""
+        v = _s(np.asarray(vectors, dtype=np.float64).reshape(len(vectors), -1)) if len(vectors) else np.zeros((0, 0))
+        _check(lib().ogl_solver_set_guess_history(self._h, _ps(v) if v.size else None, C.c_int32(v.shape[0])))
+        return self
+
+    def guess_history(self, capacity=8):
+        """The stored steps, oldest first, in the caller's cell order: an array of shape (k, n_rows)."""
+        n = self.dims().n_rows
+        out = np.zeros((capacity, n), np.float64)
+        k = C.c_int32()
+        _check(lib().ogl_solver_get_guess_history(self._h, _ps(out), C.c_int32(capacity), C.byref(k)))
+        return out[:k.value].copy()
 
     def apply_preconditioner(self, r):
         """z = M^-1 r with the preconditioner of the last solve (caller's cell order, local operator)."""

@@ -416,6 +416,26 @@ extern "C" int ogl_solver_spmv_f32(ogl_solver *s, const float *x, float *y)
     OGL_GUARD_END
 }
 
+extern "C" int ogl_solver_set_guess_history(ogl_solver *s, const ogl_scalar *vectors, int32_t k)
+{
+    OGL_GUARD_BEGIN
+    if (!s) return fail(OGL_ERR_INVALID, "NULL solver");
+    if (!s->have_pattern) return fail(OGL_ERR_STATE, "guess history before set_matrix");
+    OGL_HIP_CHECK(hipSetDevice(s->reg->device));
+    return s->set_guess_history(vectors, k);
+    OGL_GUARD_END
+}
+
+extern "C" int ogl_solver_get_guess_history(ogl_solver *s, ogl_scalar *out, int32_t capacity, int32_t *k)
+{
+    OGL_GUARD_BEGIN
+    if (!s || !k || (!out && capacity > 0)) return fail(OGL_ERR_INVALID, "NULL argument");
+    if (!s->have_pattern) return fail(OGL_ERR_STATE, "guess history before set_matrix");
+    OGL_HIP_CHECK(hipSetDevice(s->reg->device));
+    return s->get_guess_history(out, capacity, k);
+    OGL_GUARD_END
+}
+
 extern "C" int ogl_solver_apply_preconditioner(ogl_solver *s, const ogl_scalar *r, ogl_scalar *z)
 {
     OGL_GUARD_BEGIN

@@ -665,6 +665,17 @@ void launch_gmres_update_x(hipStream_t st, int32_t n, const float *V, int64_t ld
 // times inv_diag), in place of launch_gmres_scale / launch_gmres_scale_mul
 void launch_gmres_head_f32(hipStream_t st, int32_t n, float *v_out, const double *in, const double *denom,
                            const double *inv_diag, double *w, const DevScalars *gate);
+// The initial guess from the stored steps of the last solves (kernels_proj.hip; keyword guessProjection, DESIGN.md section
+// 7f).  W: w_j = A d_j at W + j * ld, j < k <= PROJ_MAX.  gram: one pass over r0 and W, the partials of the proj_n_sums(k)
+// sums S0 = sum |r0| | g_j = w_j . r0 | G_ij = w_i . w_j (i >= j, row by row), row s of the partial array at part + s *
+// n_chunks(n); launch_gmres_fin_h reduces them.  solve (one thread): Cholesky with dropping of G, h[j] = -alpha_j for
+// launch_gmres_block_update, rec = {S0, columns kept, k}.  delta: d = x - x0, one rounded difference per row.
+constexpr int PROJ_MAX = 8;
+int proj_n_sums(int k);
+void launch_proj_gram(hipStream_t st, int32_t n, const double *r0, const double *W, int64_t ld, int32_t k, double *part,
+                      const DevScalars *gate);
+void launch_proj_solve(hipStream_t st, int32_t k, const double *sums, double *h, double *rec, const DevScalars *gate);
+void launch_proj_delta(hipStream_t st, int32_t n, const double *x, const double *x0, double *d, const DevScalars *gate);
 // The Krylov basis a GKOGMRES solve works on: one of the two is set (launch_key.hpp hashes it)
 struct GmresBasis {
     const double *V = nullptr;  // basisPrecision double

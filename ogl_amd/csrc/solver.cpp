@@ -250,6 +250,7 @@ ogl_solver::~ogl_solver()
     ledger::dev_free(held_z_box);
     ledger::dev_free(held_q_heads);
     mixed.release();
+    proj.release();
     for (auto &e : poll_ev)
         if (e) ev_destroy(e);
     for (auto &e : prof_ev)

@@ -398,6 +398,37 @@ struct MixedPart {
     }
 };
 
+// The initial guess from the last solutions (keyword guessProjection K; solver_proj.cpp): the ring
+// of stored steps and W = A D, K vectors of leading dimension ld each, the partials and the small arrays of the pre-step.
+// Sized at the first solve with K > 0 and kept.  The stored vectors, oldest first: slots first, first + 1, .. (mod K).
+struct ProjPart {
+    DevBuf<double> ring, W, part, small;
+    int K = 0, count = 0, first = 0;
+    int64_t ld = 0;
+    uint64_t pat_id = 0;
+    // the solve under way: vectors offered, launches of its pre-step, whether a step may be stored after it
+    int offered = 0, launches = 0;
+    bool active = false;
+    hipEvent_t ev[5] = {};  // property guessProjectionTimed: products | Gram pass | small solve | update
+    bool timed = false;
+    double *slot(int j) const { return ring.p + (size_t)((first + j) % K) * (size_t)ld; }  // stored vector j, oldest first
+    double *sums() const { return small.p; }
+    double *sums_copy() const { return small.p + 64; }
+    double *h() const { return small.p + 128; }
+    double *rec() const { return small.p + 144; }
+    static constexpr size_t SMALL_LEN = 160;
+    void clear() { count = first = 0; }
+    void release()
+    {
+        for (DevBuf<double> *b : {&ring, &W, &part, &small}) b->release();
+        for (auto &e : ev)
+            if (e) ev_destroy(e);
+        for (auto &e : ev) e = nullptr;
+        K = 0;
+        clear();
+    }
+};
+
 }  // namespace ogl
 
 struct ogl_solver;
@@ -710,6 +741,15 @@ struct ogl_solver {
     // property basisPrecision (0 double | 1 single; GKOGMRES only, ignored elsewhere): its validation and the refusal with mgs
     int basis_requested(bool *single);
     int spmv_f32(const float *x, float *y);
+    // keyword guessProjection (solver_proj.cpp): x0 + sum_j alpha_j d_j over the stored steps of the
+    // last solves in place of x0, then the same solve
+    ogl::ProjPart proj;
+    int proj_requested(int *K);   // the keyword's validation and the refusal on several ranks
+    int proj_sync(int K);         // what clears the ring (guessProjectionReset, a change of K or of the pattern); the buffers
+    int proj_pre_step(int K);     // before anything of the solve: x0 kept, the projection applied to d_x
+    int proj_post_step(int rc, const ogl_perf *perf);  // after it: the step stored, the properties
+    int set_guess_history(const double *vectors, int32_t k);
+    int get_guess_history(double *out, int32_t capacity, int32_t *k);
     // run_krylov = plan -> prepare -> loop -> finish; one function per solver x turn shape (solver.cpp)
     struct KrylovRun;
     int krylov_plan(KrylovRun &k);

@@ -1328,20 +1328,29 @@ int ogl_solver::apply_resident(ogl_perf *perf)
     OGL_TRY(ortho_requested(&ortho));
     bool basis_single = false;
     OGL_TRY(basis_requested(&basis_single));
+    int proj_k = 0;
+    OGL_TRY(proj_requested(&proj_k));
+    // (keyword guessProjection: d_x becomes the projected guess, and from here on the solve is the one called with it)
+    OGL_TRY(proj_pre_step(proj_k));
     {
         TraceRange trace_pc("init_preconditioner", field);
         OGL_TRY(init_preconditioner());
     }
+    int rc = OGL_OK;
     switch (cfg.solver) {
     case OGL_SOLVER_CG:
-        return run_cg(perf);
+        rc = run_cg(perf);
+        break;
     case OGL_SOLVER_BICGSTAB:
-        return run_bicgstab(perf);
+        rc = run_bicgstab(perf);
+        break;
     case OGL_SOLVER_GMRES:
-        return run_krylov(perf);
+        rc = run_krylov(perf);
+        break;
     default:
         return fail(OGL_ERR_UNSUPPORTED, "solver kind %d is not built", cfg.solver);
     }
+    return proj_post_step(rc, perf);
 }
 
 // lduLduBase::solve_multi_gpu_impl (lduLduBase.H:189-308)
