@@ -382,6 +382,16 @@ int ogl_solver_spmv_f32(ogl_solver *s, const float *x, float *y);
  * solve the properties guessProjectionOffered (k), guessProjectionKept (columns the projection kept), guessProjectionStored
  * (vectors in the ring now), guessProjectionNormBefore (sum |b - A x0| at the caller's guess) and guessProjectionLaunches
  * describe it.
+ * Property guessProjectionCredit (0 | 1, default 0; anything else OGL_ERR_INVALID): with 1, K >= 1 and a column kept, the
+ * criterion's initial residual is sum |b - A x0| at the CALLER's guess over the solve's own norm factor (one division), in
+ * every comparison res < relTol * initial and in ogl_perf::initial_residual -- relTol then credits the projection, and a
+ * projection that already meets it ends the solve at its first check (n_iterations 1).  Everything else is the solve from
+ * the projected guess; guessProjectionCreditInUse (0 | 1) says whether the credit was applied.  With mixedPrecision the
+ * solve fails with OGL_ERR_UNSUPPORTED.
+ * Property guessProjectionProducts (0 separate | 1 onePass, default 0; anything else OGL_ERR_INVALID): with 1 and the
+ * whole-matrix half storage as the in-loop layout (symmetricHalf 1) the pre-step forms b - A x0 and every A d_j in one
+ * pass over the matrix, the same bits; on any other layout the separate products run.  guessProjectionOnePassInUse (0 | 1)
+ * says which ran; guessProjectionLaunches is then 5 (6 on a ring that has wrapped) instead of k + 5.
  * set: replaces the ring by k vectors of n_rows each, contiguous, oldest first, in the caller's cell order (k = 0 clears;
  * k > K is OGL_ERR_INVALID).  get: the stored vectors into out (room for `capacity` vectors), their number into *k. */
 int ogl_solver_set_guess_history(ogl_solver *s, const ogl_scalar *vectors, int32_t k);

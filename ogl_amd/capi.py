@@ -30,6 +30,8 @@ _MG_WORDS = {"cycle": MG_CYCLE, "aggregation": MG_AGGREGATION, "cyclePrecision":
 ORTHO_METHOD = {"mgs": 0, "cgs": 1, "cgs2": 2}
 # keyword basisPrecision of GKOGMRES: likewise
 BASIS_PRECISION = {"double": 0, "single": 1}
+# keyword guessProjectionProducts: likewise
+GUESS_PROJECTION_PRODUCTS = {"separate": 0, "onePass": 1}
 FORMAT_COO, FORMAT_CSR, FORMAT_ELL = 0, 1, 2
 RENUMBER_OFF, RENUMBER_ON, RENUMBER_AUTO = 0, 1, 2
 IFACE_PROCESSOR, IFACE_CYCLIC = 0, 1
@@ -402,6 +404,18 @@ class Solver:
         """The keyword guessProjection (0 .. 8 stored steps of the last solves the initial guess is projected on; 0: off)
         for the next solves."""
         self.set_property("guessProjection", float(K))
+        return self
+
+    def set_guess_projection_credit(self, on):
+        """The keyword guessProjectionCredit (0 | 1; default 0) for the next solves: with 1 and guessProjection K >= 1 the
+        criterion's initial residual is counted from the caller's guess, so that relTol credits the projection."""
+        self.set_property("guessProjectionCredit", float(on))
+        return self
+
+    def set_guess_projection_products(self, word):
+        """The keyword guessProjectionProducts ('separate' | 'onePass'; default separate) for the next solves: how the
+        pre-step forms b - A x0 and A d_j -- k + 1 products, or one pass over the whole-matrix half storage."""
+        self.set_property("guessProjectionProducts", float(GUESS_PROJECTION_PRODUCTS[word]))
         return self
 
     def set_guess_history(self, vectors):

@@ -672,6 +672,11 @@ struct Verdict {
 };
 // `norm` is sum|r| over all ranks; `history`: null unless the caller is the workgroup that exports -- the store
 // history[iter] = res is the only memory access in here.
+// `init_res`: the scalars' init_res as the caller found it.  From the first check on that is the criterion's initial
+// normalised residual.  AT the first check (iter == 0) it is the one input the keyword guessProjectionCredit adds: sum|r| at
+// the guess the caller handed in, put there by k_proj_credit after the scalars' reset, which takes
+// the place of `norm` in the initial residual -- and in nothing else; 0, what the reset leaves, means "as before".  Every
+// caller already hands the field in, so the credit costs no kernel a load or a register it did not have.
 __device__ __forceinline__ Verdict criterion_verdict(const CritVals &c, int iter, int n_evals, double init_res,
                                                      double norm_factor, double norm, double *history)
 {
@@ -687,7 +692,7 @@ __device__ __forceinline__ Verdict criterion_verdict(const CritVals &c, int iter
     v.evaluated = true;
     v.n_evals = n_evals + 1;
     double res = norm;
-    if (iter == 0) v.init_res = res / norm_factor;                  // :102-111 (norm_factor set before)
+    if (iter == 0) v.init_res = (init_res != 0.0 ? init_res : res) / norm_factor;  // :102-111 (norm_factor set before)
     res /= norm_factor;                                             // :113
     if (c.export_res && history) history[iter] = res;               // :115-117
     v.res = res;                                                    // :119

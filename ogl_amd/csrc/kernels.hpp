@@ -676,6 +676,19 @@ void launch_proj_gram(hipStream_t st, int32_t n, const double *r0, const double 
                       const DevScalars *gate);
 void launch_proj_solve(hipStream_t st, int32_t k, const double *sums, double *h, double *rec, const DevScalars *gate);
 void launch_proj_delta(hipStream_t st, int32_t n, const double *x, const double *x0, double *d, const DevScalars *gate);
+// keyword guessProjectionProducts onePass (kernels_spmv_sym.hip): r0 = b - A x0 and W + j * ld = A in[j], j < k, in one pass
+// over the half storage; the bits of launch_spmv_sym's k + 1 products
+struct ProjProducts {
+    const double *in[PROJ_MAX];
+    double *W;
+    long ld;
+    int k;
+};
+void launch_proj_products_sym(hipStream_t st, const DevSym &A, const double *x0, const double *b, double *r0,
+                              const ProjProducts &v);
+// keyword guessProjectionCredit: s->init_res = rec[0] (S0) when a column was kept and S0 is finite and > 0, else 0 -- after
+// launch_reset_scalars and before the solve's first check (criterion_verdict, device_common.hpp)
+void launch_proj_credit(hipStream_t st, const double *rec, DevScalars *s);
 // The Krylov basis a GKOGMRES solve works on: one of the two is set (launch_key.hpp hashes it)
 struct GmresBasis {
     const double *V = nullptr;  // basisPrecision double

@@ -169,9 +169,25 @@ __global__ __launch_bounds__(BLOCK) void k_proj_delta(int n, const double *__res
     st2(d, rp, t);
 }
 
+// Keyword guessProjectionCredit: S0 = sum |b - A x0| of the pre-step (rec[0]) into the criterion's state, between the
+// scalars' reset and the solve's first check, where criterion_verdict reads it as the numerator of the initial residual.
+// Nothing comes back to the host.  No column kept: x is still the caller's guess and the first norm of the solve is that
+// residual's own, so nothing is credited -- the plain solve; the same for an S0 that is not finite or not > 0.
+__global__ __launch_bounds__(WAVE) void k_proj_credit(const double *__restrict__ rec, DevScalars *s)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double s0 = rec[0];
+    s->init_res = (rec[1] >= 1.0 && s0 > 0.0 && isfinite(s0)) ? s0 : 0.0;
+}
+
 }  // namespace
 
 int proj_n_sums(int k) { return 1 + k + k * (k + 1) / 2; }
+
+void launch_proj_credit(hipStream_t st, const double *rec, DevScalars *s)
+{
+    hipLaunchKernelGGL(k_proj_credit, dim3(1), dim3(WAVE), 0, st, rec, s);
+}
 
 void launch_proj_gram(hipStream_t st, int32_t n, const double *r0, const double *W, int64_t ld, int32_t k, double *part,
                       const DevScalars *gate)

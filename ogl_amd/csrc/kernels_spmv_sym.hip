@@ -52,6 +52,55 @@ __global__ __launch_bounds__(BLOCK) void k_spmv_sym(int n_rows, int n_chunks, Sy
     }
 }
 
+// The matrix work of the guess projection's pre-step (keyword guessProjectionProducts onePass; solver_proj.cpp, DESIGN.md
+// section 7f) in one pass over the planes: r0 = b - A x0 and w_j = A d_j, j < k <= PROJ_MAX.  A thread loads its mask, its
+// own planes and the twins of its lower entries once and keeps them; every vector then costs its gathers and one store --
+// 33 N + 8 N (b) + 16 N (k + 1) bytes instead of 49 N (k + 1) + 8 N.  Gathers and sums are the functions k_spmv_sym runs
+// (sym_walk.hpp), so r0 and every w_j have the bits of the k + 1 separate products.  The vectors go in batches of
+// PROJ_BATCH: the gathers of a batch are in flight together, and the registers are the planes' 2 ND pairs plus the
+// batch's (2 ND + 1) pairs whatever k is.  Under STREAM the once-read planes still pass the caches, once.
+constexpr int PROJ_BATCH = 2;
+template <int ND, bool FAST, bool STREAM>
+__global__ __launch_bounds__(BLOCK) void k_proj_products_sym(int n_rows, int n_chunks, SymOffsets off,
+                                                             const uint8_t *__restrict__ mask,
+                                                             const double *__restrict__ planes,
+                                                             const double *__restrict__ x0, const double *__restrict__ b,
+                                                             double *__restrict__ r0, ProjProducts v,
+                                                             const int *__restrict__ block_order)
+{
+    const int chunk = block_order ? block_order[blockIdx.x] : xcd_chunk(blockIdx.x);
+    if (chunk < 0 || chunk >= n_chunks) return;
+    const RowPair rp = my_rows(chunk, n_rows);
+    const unsigned mm = *reinterpret_cast<const unsigned short *>(mask + rp.row);
+    const unsigned m0 = mm & 0xffu, m1 = mm >> 8;
+    double2 up[ND], lo[ND];
+    sym_own_planes<double, ND, FAST, STREAM>(up, chunk, planes);
+    {
+        double2 xl[ND], xu[ND];
+        const double2 acc = ld2(b, rp), xd = ld2(x0, rp);
+        sym_twin_planes<double, ND, FAST, STREAM>(lo, up, rp.row, off, planes);
+        sym_gather<double, ND, FAST>(xl, xu, xd, rp.row, n_rows, off, x0);
+        st2(r0, rp, sym_sum<SPMV_RESIDUAL, double, ND>(m0, m1, up, lo, xd, xl, xu, acc));
+    }
+#pragma unroll 1
+    for (int j0 = 0; j0 < v.k; j0 += PROJ_BATCH) {
+        double2 dl[PROJ_BATCH][ND], du[PROJ_BATCH][ND], dd[PROJ_BATCH];
+#pragma unroll
+        for (int e = 0; e < PROJ_BATCH; ++e) {  // (past the last vector: the last one once more, loaded and not used)
+            const double *__restrict__ d = v.in[min(j0 + e, v.k - 1)];
+            dd[e] = ld2(d, rp);
+            sym_gather<double, ND, FAST>(dl[e], du[e], dd[e], rp.row, n_rows, off, d);
+        }
+#pragma unroll
+        for (int e = 0; e < PROJ_BATCH; ++e) {
+            if (j0 + e >= v.k) break;
+            double2 zero;
+            zero.x = zero.y = 0.0;
+            st2(v.W + (size_t)(j0 + e) * v.ld, rp, sym_sum<SPMV_PLAIN, double, ND>(m0, m1, up, lo, dd[e], dl[e], du[e], zero));
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Small systems on half storage, two launches per GKOCG turn: step_1x_fin and the SpMV in one kernel.  The SpMV
 // needs p_new = z + (rho/rho') p at the columns of its rows, which other workgroups own -- but p_new is an
@@ -435,6 +484,18 @@ void launch_spmv_sym(hipStream_t st, const DevSym &A, int mode, const double *x,
             go(Plain{}, std::integral_constant<int, 1>{});
         else
             go(Plain{}, std::integral_constant<int, 0>{});
+    });
+}
+
+void launch_proj_products_sym(hipStream_t st, const DevSym &A, const double *x0, const double *b, double *r0,
+                              const ProjProducts &v)
+{
+    if (A.n_rows == 0) return;
+    const int nc = (int)n_chunks(A.n_rows);
+    const dim3 grid(A.block_order ? A.n_blocks : xcd_grid(nc)), block(BLOCK);
+    sym_dispatch(A, [&](const SymOffsets &off, auto nd, auto fast, auto stream) {
+        hipLaunchKernelGGL((k_proj_products_sym<decltype(nd)::value, decltype(fast)::value, decltype(stream)::value>), grid,
+                           block, 0, st, A.n_rows, nc, off, A.mask, A.planes, x0, b, r0, v, A.block_order);
     });
 }
 

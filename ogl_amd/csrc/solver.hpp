@@ -409,6 +409,8 @@ struct ProjPart {
     // the solve under way: vectors offered, launches of its pre-step, whether a step may be stored after it
     int offered = 0, launches = 0;
     bool active = false;
+    bool credit = false;    // keyword guessProjectionCredit 1 on this solve (K > 0)
+    bool one_pass = false;  // keyword guessProjectionProducts onePass, and this solve's products ran that way
     hipEvent_t ev[5] = {};  // property guessProjectionTimed: products | Gram pass | small solve | update
     bool timed = false;
     double *slot(int j) const { return ring.p + (size_t)((first + j) % K) * (size_t)ld; }  // stored vector j, oldest first
@@ -746,7 +748,10 @@ struct ogl_solver {
     ogl::ProjPart proj;
     int proj_requested(int *K);   // the keyword's validation and the refusal on several ranks
     int proj_sync(int K);         // what clears the ring (guessProjectionReset, a change of K or of the pattern); the buffers
-    int proj_pre_step(int K);     // before anything of the solve: x0 kept, the projection applied to d_x
+    int proj_credit_requested(int K, bool mixed_on, bool *credit);  // keyword guessProjectionCredit: validation, the refusal
+    int proj_products_requested(bool *one_pass);                    // keyword guessProjectionProducts: validation
+    int proj_pre_step(int K, bool credit, bool one_pass);  // before anything of the solve: x0 kept, the projection applied to d_x
+    void proj_credit(hipStream_t st, ogl::DevScalars *s);  // after the scalars' reset: S0 into the criterion's state
     int proj_post_step(int rc, const ogl_perf *perf);  // after it: the step stored, the properties
     int set_guess_history(const double *vectors, int32_t k);
     int get_guess_history(double *out, int32_t capacity, int32_t *k);

@@ -441,6 +441,7 @@ int ogl_solver::krylov_prepare(KrylovRun &k)
 
     k.t_start = now_ms();
     launch_reset_scalars(st, s, crit);
+    proj_credit(st, s);  // (keyword guessProjectionCredit: what the first check's initial residual is counted from)
 
     FinArgs fa;
     // norm factor, part 1: xbar = mean(x) (StoppingCriterion.C:17-19)
@@ -1331,7 +1332,11 @@ int ogl_solver::apply_resident(ogl_perf *perf)
     int proj_k = 0;
     OGL_TRY(proj_requested(&proj_k));
     // (keyword guessProjection: d_x becomes the projected guess, and from here on the solve is the one called with it)
-    OGL_TRY(proj_pre_step(proj_k));
+    bool proj_cr = false;
+    OGL_TRY(proj_credit_requested(proj_k, mixed_on, &proj_cr));
+    bool proj_one_pass = false;
+    OGL_TRY(proj_products_requested(&proj_one_pass));
+    OGL_TRY(proj_pre_step(proj_k, proj_cr, proj_one_pass));
     {
         TraceRange trace_pc("init_preconditioner", field);
         OGL_TRY(init_preconditioner());

@@ -24,6 +24,39 @@ int ogl_solver::proj_requested(int *K)
     return OGL_OK;
 }
 
+// Property guessProjectionCredit: 0 (the default) | 1.  With 1 the criterion's initial residual is counted from the guess
+// the caller handed in, S0 / norm_factor, so that relTol credits the projection instead of charging
+// for it.  The mixed mode keeps a copy of the criterion of its own, which does not take the credit: refused, not run
+// without it in silence.  With K = 0 the keyword has nothing to act on.
+int ogl_solver::proj_credit_requested(int K, bool mixed_on, bool *credit)
+{
+    *credit = false;
+    const double v = prop("guessProjectionCredit", 0.0);
+    if (v != 0.0 && v != 1.0) return fail(OGL_ERR_INVALID, "guessProjectionCredit %g is not 0 or 1", v);
+    if (v == 1.0 && K > 0 && mixed_on)
+        return fail(OGL_ERR_UNSUPPORTED,
+                    "guessProjectionCredit 1 is not built for mixedPrecision: its outer criterion does not take the credit");
+    *credit = v == 1.0 && K > 0;
+    return OGL_OK;
+}
+
+// Property guessProjectionProducts: 0 (separate, the default: k + 1 launches of the in-loop product) | 1 (onePass)
+int ogl_solver::proj_products_requested(bool *one_pass)
+{
+    const double v = prop("guessProjectionProducts", 0.0);
+    *one_pass = v == 1.0;
+    if (v != 0.0 && v != 1.0)
+        return fail(OGL_ERR_INVALID, "guessProjectionProducts %g is not 0 (separate) or 1 (onePass)", v);
+    return OGL_OK;
+}
+
+// Called by the solve between the reset of its scalars and its first check: S0 of the pre-step into the criterion's state,
+// device to device.  The launch is the same for every solve of the field (rec and the scalar block do not move).
+void ogl_solver::proj_credit(hipStream_t st, ogl::DevScalars *s)
+{
+    if (proj.active && proj.credit && proj.offered >= 1) launch_proj_credit(st, proj.rec(), s);
+}
+
 // The ring is cleared by a write of 1 to guessProjectionReset, by a change of K and by a new sparsity pattern; a change of
 // coefficients keeps it (W is formed anew in every solve).  With K > 0 the buffers are sized here, once.
 int ogl_solver::proj_sync(int K)
@@ -46,9 +79,11 @@ int ogl_solver::proj_sync(int K)
     return OGL_OK;
 }
 
-int ogl_solver::proj_pre_step(int K)
+int ogl_solver::proj_pre_step(int K, bool credit, bool one_pass)
 {
     proj.active = false;
+    proj.credit = credit;
+    proj.one_pass = false;
     if (K == 0 && proj.K == 0) return OGL_OK;  // (never asked for: nothing to clear, nothing to publish)
     OGL_TRY(proj_sync(K));
     const int n = pat.n_rows;
@@ -72,10 +107,23 @@ int ogl_solver::proj_pre_step(int K)
     }
     OGL_TRY(mark(0));
     // r0 = b - A x0 with the prologue's residual product; w_j = A d_j with the in-loop product, oldest first
-    OGL_TRY(dist_spmv(SPMV_RESIDUAL, d_x.p, d_b.p, d_r.p, SpmvDots{}, nullptr));
-    for (int j = 0; j < k; ++j)
-        OGL_TRY(dist_spmv(SPMV_PLAIN, proj.slot(j), nullptr, proj.W.p + (size_t)j * (size_t)proj.ld, SpmvDots{}, nullptr));
-    proj.launches += 1 + k;
+    // (keyword guessProjectionProducts onePass, whole-matrix half storage only: all k + 1 products in one pass of the planes,
+    //  the same bits -- k_proj_products_sym; on every other in-loop layout the keyword is accepted and these launches run)
+    proj.one_pass = one_pass && spmv_layout == SpmvLayout::Sym && pat.non_local_nnz == 0;
+    if (proj.one_pass) {
+        ProjProducts v{};
+        for (int j = 0; j < k; ++j) v.in[j] = proj.slot(j);
+        v.W = proj.W.p;
+        v.ld = (long)proj.ld;
+        v.k = k;
+        launch_proj_products_sym(st, sym(), d_x.p, d_b.p, d_r.p, v);
+        proj.launches += 1;
+    } else {
+        OGL_TRY(dist_spmv(SPMV_RESIDUAL, d_x.p, d_b.p, d_r.p, SpmvDots{}, nullptr));
+        for (int j = 0; j < k; ++j)
+            OGL_TRY(dist_spmv(SPMV_PLAIN, proj.slot(j), nullptr, proj.W.p + (size_t)j * (size_t)proj.ld, SpmvDots{}, nullptr));
+        proj.launches += 1 + k;
+    }
     OGL_TRY(mark(1));
     launch_proj_gram(st, n, d_r.p, proj.W.p, proj.ld, k, proj.part.p, nullptr);
     launch_gmres_fin_h(st, n, nullptr, proj.part.p, proj_n_sums(k), proj.sums(), proj.sums_copy(), false);
@@ -128,6 +176,10 @@ int ogl_solver::proj_post_step(int rc, const ogl_perf *perf)
     props["guessProjectionStored"] = (double)proj.count;
     props["guessProjectionNormBefore"] = rec[0];
     props["guessProjectionLaunches"] = (double)proj.launches;
+    props["guessProjectionOnePassInUse"] = (proj.offered > 0 && proj.one_pass) ? 1.0 : 0.0;
+    // (what k_proj_credit decided, from the same three numbers)
+    props["guessProjectionCreditInUse"] =
+        (proj.credit && proj.offered > 0 && kept >= 1 && rec[0] > 0.0 && std::isfinite(rec[0])) ? 1.0 : 0.0;
     if (proj.timed) {
         static const char *const names[4] = {"guessProjectionProductsMs", "guessProjectionGramMs", "guessProjectionSolveMs",
                                              "guessProjectionUpdateMs"};
