@@ -396,7 +396,18 @@ int ogl_solver_spmv_f32(ogl_solver *s, const float *x, float *y);
  * k > K is OGL_ERR_INVALID).  get: the stored vectors into out (room for `capacity` vectors), their number into *k. */
 int ogl_solver_set_guess_history(ogl_solver *s, const ogl_scalar *vectors, int32_t k);
 int ogl_solver_get_guess_history(ogl_solver *s, ogl_scalar *out, int32_t capacity, int32_t *k);
-/* z = M^-1 r with the preconditioner of the last solve (r, z: host vectors of n_rows in the caller's cell order; the
+/* Preconditioners IC / ILU / IRILU without dependent launches; both properties belong to the solve
+ * that generates the preconditioner, a stored object of the registry-wide cache is applied the way it was generated.
+ * Property triangularSolves (0 exact | 1 isai, default 0; anything else OGL_ERR_INVALID): with 1, IC and ILU apply
+ * z = W_U (W_L r) -- W_L a sparse approximate inverse of L on the sparsity_power-th power of the factor's lower-triangle
+ * pattern, W_U of U on its transpose -- in two product launches instead of the level-scheduled exact solves.  A row of W_L
+ * wider than 32 entries and IRILU with 1 are OGL_ERR_UNSUPPORTED; every other preconditioner ignores the property.  Memory:
+ * W_L + W_U, about one more copy of the matrix at sparsity_power 1.
+ * Property factorSweeps (integer 0 .. 10, default 0; anything else OGL_ERR_INVALID): N >= 1 forms the factor by N
+ * synchronous fixed-point sweeps, one launch each, instead of level by level; a breakdown is judged after the last sweep.
+ * After a solve: triangularSolvesInUse (0 | 1), triangularWEntries (entries of W_L), factorSweepsInUse (N) and
+ * iluLaunchesPerApply (2 under isai, 4 on a renumbered device copy) describe the object in use.
+ * z = M^-1 r with the preconditioner of the last solve (r, z: host vectors of n_rows in the caller's cell order; the
  * local operator only).  OGL_ERR_STATE before the first solve. */
 int ogl_solver_apply_preconditioner(ogl_solver *s, const ogl_scalar *r, ogl_scalar *z);
 /* preconditioner Multigrid: the hierarchy of the last solve, level 0 = the local system matrix (property mgLevels = the

@@ -32,6 +32,8 @@ ORTHO_METHOD = {"mgs": 0, "cgs": 1, "cgs2": 2}
 BASIS_PRECISION = {"double": 0, "single": 1}
 # keyword guessProjectionProducts: likewise
 GUESS_PROJECTION_PRODUCTS = {"separate": 0, "onePass": 1}
+# keyword triangularSolves of IC / ILU: likewise
+TRIANGULAR_SOLVES = {"exact": 0, "isai": 1}
 FORMAT_COO, FORMAT_CSR, FORMAT_ELL = 0, 1, 2
 RENUMBER_OFF, RENUMBER_ON, RENUMBER_AUTO = 0, 1, 2
 IFACE_PROCESSOR, IFACE_CYCLIC = 0, 1
@@ -398,6 +400,19 @@ class Solver:
     def set_basis_precision(self, word):
         """The keyword basisPrecision ('double' | 'single': how GKOGMRES stores its Krylov basis) for the next solves."""
         self.set_property("basisPrecision", float(BASIS_PRECISION[word]))
+        return self
+
+    def set_triangular_solves(self, word):
+        """The keyword triangularSolves ('exact' | 'isai'; default exact) of IC / ILU for the next solves: the triangular
+        solves level by level, or as two products with sparse approximate inverses on the sparsityPower-th power of the
+        factor's pattern."""
+        self.set_property("triangularSolves", float(TRIANGULAR_SOLVES[word]))
+        return self
+
+    def set_factor_sweeps(self, N):
+        """The keyword factorSweeps (0 .. 10; default 0) of IC / ILU / IRILU for the next solves: 0 the exact level-scheduled
+        factorisation, N >= 1 the factor from N synchronous fixed-point sweeps."""
+        self.set_property("factorSweeps", float(N))
         return self
 
     def set_guess_projection(self, K):

@@ -1735,6 +1735,81 @@ bool build_factor_structure(const HostPattern &p, bool ic, FactorStructure &F, o
     return true;
 }
 
+void build_factor_gather_lists(const FactorStructure &F, std::vector<int32_t> &gs_ptr, std::vector<int32_t> &gs_a,
+                               std::vector<int32_t> &gs_b)
+{
+    const int32_t N = (int32_t)F.row_ptrs.size() - 1, nf = (int32_t)F.cols.size();
+    gs_ptr.assign((size_t)nf + 1, 0);
+    gs_a.clear();
+    gs_b.clear();
+    std::vector<int32_t> where((size_t)N, -1), stamp((size_t)N, -1);
+    struct Pair {
+        int32_t target, a, b;
+    };
+    std::vector<Pair> row;
+    for (int32_t i = 0; i < N; ++i) {
+        const int32_t r0 = F.row_ptrs[(size_t)i], r1 = F.row_ptrs[(size_t)i + 1];
+        for (int32_t e = r0; e < r1; ++e) {
+            where[(size_t)F.cols[(size_t)e]] = e;
+            stamp[(size_t)F.cols[(size_t)e]] = i;
+        }
+        row.clear();
+        for (int32_t e = r0; e < F.diag[(size_t)i]; ++e) {  // k ascending: the same pairs as the scatter form
+            const int32_t k = F.cols[(size_t)e];
+            for (int32_t q = F.diag[(size_t)k] + 1; q < F.row_ptrs[(size_t)k + 1]; ++q) {
+                const int32_t j = F.cols[(size_t)q];
+                if (stamp[(size_t)j] == i) row.push_back(Pair{where[(size_t)j], e, q});
+            }
+        }
+        std::stable_sort(row.begin(), row.end(), [](const Pair &x, const Pair &y) { return x.target < y.target; });
+        for (const Pair &p : row) {
+            ++gs_ptr[(size_t)p.target + 1];
+            gs_a.push_back(p.a);
+            gs_b.push_back(p.b);
+        }
+    }
+    for (int32_t e = 0; e < nf; ++e) gs_ptr[(size_t)e + 1] += gs_ptr[(size_t)e];
+}
+
+bool factor_isai_pattern(const FactorStructure &F, int power, int max_row, std::vector<int32_t> &w_row_ptrs,
+                         std::vector<int32_t> &w_cols, std::vector<int32_t> &t_row_ptrs, std::vector<int32_t> &t_cols,
+                         std::vector<int32_t> &t_map, ogl_label &first_wide_row)
+{
+    const int32_t N = (int32_t)F.row_ptrs.size() - 1;
+    w_row_ptrs.assign((size_t)N + 1, 0);
+    w_cols.clear();
+    w_cols.reserve(F.cols.size());
+    std::vector<int32_t> seen((size_t)N, -1), row, next;
+    for (int32_t i = 0; i < N; ++i) {
+        row.clear();
+        for (int32_t e = F.row_ptrs[(size_t)i]; e <= F.diag[(size_t)i]; ++e) {
+            seen[(size_t)F.cols[(size_t)e]] = i;
+            row.push_back(F.cols[(size_t)e]);
+        }
+        for (int pw = 1; pw < power && (int)row.size() <= max_row; ++pw) {
+            next = row;
+            for (int32_t j : row)
+                for (int32_t e = F.row_ptrs[(size_t)j]; e <= F.diag[(size_t)j]; ++e) {
+                    const int32_t c = F.cols[(size_t)e];
+                    if (seen[(size_t)c] != i) {
+                        seen[(size_t)c] = i;
+                        next.push_back(c);
+                    }
+                }
+            row.swap(next);
+        }
+        if ((int)row.size() > max_row) {
+            first_wide_row = i;
+            return false;
+        }
+        std::sort(row.begin(), row.end());
+        w_cols.insert(w_cols.end(), row.begin(), row.end());
+        w_row_ptrs[(size_t)i + 1] = (int32_t)w_cols.size();
+    }
+    transpose_pattern(N, w_row_ptrs, w_cols, t_row_ptrs, t_cols, t_map);
+    return true;
+}
+
 void factor_segments(const std::vector<int32_t> &level_ptr, int32_t thin_rows, std::vector<int32_t> &seg)
 {
     seg.clear();

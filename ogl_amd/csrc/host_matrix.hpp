@@ -285,6 +285,17 @@ struct FactorStructure {
 };
 // false: row `bad_row` has no diagonal entry
 bool build_factor_structure(const HostPattern &p, bool ic, FactorStructure &F, ogl_label &bad_row);
+// Keyword factorSweeps, ILU: the update pairs of build_factor_structure in gather form -- for every factor entry
+// e = (i, j) the pairs (pos(i, k), pos(k, j)), k < min(i, j) ascending, at gs_ptr[e] .. gs_ptr[e + 1].  (IC's list is
+// in gather form already.)
+void build_factor_gather_lists(const FactorStructure &F, std::vector<int32_t> &gs_ptr, std::vector<int32_t> &gs_a,
+                               std::vector<int32_t> &gs_b);
+// Keyword triangularSolves isai: the pattern of W_L = the `power`-th power of the factor's lower-triangle pattern, the
+// diagonal included (rows ascending by column, the diagonal last), and its transpose (the pattern of W_U) with
+// t_map = position in W_L.  false (first_wide_row set): a row would get more than max_row entries.
+bool factor_isai_pattern(const FactorStructure &F, int power, int max_row, std::vector<int32_t> &w_row_ptrs,
+                         std::vector<int32_t> &w_cols, std::vector<int32_t> &t_row_ptrs, std::vector<int32_t> &t_cols,
+                         std::vector<int32_t> &t_map, ogl_label &first_wide_row);
 // Runs of consecutive levels of at most `thin_rows` rows each become one single-workgroup segment; every other level is
 // a segment of its own.  seg = (first level, end level, thin) triples.
 void factor_segments(const std::vector<int32_t> &level_ptr, int32_t thin_rows, std::vector<int32_t> &seg);

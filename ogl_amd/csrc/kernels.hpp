@@ -332,6 +332,22 @@ constexpr int IRILU_SWEEPS = 5;
 // one Richardson sweep x_out = x + D^-1 (b - T x) over all rows (inv_d == nullptr: D = I)
 void launch_tri_sweep(hipStream_t st, int32_t n, const DevTri &T, const double *inv_d, const double *b,
                       const double *x, double *x_out, const DevScalars *gate);
+// Keyword factorSweeps: the factor from synchronous fixed-point sweeps, one thread per row, every
+// entry from the values the sweep before left (`in` -> `out`, never in place).  a: the gathered values of A on the
+// factor's pattern.  gs_*: ILU's update pairs in gather form (build_factor_gather_lists); IC reads F.upd_*.
+// start: l_ii = sqrt(a_ii), l_ij = a_ij / sqrt(a_jj) (IC); l_ij = a_ij / a_jj, u_ij = a_ij (ILU).
+void launch_factor_sweep_start(hipStream_t st, const DevFactor &F, const double *a, double *out);
+// judge: the last sweep -- the smallest row whose l_ii is not > 0 (IC) / whose u_ii is 0 or not finite (ILU) goes into
+// F.breakdown
+void launch_factor_sweep(hipStream_t st, const DevFactor &F, const int32_t *gs_ptr, const int32_t *gs_a,
+                         const int32_t *gs_b, const double *a, const double *in, double *out, bool judge);
+// Keyword triangularSolves isai: row i of the approximate inverse of one triangle of the factor on the pattern J of row i
+// of W (ascending, at most FACTOR_ISAI_MAX_ROW entries), by substitution over T(J, J); lanes own rows, the entries of T
+// are searched in its rows.  Lower (W_L L = I on the pattern): from the diagonal, J's last entry, down; upper (ILU's U,
+// W_U U = I on the pattern): from the diagonal, J's first entry, up.
+constexpr int FACTOR_ISAI_MAX_ROW = 32;
+void launch_factor_isai_generate(hipStream_t st, int32_t n, const DevTri &T, const int32_t *w_row_ptrs,
+                                 const int32_t *w_cols, double *w_vals);
 // inv_d[i] = 1 / f[diag[i]]
 void launch_factor_inv_diag(hipStream_t st, int32_t n, const int32_t *diag, const double *f, double *inv_d);
 // gated permutations (as launch_permute_gather / _scatter)

@@ -3,6 +3,8 @@
 // Operation order is fixed (incomplete factorisations): rows in ascending index, entries in ascending column,
 // products and sums rounded separately (-ffp-contract=off), so the result equals a sequential walk bit for bit.
 // No kernel waits for another workgroup: a level is one launch, a run of thin levels one single-workgroup launch.
+// Keywords factorSweeps (the factor from synchronous fixed-point sweeps, one launch each) and triangularSolves isai (the
+// approximate inverses of the two triangles, applied as sparse products): DESIGN.md section 7a.
 #include "device_common.hpp"
 
 namespace ogl {
@@ -58,6 +60,98 @@ __global__ __launch_bounds__(BLOCK) void k_factor_thin(DevFactor F, const int *_
     for (int l = l0; l < l1; ++l) {
         for (int t = level_ptr[l] + (int)threadIdx.x; t < level_ptr[l + 1]; t += BLOCK) factor_row(F, rows[t]);
         __syncthreads();  // (one workgroup: its waves share the CU's L1, the barrier's fence orders the stores)
+    }
+}
+
+// keyword factorSweeps: the start values of the fixed-point sweeps, row i
+__global__ __launch_bounds__(BLOCK) void k_factor_sweep_start(DevFactor F, const double *__restrict__ a,
+                                                              double *__restrict__ out)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= F.n_rows) return;
+    const int r0 = F.row_ptrs[i], d = F.diag[i], r1 = F.row_ptrs[i + 1];
+    if (F.ic) {
+        for (int e = r0; e < d; ++e) out[e] = a[e] / sqrt(a[F.diag[F.cols[e]]]);
+        out[d] = sqrt(a[d]);
+    } else {
+        for (int e = r0; e < d; ++e) out[e] = a[e] / a[F.diag[F.cols[e]]];
+        for (int e = d; e < r1; ++e) out[e] = a[e];
+    }
+}
+
+// one synchronous sweep of row i: every entry from the values of the sweep before (in), its updates in ascending k
+template <bool JUDGE>
+__global__ __launch_bounds__(BLOCK) void k_factor_sweep(DevFactor F, const int *__restrict__ gs_ptr,
+                                                        const int *__restrict__ gs_a, const int *__restrict__ gs_b,
+                                                        const double *__restrict__ a, const double *__restrict__ in,
+                                                        double *__restrict__ out)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= F.n_rows) return;
+    const int r0 = F.row_ptrs[i], d = F.diag[i], r1 = F.row_ptrs[i + 1];
+    if (F.ic) {
+        for (int e = r0; e < d; ++e) {  // l_ij = (a_ij - sum_m<j l_im l_jm) / l_jj
+            double s = a[e];
+            for (int t = F.upd_ptr[e]; t < F.upd_ptr[e + 1]; ++t) s = s - in[F.upd_a[t]] * in[F.upd_b[t]];
+            out[e] = s / in[F.diag[F.cols[e]]];
+        }
+        double s = a[d];
+        for (int e = r0; e < d; ++e) s = s - in[e] * in[e];
+        const double l = sqrt(s);
+        out[d] = l;
+        if (JUDGE && !(l > 0.0)) atomicMin(F.breakdown, i);
+    } else {
+        for (int e = r0; e < r1; ++e) {  // s = a_ij - sum_k<min(i,j) l_ik u_kj; l_ij = s / u_jj, u_ij = s
+            double s = a[e];
+            for (int t = gs_ptr[e]; t < gs_ptr[e + 1]; ++t) s = s - in[gs_a[t]] * in[gs_b[t]];
+            out[e] = e < d ? s / in[F.diag[F.cols[e]]] : s;
+            if (JUDGE && e == d && !(fabs(s) > 0.0 && fabs(s) <= 1.7976931348623157e308)) atomicMin(F.breakdown, i);
+        }
+    }
+}
+
+// keyword triangularSolves isai: row i of the approximate inverse of triangle T on the row's pattern J, by substitution
+// over T(J, J); w is read back by the lane that wrote it
+__global__ __launch_bounds__(BLOCK) void k_factor_isai_generate(int n, DevTri T, const int *__restrict__ w_row_ptrs,
+                                                                const int *__restrict__ w_cols, double *w)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int *__restrict__ c = T.cols;
+    const double *__restrict__ v = T.vals;
+    const int a = w_row_ptrs[i], m = w_row_ptrs[i + 1] - a;
+    if (T.upper) {  // J[0] = i, upwards: w_t = (delta_t0 - sum_q<t w_q u(J[q], J[t])) / u(J[t], J[t])
+        for (int t = 0; t < m; ++t) {
+            const int jt = w_cols[a + t];
+            double s = t == 0 ? 1.0 : 0.0;
+            for (int q = 0; q < t; ++q) {
+                const int jq = w_cols[a + q], e1 = T.end[jq];
+                int lo = T.beg[jq] + 1, hi = e1;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (c[mid] < jt) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lo < e1 && c[lo] == jt) s = s - w[a + q] * v[lo];
+            }
+            w[a + t] = s / v[T.beg[jt]];
+        }
+    } else {  // J[m - 1] = i, downwards: w_t = (delta_t,m-1 - sum_q>t w_q l(J[q], J[t])) / l(J[t], J[t])
+        for (int t = m - 1; t >= 0; --t) {
+            const int jt = w_cols[a + t];
+            double s = t == m - 1 ? 1.0 : 0.0;
+            for (int q = t + 1; q < m; ++q) {
+                const int jq = w_cols[a + q], e1 = T.end[jq];
+                int lo = T.beg[jq], hi = e1;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (c[mid] < jt) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lo < e1 && c[lo] == jt) s = s - w[a + q] * v[lo];
+            }
+            w[a + t] = T.unit ? s : s / v[T.end[jt]];
+        }
     }
 }
 
@@ -192,6 +286,31 @@ void launch_tri_sweep(hipStream_t st, int32_t n, const DevTri &T, const double *
 {
     if (n == 0) return;
     hipLaunchKernelGGL(k_tri_sweep, dim3(blocks_for(n)), dim3(BLOCK), 0, st, n, T, inv_d, b, x, x_out, gate);
+}
+
+void launch_factor_sweep_start(hipStream_t st, const DevFactor &F, const double *a, double *out)
+{
+    if (F.n_rows == 0) return;
+    hipLaunchKernelGGL(k_factor_sweep_start, dim3(blocks_for(F.n_rows)), dim3(BLOCK), 0, st, F, a, out);
+}
+
+void launch_factor_sweep(hipStream_t st, const DevFactor &F, const int32_t *gs_ptr, const int32_t *gs_a,
+                         const int32_t *gs_b, const double *a, const double *in, double *out, bool judge)
+{
+    if (F.n_rows == 0) return;
+    if (judge)
+        hipLaunchKernelGGL(k_factor_sweep<true>, dim3(blocks_for(F.n_rows)), dim3(BLOCK), 0, st, F, gs_ptr, gs_a, gs_b, a, in,
+                           out);
+    else
+        hipLaunchKernelGGL(k_factor_sweep<false>, dim3(blocks_for(F.n_rows)), dim3(BLOCK), 0, st, F, gs_ptr, gs_a, gs_b, a, in,
+                           out);
+}
+
+void launch_factor_isai_generate(hipStream_t st, int32_t n, const DevTri &T, const int32_t *w_row_ptrs,
+                                 const int32_t *w_cols, double *w_vals)
+{
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_factor_isai_generate, dim3(blocks_for(n)), dim3(BLOCK), 0, st, n, T, w_row_ptrs, w_cols, w_vals);
 }
 
 void launch_factor_inv_diag(hipStream_t st, int32_t n, const int32_t *diag, const double *f, double *inv_d)

@@ -196,12 +196,38 @@ struct FactorPart {
     DevBuf<double> vals, t_vals, inv_d;
     DevBuf<int32_t> breakdown;  // first row with a zero / non-positive pivot (0x7f7f7f7f: none)
     std::vector<int32_t> fwd_ptr_h, bwd_ptr_h;
+    // keyword factorSweeps N (what this object was generated with): the gathered values of A, the second buffer of the
+    // sweeps, and ILU's update pairs in gather form, built for pattern gs_pat_id
+    int sweeps = 0;
+    DevBuf<double> a_vals, sw_vals;
+    DevBuf<int32_t> gs_ptr, gs_a, gs_b;
+    uint64_t gs_pat_id = 0;
+    // keyword triangularSolves isai (what this object was generated with): W_L in w.w_*, W_U in w.wt_* (IC: gathered
+    // through wt_map), both in the caller's numbering, their pattern built for (w_pat_id, w_power, w_ic)
+    bool tri_isai = false;
+    IsaiPart w;
+    uint64_t w_pat_id = 0;
+    int w_power = 0;
+    bool w_ic = false;
+    void release_sweeps()
+    {
+        for (DevBuf<int32_t> *b : {&gs_ptr, &gs_a, &gs_b}) b->release();
+        for (DevBuf<double> *b : {&a_vals, &sw_vals}) b->release();
+        gs_pat_id = 0;
+    }
+    void release_isai()
+    {
+        w.release();
+        w_pat_id = 0;
+    }
     void release()
     {
         for (DevBuf<int32_t> *b : {&row_ptrs, &cols, &diag, &map_ptr, &map, &upd_ptr, &upd_a, &upd_b, &t_row_ptrs, &t_cols, &t_map,
                                    &fwd_ptr, &fwd_rows, &bwd_ptr, &bwd_rows, &breakdown})
             b->release();
         for (DevBuf<double> *b : {&vals, &t_vals, &inv_d}) b->release();
+        release_sweeps();
+        release_isai();
     }
     DevFactor factor_view() const
     {
@@ -657,6 +683,7 @@ struct ogl_solver {
     // this solver's launch segments of the factor's level schedules ((first level, end level, thin) triples, property
     // iluThinRows), formed when the preconditioner is set up for a solve
     std::vector<int32_t> fac_seg_fwd, fac_seg_bwd;
+    bool fac_isai_scratch = false;  // the last apply set up here ran triangularSolves isai (its scratch is held)
     ogl::DevBuf<double> d_part0, d_part1, d_part2;  // (part2: beta partials of the fused-finaliser turn)
     int64_t band_order_rows = 0;
     bool source_diag_valid = false;  // d_source's diagonal segment is the diagonal of d_vals (set by the coefficient update)
@@ -709,6 +736,7 @@ struct ogl_solver {
     int prepare_apply();  // this solver's scratch and launch schedule for applies of precond_data
     void apply_factor(const double *in, double *out, const ogl::DevScalars *gate, double *dot_part);
     int check_factor_breakdown(int32_t word);
+    int check_factor_keywords();  // keywords triangularSolves and factorSweeps: validation, and IRILU + isai refused
     // out = M^-1 in for every kind (the Krylov loops fuse scalar Jacobi through `precond` instead); dot_part != nullptr:
     // also the per-chunk partials of sum_i in_i * out_i (CG's rho), out of the same kernel where the kind has one
     void apply_preconditioner(const double *in, double *out, const ogl::DevScalars *gate,

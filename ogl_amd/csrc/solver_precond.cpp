@@ -205,44 +205,123 @@ int ogl_solver::generate_factor(PrecondData &P)
     FactorPart &F = P.fac;
     const bool ic = cfg.preconditioner == OGL_PRECOND_IC;
     const PrecondKind skind = ic ? PrecondKind::Ic : PrecondKind::Ilu;  // (ILU and IRILU share the factor)
-    if (!P.has_structure(pat_id, skind, 0)) {
-        P.struct_pat_id = 0;
+    // keywords of the generating solve (validated in init_preconditioner): recorded in the object, which is applied the
+    // way it was generated
+    const bool want_isai = prop("triangularSolves", 0.0) == 1.0 && cfg.preconditioner != OGL_PRECOND_IRILU;
+    const int sweeps = (int)prop("factorSweeps", 0.0);
+    const int power = cfg.sparsity_power;
+    const bool have = P.has_structure(pat_id, skind, 0);
+    const bool need_w = want_isai && !(F.w_pat_id == pat_id && F.w_power == power && F.w_ic == ic);
+    const bool need_gs = sweeps > 0 && !ic && F.gs_pat_id != pat_id;
+    if (!have || need_w || need_gs) {
         OGL_TRY(download_local_pattern(pat));
         FactorStructure S;
         ogl_label bad = -1;
         if (!build_factor_structure(pat, ic, S, bad))
             return fail(OGL_ERR_INVALID, "preconditioner %s: row %d has no diagonal entry", precond_name(precond_kind_of(cfg)),
                         bad);
-        const std::pair<DevBuf<int32_t> *, const std::vector<int32_t> *> arrays[] = {
-            {&F.row_ptrs, &S.row_ptrs}, {&F.cols, &S.cols},         {&F.diag, &S.diag},         {&F.map_ptr, &S.map_ptr},
-            {&F.map, &S.map},           {&F.upd_ptr, &S.upd_ptr},   {&F.upd_a, &S.upd_a},       {&F.upd_b, &S.upd_b},
-            {&F.t_row_ptrs, &S.t_row_ptrs}, {&F.t_cols, &S.t_cols}, {&F.t_map, &S.t_map},       {&F.fwd_ptr, &S.fwd_ptr},
-            {&F.fwd_rows, &S.fwd_rows}, {&F.bwd_ptr, &S.bwd_ptr},   {&F.bwd_rows, &S.bwd_rows}};
-        for (const auto &a : arrays) OGL_TRY(upload(*a.first, *a.second, 0, reg->stager, st));
-        F.n_rows = pat.n_rows;
-        F.ic = ic;
-        F.nnz = (int32_t)S.cols.size();
-        OGL_TRY(F.vals.alloc(std::max<size_t>(1, S.cols.size()), st));
-        if (ic) OGL_TRY(F.t_vals.alloc(std::max<size_t>(1, S.cols.size()), st));
-        else F.t_vals.release();
-        OGL_TRY(F.breakdown.alloc(1, st));
-        F.fwd_ptr_h = S.fwd_ptr;
-        F.bwd_ptr_h = S.bwd_ptr;
-        props["iluUpdates"] = (double)S.upd_a.size();
-        P.set_structure(pat_id, skind, 0);
+        // (first what can refuse: the object stays what it was)
+        std::vector<int32_t> w_rp, w_c, wt_rp, wt_c, wt_m;
+        if (need_w && !factor_isai_pattern(S, power, FACTOR_ISAI_MAX_ROW, w_rp, w_c, wt_rp, wt_c, wt_m, bad))
+            return fail(OGL_ERR_UNSUPPORTED,
+                        "preconditioner %s, triangularSolves isai, sparsityPower %d: row %d of the approximate inverse has "
+                        "more than %d pattern entries (lower sparsityPower)", precond_name(skind), power, bad,
+                        FACTOR_ISAI_MAX_ROW);
+        if (!have) {
+            P.struct_pat_id = 0;
+            const std::pair<DevBuf<int32_t> *, const std::vector<int32_t> *> arrays[] = {
+                {&F.row_ptrs, &S.row_ptrs}, {&F.cols, &S.cols},         {&F.diag, &S.diag},         {&F.map_ptr, &S.map_ptr},
+                {&F.map, &S.map},           {&F.upd_ptr, &S.upd_ptr},   {&F.upd_a, &S.upd_a},       {&F.upd_b, &S.upd_b},
+                {&F.t_row_ptrs, &S.t_row_ptrs}, {&F.t_cols, &S.t_cols}, {&F.t_map, &S.t_map},       {&F.fwd_ptr, &S.fwd_ptr},
+                {&F.fwd_rows, &S.fwd_rows}, {&F.bwd_ptr, &S.bwd_ptr},   {&F.bwd_rows, &S.bwd_rows}};
+            for (const auto &a : arrays) OGL_TRY(upload(*a.first, *a.second, 0, reg->stager, st));
+            F.n_rows = pat.n_rows;
+            F.ic = ic;
+            F.nnz = (int32_t)S.cols.size();
+            OGL_TRY(F.vals.alloc(std::max<size_t>(1, S.cols.size()), st));
+            if (ic) OGL_TRY(F.t_vals.alloc(std::max<size_t>(1, S.cols.size()), st));
+            else F.t_vals.release();
+            OGL_TRY(F.breakdown.alloc(1, st));
+            F.fwd_ptr_h = S.fwd_ptr;
+            F.bwd_ptr_h = S.bwd_ptr;
+            props["iluUpdates"] = (double)S.upd_a.size();
+            P.set_structure(pat_id, skind, 0);
+        }
+        if (need_gs) {
+            F.gs_pat_id = 0;
+            std::vector<int32_t> gp, ga, gb;
+            build_factor_gather_lists(S, gp, ga, gb);
+            OGL_TRY(upload(F.gs_ptr, gp, 0, reg->stager, st));
+            OGL_TRY(upload(F.gs_a, ga, 0, reg->stager, st));
+            OGL_TRY(upload(F.gs_b, gb, 0, reg->stager, st));
+            F.gs_pat_id = pat_id;
+        }
+        if (need_w) {  // W_L and W_U = its transpose: CSR arrays padded like the system matrix, compressed where they qualify
+            IsaiPart &W = F.w;
+            F.w_pat_id = 0;
+            const int32_t N = pat.n_rows;
+            const bool sort_w = prop("isaiSortRows", 1.0) != 0.0;
+            auto compress = [&](SellDev &d, const std::vector<int32_t> &rp, const std::vector<int32_t> &c) -> int {
+                d.ready = false;
+                if (!cfg.compress_indices) return OGL_OK;
+                OGL_TRY(d.build(N, rp.data(), c.data(), reg->stager, st));
+                if (!d.ready && sort_w) OGL_TRY(d.build(N, rp.data(), c.data(), reg->stager, st, true));
+                return OGL_OK;
+            };
+            const size_t wn = w_c.size();
+            OGL_TRY(upload(W.w_row_ptrs, w_rp, 0, reg->stager, st));
+            OGL_TRY(upload(W.w_cols, w_c, NNZ_PAD, reg->stager, st));
+            OGL_TRY(W.w_vals.alloc(wn + NNZ_PAD, st));
+            OGL_TRY(upload(W.wt_row_ptrs, wt_rp, 0, reg->stager, st));
+            OGL_TRY(upload(W.wt_cols, wt_c, NNZ_PAD, reg->stager, st));
+            OGL_TRY(upload(W.wt_map, wt_m, NNZ_PAD, reg->stager, st));
+            OGL_TRY(W.wt_vals.alloc(wn + NNZ_PAD, st));
+            OGL_TRY(compress(W.w_sell, w_rp, w_c));
+            OGL_TRY(compress(W.wt_sell, wt_rp, wt_c));
+            W.w_nnz = (int32_t)wn;
+            F.w_power = power;
+            F.w_ic = ic;
+            F.w_pat_id = pat_id;
+        }
     }
-    // runs of levels of at most iluThinRows rows each: one single-workgroup launch per run
-    std::vector<int32_t> seg;
-    factor_segments(F.fwd_ptr_h, (int32_t)prop("iluThinRows", 256.0), seg);
+    if (!want_isai) F.release_isai();  // (switched back to exact: W goes)
+    if (sweeps == 0) F.release_sweeps();
+    F.tri_isai = want_isai;
+    F.sweeps = sweeps;
     OGL_HIP_CHECK(hipMemsetAsync(F.breakdown.p, 0x7f, sizeof(int32_t), st));
-    launch_factor_gather(st, F.nnz, F.map_ptr.p, F.map.p, csr().vals, F.vals.p);
     const DevFactor V = F.factor_view();
-    for (size_t g = 0; g + 2 < seg.size(); g += 3)
-        launch_factor_levels(st, V, F.fwd_ptr_h.data(), F.fwd_ptr.p, F.fwd_rows.p, seg[g], seg[g + 1], seg[g + 2] != 0);
+    if (sweeps > 0) {
+        // the factor from `sweeps` synchronous sweeps between two buffers, the last one into F.vals: one launch each
+        OGL_TRY(F.a_vals.alloc(std::max<size_t>(1, (size_t)F.nnz), st));
+        OGL_TRY(F.sw_vals.alloc(std::max<size_t>(1, (size_t)F.nnz), st));
+        launch_factor_gather(st, F.nnz, F.map_ptr.p, F.map.p, csr().vals, F.a_vals.p);
+        double *cur = sweeps % 2 == 0 ? F.vals.p : F.sw_vals.p, *other = sweeps % 2 == 0 ? F.sw_vals.p : F.vals.p;
+        launch_factor_sweep_start(st, V, F.a_vals.p, cur);
+        for (int k = 1; k <= sweeps; ++k) {
+            launch_factor_sweep(st, V, F.gs_ptr.p, F.gs_a.p, F.gs_b.p, F.a_vals.p, cur, other, k == sweeps);
+            std::swap(cur, other);
+        }
+    } else {
+        // runs of levels of at most iluThinRows rows each: one single-workgroup launch per run
+        std::vector<int32_t> seg;
+        factor_segments(F.fwd_ptr_h, (int32_t)prop("iluThinRows", 256.0), seg);
+        launch_factor_gather(st, F.nnz, F.map_ptr.p, F.map.p, csr().vals, F.vals.p);
+        for (size_t g = 0; g + 2 < seg.size(); g += 3)
+            launch_factor_levels(st, V, F.fwd_ptr_h.data(), F.fwd_ptr.p, F.fwd_rows.p, seg[g], seg[g + 1], seg[g + 2] != 0);
+    }
     if (ic) launch_gather_coeffs(st, F.nnz, F.t_map.p, F.vals.p, F.t_vals.p);
     if (cfg.preconditioner == OGL_PRECOND_IRILU) {
         OGL_TRY(F.inv_d.alloc((size_t)pat.n_rows + 2, st));
         launch_factor_inv_diag(st, pat.n_rows, F.diag.p, F.vals.p, F.inv_d.p);
+    }
+    if (want_isai) {
+        // W_L from L by substitution over each row's pattern; W_U = W_L^T (IC: gathered, nothing solved twice) or from U
+        IsaiPart &W = F.w;
+        launch_factor_isai_generate(st, F.n_rows, F.lower(), W.w_row_ptrs.p, W.w_cols.p, W.w_vals.p);
+        if (ic) launch_gather_coeffs(st, W.w_nnz, W.wt_map.p, W.w_vals.p, W.wt_vals.p);
+        else launch_factor_isai_generate(st, F.n_rows, F.upper(), W.wt_row_ptrs.p, W.wt_cols.p, W.wt_vals.p);
+        W.w_sell.refresh(W.w_vals.p, st);
+        W.wt_sell.refresh(W.wt_vals.p, st);
     }
     return OGL_OK;
 }
@@ -258,6 +337,36 @@ void ogl_solver::apply_factor(const double *in, double *out, const DevScalars *g
     const bool rn = pat.renumbered();
     const int32_t *perm = rn ? d_new_id.p : nullptr;
     const DevTri L = F.lower(), U = F.upper();
+    if (F.tri_isai) {
+        // keyword triangularSolves isai: y = W_L r, z = W_U y through the product kernels and layouts of ISAI's W / W^T
+        // (streamed past the caches exactly when the system matrix is); W lives in the caller's numbering
+        const bool stream_w = props.count("spmvStream") && props.at("spmvStream") == 1.0;
+        const IsaiPart &W = F.w;
+        const double *r = in;
+        double *y = d_fac_tmp[0].p, *z = rn ? d_fac_tmp[1].p : out;
+        if (rn) {
+            launch_factor_gather_perm(st, n, perm, in, d_fac_tmp[2].p, gate);
+            r = d_fac_tmp[2].p;
+        }
+        SpmvDots last{};
+        if (dot_part && !rn) {  // (the last product also leaves the partials of r . z)
+            last.with = in;
+            last.part = dot_part;
+        }
+        if (cfg.compress_indices && W.w_sell.ready)
+            launch_spmv_sell(st, W.w_sell.view(n, stream_w), SPMV_PLAIN, r, nullptr, y, SpmvDots{}, gate);
+        else
+            launch_spmv(st, W.w_view(n, stream_w), SPMV_PLAIN, r, nullptr, y, SpmvDots{}, gate);
+        if (cfg.compress_indices && W.wt_sell.ready)
+            launch_spmv_sell(st, W.wt_sell.view(n, stream_w), SPMV_PLAIN, y, nullptr, z, last, gate);
+        else
+            launch_spmv(st, W.wt_view(n, stream_w), SPMV_PLAIN, y, nullptr, z, last, gate);
+        if (rn) {
+            launch_factor_scatter_perm(st, n, perm, z, out, gate);
+            if (dot_part) launch_partials_dot(st, n, in, out, dot_part, gate);
+        }
+        return;
+    }
     if (precond_data->kind == PrecondKind::Irilu) {
         constexpr int sweeps = IRILU_SWEEPS;
         const double *b = in;
@@ -294,6 +403,23 @@ void ogl_solver::apply_factor(const double *in, double *out, const DevScalars *g
         if (rn) launch_factor_scatter_perm(st, n, perm, x, out, gate);
     }
     if (dot_part) launch_partials_dot(st, n, in, out, dot_part, gate);
+}
+
+// Keywords triangularSolves (property 0 exact | 1 isai) and factorSweeps (property 0 .. 10) of IC, ILU and IRILU; every
+// other preconditioner ignores them.
+int ogl_solver::check_factor_keywords()
+{
+    const double tri = prop("triangularSolves", 0.0), sw = prop("factorSweeps", 0.0);
+    if (tri != 0.0 && tri != 1.0)
+        return fail(OGL_ERR_INVALID, "triangularSolves %g is not 0 (exact) or 1 (isai)", tri);
+    if (!(sw >= 0.0 && sw <= 10.0) || sw != std::floor(sw))
+        return fail(OGL_ERR_INVALID, "factorSweeps %g is not an integer in [0, 10]", sw);
+    if (tri == 1.0 && cfg.preconditioner == OGL_PRECOND_IRILU)
+        return fail(OGL_ERR_UNSUPPORTED, "preconditioner IRILU with triangularSolves isai: IRILU has its own sweeps for the "
+                    "triangular solves (use IC or ILU)");
+    if (tri == 1.0 && (cfg.sparsity_power < 1 || cfg.sparsity_power > 8))
+        return fail(OGL_ERR_INVALID, "triangularSolves isai: sparsityPower %d outside [1, 8]", cfg.sparsity_power);
+    return OGL_OK;
 }
 
 // a zero (ILU) / non-positive (IC) pivot of the factor in use: the solve fails instead of handing out NaN.  `word` = the
@@ -410,16 +536,27 @@ int ogl_solver::prepare_apply()
     case PrecondKind::Irilu: {
         // vectors in the caller's order (renumbered) and IRILU's iterates
         const bool irilu = P.kind == PrecondKind::Irilu;
+        const bool tri_isai = P.fac.tri_isai;  // (of the object: it is applied the way it was generated)
         if (irilu) {
             OGL_TRY(d_fac_tmp[0].alloc(n, st));
             OGL_TRY(d_fac_tmp[1].alloc(n, st));
         }
+        if (tri_isai) {  // y = W_L r, and z in the caller's order on a renumbered copy
+            OGL_TRY(d_fac_tmp[0].alloc(n, st));
+            if (pat.renumbered()) OGL_TRY(d_fac_tmp[1].alloc(n, st));
+        } else if (fac_isai_scratch && !irilu) {  // (back on the exact solves: the scratch of the products goes)
+            d_fac_tmp[0].release();
+            d_fac_tmp[1].release();
+        }
+        fac_isai_scratch = tri_isai;
         if (pat.renumbered()) OGL_TRY(d_fac_tmp[2].alloc(n, st));
         const int32_t thin = (int32_t)prop("iluThinRows", 256.0);
         factor_segments(P.fac.fwd_ptr_h, thin, fac_seg_fwd);
         factor_segments(P.fac.bwd_ptr_h, thin, fac_seg_bwd);
         int launches = 0;
-        if (irilu) {
+        if (tri_isai) {
+            launches = 2 + (pat.renumbered() ? 2 : 0);
+        } else if (irilu) {
             launches = 2 * IRILU_SWEEPS + (pat.renumbered() ? 2 : 0);
         } else {
             for (const std::vector<int32_t> *seg : {&fac_seg_fwd, &fac_seg_bwd})
@@ -428,6 +565,9 @@ int ogl_solver::prepare_apply()
         }
         props["iluLevels"] = (double)(P.fac.fwd_ptr_h.size() - 1);
         props["iluLaunchesPerApply"] = (double)launches;  // (without the fused dot of a Krylov turn)
+        props["triangularSolvesInUse"] = tri_isai ? 1.0 : 0.0;
+        props["triangularWEntries"] = tri_isai ? (double)P.fac.w.w_nnz : 0.0;
+        props["factorSweepsInUse"] = (double)P.fac.sweeps;
         break;
     }
     }
@@ -462,6 +602,7 @@ int ogl_solver::init_preconditioner()
     if (cfg.preconditioner == OGL_PRECOND_BJ && (cfg.max_block_size < 1 || cfg.max_block_size > MAX_JACOBI_BLOCK))
         return fail(OGL_ERR_INVALID, "BJ maxBlockSize %d outside [1, %d]", cfg.max_block_size,
                     MAX_JACOBI_BLOCK);
+    if (is_factor(kind)) OGL_TRY(check_factor_keywords());
     const int stride = kind == PrecondKind::BlockJacobi ? cfg.max_block_size : (isai ? cfg.sparsity_power : 0);
     const int cache = (int)prop("preconditionerCaching", 0);
     const bool stored =
