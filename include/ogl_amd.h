@@ -537,6 +537,13 @@ int ogl_host_sym_check(ogl_label n_rows, const ogl_label *row_ptrs, const ogl_la
 int ogl_host_symx_check(ogl_label n_rows, const ogl_label *row_ptrs, const ogl_label *cols,
                         int64_t stats[8]);
 
+/* The table of input properties (csrc/properties.hpp), entry by entry: what ogl_solver_set_property is meant to be called
+ * with.  index 0 .. n-1; OGL_ERR_INVALID past the end.  kind: 0 fixed (the default is *fixed_default), 1 computed (the
+ * library works the default out from the environment or the run: *fixed_default is NaN, INTEGRATION.md section 6 says
+ * what it is), 2 state (the library reads and writes it; *fixed_default is what a read finds before the first write).
+ * The strings are static.  Any out pointer may be NULL. */
+int ogl_host_property(int32_t index, const char **name, double *fixed_default, int32_t *kind, const char **text);
+
 #ifdef __cplusplus
 }
 #endif

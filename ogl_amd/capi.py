@@ -20,6 +20,7 @@ PRECOND_NONE, PRECOND_BJ, PRECOND_ISAI, PRECOND_GISAI = 0, 1, 2, 3
 PRECOND_IC, PRECOND_ILU, PRECOND_IRILU = 4, 5, 6
 PRECOND_MULTIGRID = 7
 # keywords of the Multigrid sub-dictionary (Preconditioner.H:297-317): they travel as properties; cycle as a number
+# (defaults, ranges and one line each: the table in csrc/properties.hpp, which property_table() reads out)
 MG_KEYWORDS = ("maxLevels", "minCoarseRows", "coarseSolverIters", "cycle", "zeroGuess", "aggregation", "aggregatePasses",
                "aggregateCaching", "coarseVisits", "cyclePrecision", "smootherSweeps", "correctionScale")
 MG_CYCLE = {"v": 0, "w": 1, "f": 2}
@@ -114,6 +115,7 @@ EXPORTED_SYMBOLS = [
     "ogl_host_sell_check", "ogl_host_sym_check", "ogl_host_symx_check", "ogl_solver_get_renumbering", "ogl_host_rcm", "ogl_host_hilbert_order",
     "ogl_host_gather_sector_ratio", "ogl_host_pattern_renumbered",
     "ogl_host_addressing_fingerprint", "ogl_registry_comm_info", "ogl_memory_ledger_read", "ogl_registry_mem_info",
+    "ogl_host_property",
 ]
 
 
@@ -715,3 +717,17 @@ def host_adapt_criterion(cfg, prev_solve_iters, prev_rel_cost):
     lib().ogl_host_adapt_criterion(C.byref(cfg), C.c_int32(prev_solve_iters),
                                    C.c_double(prev_rel_cost), C.byref(mi), C.byref(fr))
     return mi.value, fr.value
+
+
+PROPERTY_KINDS = ("fixed", "computed", "state")
+
+
+def property_table():
+    """The input properties as csrc/properties.hpp declares them: [(name, default, kind, text)], kind one of
+    PROPERTY_KINDS; the default of a computed entry is NaN."""
+    out = []
+    while True:
+        name, text, dflt, kind = C.c_char_p(), C.c_char_p(), C.c_double(), C.c_int32()
+        if lib().ogl_host_property(C.c_int32(len(out)), C.byref(name), C.byref(dflt), C.byref(kind), C.byref(text)) < 0:
+            return out
+        out.append((name.value.decode(), dflt.value, PROPERTY_KINDS[kind.value], text.value.decode()))

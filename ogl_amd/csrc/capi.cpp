@@ -331,6 +331,17 @@ extern "C" int ogl_solver_set_property(ogl_solver *s, const char *key, double va
     OGL_GUARD_END
 }
 
+extern "C" int ogl_host_property(int32_t index, const char **name, double *fixed_default, int32_t *kind, const char **text)
+{
+    if (index < 0 || index >= ogl::N_KNOBS) return fail(OGL_ERR_INVALID, "no property %d (the table has %d)", index, ogl::N_KNOBS);
+    const ogl::KnobEntry &e = ogl::KNOBS[index];
+    if (name) *name = e.name;
+    if (fixed_default) *fixed_default = e.dflt.value;
+    if (kind) *kind = (int32_t)e.dflt.kind;
+    if (text) *text = e.text;
+    return OGL_OK;
+}
+
 extern "C" int ogl_solver_apply_resident(ogl_solver *s, ogl_perf *perf)
 {
     OGL_GUARD_BEGIN

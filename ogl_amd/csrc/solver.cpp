@@ -259,10 +259,32 @@ ogl_solver::~ogl_solver()
         if (e) ev_destroy(e);
 }
 
-double ogl_solver::prop(const std::string &key, double dflt) const
+double ogl_solver::knob_value(Knob k, double dflt) const
 {
-    auto it = props.find(key);
+    auto it = props.find(knob_entry(k).name);
     return it == props.end() ? dflt : it->second;
+}
+
+// Every range check of a property: the keyword, the offending value, what is allowed.
+int ogl_solver::check_knob(Knob k) const
+{
+    const KnobEntry &e = knob_entry(k);
+    const KnobDomain &d = e.domain;
+    const double v = knob_value(k, e.dflt.value);
+    if (d.type == KnobDomain::None) return OGL_OK;
+    if (d.type == KnobDomain::Open ? v > d.lo && v < d.hi : v >= d.lo && v <= d.hi && v == std::floor(v)) return OGL_OK;
+    char range[64];
+    std::snprintf(range, sizeof range, d.type == KnobDomain::Open ? "a number in (%g, %g)" : "a whole number in [%g, %g]", d.lo, d.hi);
+    std::string allowed = d.type == KnobDomain::Flag ? "0 or 1" : range;
+    if (d.type == KnobDomain::Choice) {  // the numbers with their words
+        int n = 0;
+        allowed = "one of 0 (";
+        for (const char *p = d.words; *p; ++p)
+            if (*p == '|') allowed += "), " + std::to_string(++n) + " (";
+            else allowed += *p;
+        allowed += ")";
+    }
+    return fail(OGL_ERR_INVALID, "%s %g is not %s", e.name, v, allowed.c_str());
 }
 
 // Size above which matrix data is streamed past the caches (STREAM instantiations, common.hpp).  The
@@ -274,7 +296,7 @@ double ogl_solver::stream_above_bytes() const
         const char *e = std::getenv("OGL_STREAM_ABOVE_BYTES");
         return e ? atof(e) : STREAM_MATRIX_ABOVE_BYTES;
     }();
-    return prop("streamAboveBytes", env_default);
+    return knob<Knob::streamAboveBytes>(env_default);
 }
 
 // What a turn of this solver touches BESIDES the system matrix and GKOCG's five vectors (which the built-in threshold
@@ -284,7 +306,7 @@ double ogl_solver::stream_above_bytes() const
 // the matrix alone decides, as before round 5).
 double ogl_solver::turn_extra_bytes() const
 {
-    if (prop("streamTurnSet", 1.0) == 0.0) return 0.0;
+    if (knob<Knob::streamTurnSet>() == 0.0) return 0.0;
     const double N = (double)pat.n_rows, nnz = (double)pat.local_nnz;
     double extra = 0.0;
     if (cfg.preconditioner == OGL_PRECOND_ISAI) extra += 10.0 * (nnz + N);      // tril(A) twice, ~10 bytes per entry
@@ -314,7 +336,7 @@ int32_t ogl_solver::xcd_group() const
         const char *e = std::getenv("OGL_XCD_GROUP");
         return e ? atoi(e) : -1;
     }();
-    const int v = (int)prop("xcdGroup", (double)env_default);
+    const int v = (int)knob<Knob::xcdGroup>((double)env_default);
     return v >= 0 ? v : pat_xcd_group;
 }
 
@@ -328,7 +350,7 @@ DevCsr ogl_solver::csr(bool packed) const
     A.vals = d_vals.p;
     A.stream = streamed(12.0 * (double)pat.local_nnz + 44.0 * (double)pat.n_rows);
     A.xcd_group = xcd_group();
-    A.lds_rounds = prop("spmvLdsRounds", 1.0) == 2.0 ? 2 : 1;
+    A.lds_rounds = knob<Knob::spmvLdsRounds>() == 2.0 ? 2 : 1;
     if (d_band_order.n) {
         A.block_order = d_band_order.p;
         A.n_blocks = (int32_t)d_band_order.n;
@@ -830,7 +852,7 @@ int ogl_solver::select_spmv_layout()
         // fabric (1.19 -> 1.02 x the model's bytes, profiles/r06_pmc_nocompress_summary.json), so it gets the order too.
         // Property spmvBandRows: the band in rows, 0 = off, -1 (default) = the largest offset of a banded pattern (the
         // compressed layout's tables; for the CSR arrays the distance table of the half-storage set-up, csr_band()).
-        int64_t band = (int64_t)prop("spmvBandRows", -1.0);
+        int64_t band = (int64_t)knob<Knob::spmvBandRows>();
         if (band < 0) {
             band = 0;
             if (l == L::Sell) band = sell_dev.band_rows;
@@ -868,7 +890,7 @@ int ogl_solver::select_spmv_layout()
     case L::Sell: stream = sell().stream; break;
     default: stream = csr().stream;
     }
-    props["spmvStream"] = stream ? 1.0 : 0.0;
+    set_knob<Knob::spmvStream>(stream ? 1.0 : 0.0);
     props["spmvSymFast"] = fast ? 1.0 : 0.0;
     return OGL_OK;
 }
@@ -1083,7 +1105,7 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
         // Where the pattern is built: on the device from the face addressing (setup_kernels.hip), unless the
         // environment / property says otherwise or the addressing is not conforming; host_matrix.cpp then
         static const bool host_setup_env = std::getenv("OGL_HOST_SETUP") != nullptr;
-        const bool device_setup = !host_setup_env && prop("deviceSetup", 1.0) != 0.0;
+        const bool device_setup = !host_setup_env && knob<Knob::deviceSetup>() != 0.0;
         OGL_TRY(build_host_pattern_meta(ldu, np, /*check_faces*/ !device_setup));
         // (the hash of the addressing runs on helper threads next to everything below; joined before any return)
         auto fp_new = std::async(std::launch::async, [&ldu] { return addressing_fingerprint(ldu); });
@@ -1105,7 +1127,7 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
                         return fail(OGL_ERR_INVALID, "face %d addresses a cell outside [0,%d)", f, np.n_rows);
             build_local_pattern(ldu, np);
         }
-        props["deviceSetup"] = device_setup ? 1.0 : 0.0;
+        set_knob<Knob::deviceSetup>(device_setup ? 1.0 : 0.0);
         props["patternBuiltOnDevice"] = built_on_device ? 1.0 : 0.0;
         // A symmetric lduMatrix without same-rank interfaces is tried on the half storage first (banded with
         // at most SYM_MAX_OFFSETS - 1 distances = a structured mesh, whose numbering the policy below would
@@ -1113,7 +1135,7 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
         SymDistances sym_dist{};
         bool sym_on_device = false, sym_tried = false, renumbered_on_device = false;
         // (symmetricHalfWhole_enable 0: an experiment switch -- the per-chunk variant on a pattern the whole-matrix one takes)
-        const bool whole_sym = prop("symmetricHalfWhole_enable", 1.0) != 0.0;
+        const bool whole_sym = knob<Knob::symmetricHalfWhole_enable>() != 0.0;
         if (built_on_device && whole_sym && try_sym && np.symmetric && np.local_iface_nnz == 0 && cfg.renumber != 1) {
             sym_tried = true;
             OGL_TRY(build_sym_on_device(np, &sym_dist, &sym_on_device));
@@ -1139,9 +1161,9 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
                 };
             }
             // (cell centres, when the caller passes them: the Hilbert-curve candidate; property renumberCurve 0 = RCM only)
-            if (ldu.cell_centres && prop("renumberCurve", 1.0) != 0.0) {
+            if (ldu.cell_centres && knob<Knob::renumberCurve>() != 0.0) {
                 hooks.centres = ldu.cell_centres;
-                if (built_on_device && prop("curveOnDevice", 1.0) != 0.0) {
+                if (built_on_device && knob<Knob::curveOnDevice>() != 0.0) {
                     hooks.curve = [&](ogl_label n, const double *centres, std::vector<ogl_label> &nid) {
                         return curve_on_device(n, centres, nid) == OGL_OK && !nid.empty();
                     };
@@ -1283,7 +1305,7 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
         if (sym_on_device) {
             OGL_TRY(sym_dev.finish(sym_dist.nd, sym_dist.d, pat.n_rows, reg->stager, st, props));
             sym_ok = true;
-        } else if (!sym_tried && prop("symmetricHalfWhole_enable", 1.0) != 0.0 && try_sym && pat.symmetric &&
+        } else if (!sym_tried && knob<Knob::symmetricHalfWhole_enable>() != 0.0 && try_sym && pat.symmetric &&
                    pat.local_iface_nnz == 0 && !pat.renumbered()) {
             SymLayout symL;
             if (build_sym_layout(pat.n_rows, pat.row_ptrs.data(), pat.cols.data(), symL)) {
@@ -1293,7 +1315,7 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
         }
         props["symmetricHalfPerChunk"] = 0.0;
         if (!sym_ok && try_sym && pat.symmetric && pat.local_iface_nnz == 0 && !pat.renumbered() &&
-            prop("symmetricHalfPerChunk_enable", 1.0) != 0.0) {
+            knob<Knob::symmetricHalfPerChunk_enable>() != 0.0) {
             // banded only locally (multi-block mesh, refinement shell): per-chunk distances + explicit exceptions
             OGL_TRY(download_local_pattern(pat));
             OGL_TRY(symx_dev.build(pat, reg->stager, st, props));
@@ -1353,7 +1375,7 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
             if (s21_dev.ready) cand.push_back(SpmvLayout::Csr21);
             // (property spmvForceLayout 0 | 1 | 2: CSR-stream | compressed | packed columns whatever the timing says -- how
             //  the parity tests reach a layout on a pattern where another one wins)
-            const int forced = (int)prop("spmvForceLayout", -1.0);
+            const int forced = (int)knob<Knob::spmvForceLayout>();
             const SpmvLayout by_force[3] = {SpmvLayout::Csr, SpmvLayout::Sell, SpmvLayout::Csr21};
             SpmvLayout win;
             OGL_TRY(tune_spmv_layouts(cand, forced >= 0 && forced < 3 ? &by_force[forced] : nullptr, &win));

@@ -15,6 +15,7 @@
 #include "common.hpp"
 #include "host_matrix.hpp"
 #include "kernels.hpp"
+#include "properties.hpp"
 #include "setup_kernels.hpp"
 #include "spmv_layouts.hpp"
 
@@ -808,7 +809,29 @@ struct ogl_solver {
     int turn_bicg(KrylovRun &k, int enq, int pe);
     int time_spmv(int repeats, double *avg_ms);
     ogl::DevHalo halo() const;
-    double prop(const std::string &key, double dflt) const;
+    // The input properties (properties.hpp): a read names its knob by identifier and takes the table's default; only a
+    // knob of the computed kind takes its default from the call site, and only it may.
+    double knob_value(ogl::Knob k, double dflt) const;
+    template <ogl::Knob K>
+    double knob() const
+    {
+        static_assert(ogl::knob_entry(K).dflt.kind != ogl::KnobKind::Computed, "a computed knob takes its default from the call site");
+        return knob_value(K, ogl::knob_entry(K).dflt.value);
+    }
+    template <ogl::Knob K>
+    double knob(double computed_default) const
+    {
+        static_assert(ogl::knob_entry(K).dflt.kind == ogl::KnobKind::Computed, "this knob's default stands in the table");
+        return knob_value(K, computed_default);
+    }
+    template <ogl::Knob K>
+    void set_knob(double v)  // (the effective value written back, or state)
+    {
+        static_assert(ogl::knob_entry(K).written_back || ogl::knob_entry(K).dflt.kind == ogl::KnobKind::State,
+                      "the library writes only state and the knobs marked WRITTEN_BACK");
+        props[ogl::knob_entry(K).name] = v;
+    }
+    int check_knob(ogl::Knob k) const;  // the current value against the table's domain: OGL_ERR_INVALID, one phrasing
     // ogl_solver_set_matrix_like: the solver whose device copy of upper / lower this set_matrix may take (only during
     // that call), and what THIS solver's copy was uploaded from (host arrays + sampled checksum) for a later taker
     const ogl_solver *share_from = nullptr;

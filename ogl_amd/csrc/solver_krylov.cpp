@@ -18,7 +18,7 @@ using namespace ogl;
 HaloPutFused ogl_solver::begin_halo_put()
 {
     HaloPutFused put;
-    if (!(pat.non_local_nnz > 0 && peer_halo) || prop("haloFused", 1.0) == 0.0 || peer_safe_wait())
+    if (!(pat.non_local_nnz > 0 && peer_halo) || knob<Knob::haloFused>() == 0.0 || peer_safe_wait())
         return put;
     cur_halo = next_exchange(sizeof(double));
     put.P = cur_halo;
@@ -75,7 +75,7 @@ int ogl_solver::dist_spmv(int mode, const double *x, const double *b, double *y,
     // report the same PCI bus id): no workgroup of the SpMV waits -- ONE workgroup of a
     // kernel of its own does, then the non-local part is added by kernels that find the values there.  Many waiting
     // workgroups of several ranks on one device can hold every slot the producers' put kernels need.
-    if (peer_halo && !peer_safe_wait() && prop("haloFused", 1.0) != 0.0) {
+    if (peer_halo && !peer_safe_wait() && knob<Knob::haloFused>() != 0.0) {
         PeerHalo ph = cur_halo;
         if (!prepacked) {
             ph = next_exchange(sizeof(double));
@@ -184,9 +184,8 @@ int ogl_solver::ortho_requested(int *method)
 {
     *method = 0;
     if (cfg.solver != OGL_SOLVER_GMRES) return OGL_OK;
-    const double v = prop("orthoMethod", 0.0);
-    if (v != 0.0 && v != 1.0 && v != 2.0)
-        return fail(OGL_ERR_INVALID, "orthoMethod %g is none of 0 (mgs), 1 (cgs), 2 (cgs2)", v);
+    OGL_TRY(check_knob(Knob::orthoMethod));
+    const double v = knob<Knob::orthoMethod>();
     const int n_ranks = reg->comm ? reg->comm->n_ranks : 1;
     if (v != 0.0 && n_ranks > 1)
         return fail(OGL_ERR_UNSUPPORTED, "orthoMethod %s runs GKOGMRES on one rank: this registry has %d ranks",
@@ -202,8 +201,8 @@ int ogl_solver::basis_requested(bool *single)
 {
     *single = false;
     if (cfg.solver != OGL_SOLVER_GMRES) return OGL_OK;
-    const double v = prop("basisPrecision", 0.0);
-    if (v != 0.0 && v != 1.0) return fail(OGL_ERR_INVALID, "basisPrecision %g is neither 0 (double) nor 1 (single)", v);
+    OGL_TRY(check_knob(Knob::basisPrecision));
+    const double v = knob<Knob::basisPrecision>();
     int ortho = 0;
     OGL_TRY(ortho_requested(&ortho));
     if (v == 1.0 && ortho == 0)
@@ -245,13 +244,13 @@ int ogl_solver::krylov_plan(KrylovRun &k)
     k.has_diag = precond != nullptr;
     const bool multi = k.multi = reg->comm->multi();
     const bool small = !multi && nc >= 1 &&
-                       nc <= std::min((int)prop("fusedFinMaxChunks", (double)FUSED_FIN_MAX_CHUNKS), FUSED_FIN_MAX_CHUNKS) &&
-                       prop("fusedFinalizers", 1.0) != 0.0;
+                       nc <= std::min((int)knob<Knob::fusedFinMaxChunks>(), FUSED_FIN_MAX_CHUNKS) &&
+                       knob<Knob::fusedFinalizers>() != 0.0;
     // small single-rank GKOCG systems: finalisers folded into the step kernels, 3 launches per turn (kernels_krylov.hip)
     // ... and for LARGER single-rank GKOCG systems the same three launches with the LEADER finalisation (device_common.hpp):
     // workgroup 0 of the consuming kernel is the finaliser, the others poll its mailbox -- instead of two
     // single-workgroup launches (10 + 7 us at 10 M rows) and their dispatch gaps per turn (property leadFinalizers)
-    const bool lead_any = !multi && !small && nc >= 3 * 16 && prop("leadFinalizers", 1.0) != 0.0;
+    const bool lead_any = !multi && !small && nc >= 3 * 16 && knob<Knob::leadFinalizers>() != 0.0;
     // (GKOCG with a materialised z -- block Jacobi, ISAI -- takes the leader finalisation too: the same two kernels with
     //  z in r's place, the preconditioner's launches between step_2r and the next turn's check)
     const bool lead_ok = lead_any && !bicg && !gmres;
@@ -262,7 +261,7 @@ int ogl_solver::krylov_plan(KrylovRun &k)
     // (k_bicg_fold1/2/3: 5 launches per turn instead of 8, plus the preconditioner's own)
     // (larger systems: the same five launches with the leader finalisation, any preconditioner -- the 2 M-row momentum
     //  systems of configs[2] spend a tenth of a turn in three single-workgroup launches and their gaps)
-    k.bicg_fold = bicg && (small || lead_any) && prop("bicgFold", 1.0) != 0.0;
+    k.bicg_fold = bicg && (small || lead_any) && knob<Knob::bicgFold>() != 0.0;
     // ... and for small single-rank GKOGMRES systems the finaliser between two Gram-Schmidt links is folded into the next
     // link's kernel (k_gmres_mgs_fold: one launch per link instead of two)
     // (larger systems: with the leader finalisation on request only, property gmresLead -- a Gram-Schmidt link moves 16 N
@@ -271,7 +270,7 @@ int ogl_solver::krylov_plan(KrylovRun &k)
     props["orthoMethodInUse"] = (double)k.ortho;
     OGL_TRY(basis_requested(&k.basis_single));
     k.ldvf = ((int64_t)n + 3) & ~(int64_t)3;
-    k.gmres_fold = gmres && !k.ortho && (small || (lead_any && prop("gmresLead", 0.0) != 0.0)) && prop("gmresFold", 1.0) != 0.0;
+    k.gmres_fold = gmres && !k.ortho && (small || (lead_any && knob<Knob::gmresLead>() != 0.0)) && knob<Knob::gmresFold>() != 0.0;
     // launches of a single-rank turn, averaged over a full cycle: the SpMV's one, the scaling's one and the Gram-Schmidt step
     // with the column's finaliser -- it + 3 folded links or 2 it + 4 launches at column `it`, 4 | 6 in block form (the
     // preconditioner's own launches, where it has any, are not counted)
@@ -293,9 +292,9 @@ int ogl_solver::krylov_plan(KrylovRun &k)
     // nothing to put and only waits for a put of the PREVIOUS launch.  Every rank must run the same turn (what the
     // neighbours put differs): agreed below together with the global row count.
     bool merged = !bicg && !gmres && !generic && nc >= 1 && spmv_layout == SpmvLayout::Sym &&
-                  ((fused && small) ? prop("fusedTurn", 1.0) != 0.0 : prop("fusedTurnBig", sym().stream ? 0.0 : 1.0) != 0.0);
+                  ((fused && small) ? knob<Knob::fusedTurn>() != 0.0 : knob<Knob::fusedTurnBig>(sym().stream ? 0.0 : 1.0) != 0.0);
     if (multi)
-        merged = merged && peer_halo && prop("haloFused", 1.0) != 0.0 && prop("fusedTurnMulti", 1.0) != 0.0 &&
+        merged = merged && peer_halo && knob<Knob::haloFused>() != 0.0 && knob<Knob::fusedTurnMulti>() != 0.0 &&
                  !peer_safe_wait();
     k.n_global = (double)n;
     if (multi) {
@@ -321,8 +320,8 @@ int ogl_solver::krylov_plan(KrylovRun &k)
         // (tags restart at 1 with every solve: no word of an earlier solve may survive)
         OGL_HIP_CHECK(hipMemsetAsync(lead_box, 0, LEAD_REPLICAS * LEAD_REPLICA_STRIDE * sizeof(unsigned long long), st));
         k.lead.box = lead_box;
-        k.lead.timeout_ticks = (long long)(prop("leadTimeoutS", 10.0) * 1e8);
-        k.lead.early_loads = prop("leadEarlyLoads", 1.0) != 0.0 ? 1 : 0;
+        k.lead.timeout_ticks = (long long)(knob<Knob::leadTimeoutS>() * 1e8);
+        k.lead.early_loads = knob<Knob::leadEarlyLoads>() != 0.0 ? 1 : 0;
     }
     props["leadFinalizersInUse"] = k.lead.box ? 1.0 : 0.0;
     props["fusedFinalizersInUse"] = ((fused || k.bicg_fold || k.gmres_fold) && small) ? 1.0 : 0.0;
@@ -345,8 +344,8 @@ int ogl_solver::krylov_prepare(KrylovRun &k)
     //  rows two buffers give +1.2 % over none, four the same as two, eight lose 6 % -- the pending directions push the
     //  turn's other vectors out of the Infinity Cache: profiles/r06_defer_ab.txt)
     int ring_k = 0;
-    if (k.lead.box != nullptr && k.fused && !k.fused2 && prop("deferX2", 1.0) != 0.0) {
-        const double want = prop("deferX", 2.0);
+    if (k.lead.box != nullptr && k.fused && !k.fused2 && knob<Knob::deferX2>() != 0.0) {
+        const double want = knob<Knob::deferX>();
         ring_k = want >= 8.0 ? 8 : want >= 4.0 ? 4 : want >= 2.0 ? 2 : 0;
     }
     props["deferXInUse"] = (double)ring_k;
@@ -369,8 +368,8 @@ int ogl_solver::krylov_prepare(KrylovRun &k)
 
     // StoppingCriterion ctor + build_dist_stopping_criterion (StoppingCriterion.H:164-234)
     k.is_final = cfg.rel_tol == 0.0;  // get_is_final, :242
-    const int prev_iters = (int)prop(k.is_final ? "prevSolveIters_final" : "prevSolveIters", 1);
-    const double prev_cost = prop("_prev_solve", 0.0);
+    const int prev_iters = (int)(k.is_final ? knob<Knob::prevSolveIters_final>() : knob<Knob::prevSolveIters>());
+    const double prev_cost = knob<Knob::_prev_solve>();
     DevCriterion &crit = k.crit;
     crit.tolerance = cfg.tolerance;
     crit.rel_tol = cfg.rel_tol;
@@ -686,7 +685,7 @@ int ogl_solver::turn_gmres_f32_basis(KrylovRun &k, int it, int pe)
 // (with cgs2's second-round partials).  The coefficients are zeroed first: the update leaves the basis as it is.
 int ogl_solver::time_ortho_kernels(KrylovRun &k)
 {
-    const int timed = (int)prop("orthoTimedLaunches", 0.0);
+    const int timed = (int)knob<Knob::orthoTimedLaunches>();
     if (timed <= 0 || !k.ortho) return OGL_OK;
     hipStream_t st = k.st;
     EventPair ev;
@@ -854,12 +853,12 @@ int ogl_solver::plan_held_z(KrylovRun &k)
     case SpmvLayout::Symx: streams = symx().stream; break;
     default: streams = csr().stream; break;
     }
-    if (prop("heldZ", streams ? 1.0 : 0.0) == 0.0 || held_z_census < 0) return OGL_OK;
+    if (knob<Knob::heldZ>(streams ? 1.0 : 0.0) == 0.0 || held_z_census < 0) return OGL_OK;
     int per_wg = 0;
     int grid = held_z_grid(&per_wg);
-    grid = std::min(grid, (int)prop("heldZGrid", (double)grid));  // (only ever fewer workgroups: tests reach LDS-held chunks with it)
+    grid = std::min(grid, (int)knob<Knob::heldZGrid>((double)grid));  // (only ever fewer workgroups: tests reach LDS-held chunks with it)
     if (grid < 2 * 16) return OGL_OK;  // (the 2 x 16 leaders of the sums)
-    const double cap = std::min((double)grid * per_wg, prop("heldZMaxChunks", (double)grid * per_wg));
+    const double cap = std::min((double)grid * per_wg, knob<Knob::heldZMaxChunks>((double)grid * per_wg));
     if ((double)k.nc > cap) return OGL_OK;
     // ... and the held-q turn on top of it: half storage, by default where that layout streams (property heldQ), and
     // only where the POSITIONS of its launch order -- the band order has holes, the default map is padded -- fit the slots.
@@ -869,7 +868,7 @@ int ogl_solver::plan_held_z(KrylovRun &k)
     int n_pos = 0;
     if (spmv_layout == SpmvLayout::Sym) {
         n_pos = held_q_positions(sym());
-        held_q = prop("heldQ", sym().stream && grid % 8 == 0 ? 1.0 : 0.0) != 0.0 && (double)n_pos <= (double)grid * per_wg;
+        held_q = knob<Knob::heldQ>(sym().stream && grid % 8 == 0 ? 1.0 : 0.0) != 0.0 && (double)n_pos <= (double)grid * per_wg;
     }
     hipStream_t st = k.st;
     const size_t words = (held_q ? 6 : 4) * (size_t)k.nc;  // (both turn kernels of a mixed solve use the one box: the tags tell)
@@ -889,7 +888,7 @@ int ogl_solver::plan_held_z(KrylovRun &k)
         int timed_out = 1;
         // (a census that cannot see everybody within a second has its answer)
         const int rc = launch_resident_census(st, grid, static_cast<unsigned *>(c), static_cast<int *>(c) + 1,
-                                              (long long)(prop("heldZCensusS", 1.0) * 1e8));
+                                              (long long)(knob<Knob::heldZCensusS>() * 1e8));
         hipError_t e = rc == 0 ? hipMemcpyAsync(&timed_out, static_cast<int *>(c) + 1, sizeof(int), hipMemcpyDeviceToHost, st)
                                : hipErrorUnknown;
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -904,8 +903,8 @@ int ogl_solver::plan_held_z(KrylovRun &k)
     // heldZEarlyX 0 switches early x off; heldZEarlySlots: for how many of a workgroup's slots it runs.  4 by default: the
     // wait it covers is 6 us, a slot of it takes 2 us, and every slot more is 1/20 of p read twice.  Measured
     // (profiles/r11_resident_waits.txt, section 3): 0 and 4 slots run level, all 20 are slower by 2 %.
-    const int early_slots = std::max(0, std::min(per_wg, (int)prop("heldZEarlySlots", 4.0)));
-    k.hz.early_slots = prop("heldZEarlyX", 1.0) != 0.0 ? early_slots : 0;
+    const int early_slots = std::max(0, std::min(per_wg, (int)knob<Knob::heldZEarlySlots>()));
+    k.hz.early_slots = knob<Knob::heldZEarlyX>() != 0.0 ? early_slots : 0;
     props["heldZInUse"] = 1.0;
     props["heldZGridInUse"] = (double)grid;
     if (held_q) {
@@ -919,8 +918,8 @@ int ogl_solver::plan_held_z(KrylovRun &k)
         // nothing, so the others fill the slots past HQ_STATIC.  The draw is complete only where, queue by queue, the
         // drawing workgroups' free slots hold the queue; anything else runs the static map.
         const int slots = HQ_R + HZ_L;
-        const int S = std::max(0, std::min(HQ_STATIC, (int)prop("heldQStaticSlots", (double)HQ_STATIC_DEFAULT)));
-        const int idle = (int)prop("heldQIdleGroups", 0.0);
+        const int S = std::max(0, std::min(HQ_STATIC, (int)knob<Knob::heldQStaticSlots>()));
+        const int idle = (int)knob<Knob::heldQIdleGroups>();
         const int drawers = (S == 0 && idle > 0 && idle % N_XCD == 0 && idle < grid) ? grid - idle : grid;
         bool fits = (long long)S * grid < n_pos;  // (else there is nothing to draw)
         for (int q = 0; fits && q < N_XCD; ++q) {
@@ -1044,7 +1043,7 @@ int ogl_solver::turn_bicg(KrylovRun &k, int enq, int pe)
                       SpmvDots{d_rr.p, d_part0.p, nullptr}, s));
     if (pe >= 0) OGL_HIP_CHECK(hipEventRecord(prof_ev[2 * pe + 1], st));
     OGL_TRY(finalize(FIN_BICG_ALPHA, f1));
-    if (!k.multi && prop("bicgMergedCheck", 1.0) != 0.0) {
+    if (!k.multi && knob<Knob::bicgMergedCheck>() != 0.0) {
         // single rank: the mid-turn check moves behind the second SpMV and shares its finaliser (8 launches
         // per turn instead of 9; when it stops the solve that SpMV ran for nothing)
         launch_bicg_step2(st, n, d_r.p, d_v.p, d_s.p, precond, z, d_part2.p, s);
@@ -1128,7 +1127,7 @@ int ogl_solver::krylov_loop(KrylovRun &k)
     // 286.1 against 285.3 us at 10M rows: the gap between two dependent kernels is the device's dispatch
     // latency, not host launch cost) and stays off by default.
     const bool graphable = !k.gmres && !k.bicg && !k.generic && !k.multi && k.prof_cap == 0 &&
-                           prop("hipGraph", fused ? 1.0 : 0.0) != 0.0;
+                           knob<Knob::hipGraph>(fused ? 1.0 : 0.0) != 0.0;
     // (on by default for the folded 2- / 3-launch turns of small systems, where the host's launch rate shows: 32^3
     //  15.1 -> 13.0 us per 3-launch turn, 64^3 17.3 -> 16.7; the 5-launch turn of larger systems measures the same either way;
     //  a batch of 16 turns leaves the two p buffers of the 2-launch turn where it found them)
@@ -1183,7 +1182,7 @@ int ogl_solver::krylov_loop(KrylovRun &k)
             }
             ledger::created(ledger::GRAPH_EXEC);
             cg_graph_key = key;
-            props["hipGraphCaptures"] = prop("hipGraphCaptures", 0.0) + 1.0;
+            set_knob<Knob::hipGraphCaptures>(knob<Knob::hipGraphCaptures>() + 1.0);
         }
         OGL_HIP_CHECK(hipGraphLaunch(cg_graph, st));
         k.enq += batch;
@@ -1235,7 +1234,7 @@ int ogl_solver::krylov_finish(KrylovRun &k, ogl_perf *perf)
     if (k.folded() && !fin.stop) return fail(OGL_ERR_STATE, "criterion did not stop within maxIter + frequency");
     if (fin.comm_error && !k.multi && k.lead.box)
         return fail(OGL_ERR_STATE, "leader finalisation timed out: the sums of a turn were not published within "
-                    "leadTimeoutS = %g s (check %d)", prop("leadTimeoutS", 10.0), fin.iter);
+                    "leadTimeoutS = %g s (check %d)", knob<Knob::leadTimeoutS>(), fin.iter);
     if (fin.comm_error)
         return fail(OGL_ERR_COMM, "peer all-reduce timed out: a rank did not take part (check %d)",
                     fin.iter);
@@ -1297,7 +1296,7 @@ int ogl_solver::krylov_finish(KrylovRun &k, ogl_perf *perf)
     // store_number_of_iterations + relative residual-evaluation cost (lduLduBase.H:286-293);
     // both are stored as labels, i.e. truncated (common.C:75-76,117-123).  The stored count is the
     // raw number of checks for every solver (GKOBiCGStab.H:98-103).
-    props[k.is_final ? "prevSolveIters_final" : "prevSolveIters"] = fin.iter;
+    k.is_final ? set_knob<Knob::prevSolveIters_final>(fin.iter) : set_knob<Knob::prevSolveIters>(fin.iter);
     const double time_per_iter = t_solve * 1e3 / std::max(perf->n_iterations, 1);
     const double res_norm_time = std::max(1e-3, (double)chk_ms * 1e3);
     double rel_cost = time_per_iter / res_norm_time;
@@ -1310,7 +1309,7 @@ int ogl_solver::krylov_finish(KrylovRun &k, ogl_perf *perf)
         OGL_HIP_CHECK(hipStreamSynchronize(st));
         OGL_HIP_CHECK(hipMemcpy(&rel_cost, sums_ptr(s), sizeof(double), hipMemcpyDeviceToHost));
     }
-    props["_prev_solve"] = std::floor(rel_cost);
+    set_knob<Knob::_prev_solve>(std::floor(rel_cost));
     return OGL_OK;
 }
 

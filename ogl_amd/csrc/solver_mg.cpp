@@ -33,51 +33,31 @@ int read_i32(MultigridPart &M, const int32_t *dev, int32_t *host, hipStream_t st
     return OGL_OK;
 }
 
-// keyword `key`: an integral value in [lo, hi]
-int check_whole(const char *key, double v, int lo, int hi)
-{
-    if (v >= (double)lo && v <= (double)hi && v == (double)(int)v) return OGL_OK;
-    return fail(OGL_ERR_INVALID, "preconditioner Multigrid: %s %g outside [%d, %d]", key, v, lo, hi);
-}
-
-// smootherSweeps and correctionScale, for whoever sets the hierarchy up and for whoever applies it
-int check_smoother(double sweeps, double scale)
-{
-    OGL_TRY(check_whole("smootherSweeps", sweeps, 1, MG_MAX_SWEEPS));
-    // (a condition, not a tuning value: with an exact coarse solve the correction step I - scale Pi stops contracting at 2)
-    if (!(scale > 0.0 && scale < 2.0))
-        return fail(OGL_ERR_INVALID, "preconditioner Multigrid: correctionScale %g outside (0, 2)", scale);
-    return OGL_OK;
-}
-
 }  // namespace
 
 int ogl_solver::check_multigrid_keywords()
 {
     // (the keywords of the preconditioner's sub-dictionary travel as properties, Preconditioner.H:297-317)
-    if (prop("cycle", 0.0) != 0.0)
+    if (knob<Knob::cycle>() != 0.0)
         return fail(OGL_ERR_UNSUPPORTED, "preconditioner Multigrid: cycle %s is not built (only cycle v)",
-                    prop("cycle", 0.0) == 1.0 ? "w" : "f");
-    if (prop("zeroGuess", 1.0) == 0.0)
+                    knob<Knob::cycle>() == 1.0 ? "w" : "f");
+    if (knob<Knob::zeroGuess>() == 0.0)
         return fail(OGL_ERR_UNSUPPORTED, "preconditioner Multigrid: zeroGuess false is not built");
-    if (prop("maxLevels", 9.0) < 0.0)
-        return fail(OGL_ERR_INVALID, "preconditioner Multigrid: maxLevels %d is negative", (int)prop("maxLevels", 9.0));
-    if (prop("coarseSolverIters", 4.0) < 0.0)
+    if (knob<Knob::maxLevels>() < 0.0)
+        return fail(OGL_ERR_INVALID, "preconditioner Multigrid: maxLevels %d is negative", (int)knob<Knob::maxLevels>());
+    if (knob<Knob::coarseSolverIters>() < 0.0)
         return fail(OGL_ERR_INVALID, "preconditioner Multigrid: coarseSolverIters %d is negative",
-                    (int)prop("coarseSolverIters", 4.0));
-    const double aggregation = prop("aggregation", 0.0);
-    if (aggregation != 0.0 && aggregation != 1.0)
-        return fail(OGL_ERR_INVALID, "preconditioner Multigrid: aggregation %g is neither 0 (pgm) nor 1 (hashed)", aggregation);
-    OGL_TRY(check_whole("aggregatePasses", prop("aggregatePasses", 1.0), 1, MG_MAX_PASSES));
-    OGL_TRY(check_whole("aggregateCaching", prop("aggregateCaching", 0.0), 0, 1000000));
+                    (int)knob<Knob::coarseSolverIters>());
+    OGL_TRY(check_knob(Knob::aggregation));
+    OGL_TRY(check_knob(Knob::aggregatePasses));
+    OGL_TRY(check_knob(Knob::aggregateCaching));
     // (read-only: 1 once this solve's generation turns out to be a refresh -- not where a stored hierarchy is applied as it is)
     props["mgAggregatesReused"] = 0.0;
-    OGL_TRY(check_whole("coarseVisits", prop("coarseVisits", 1.0), 1, MG_MAX_COARSE_VISITS));
-    const double precision = prop("cyclePrecision", 0.0);
-    if (precision != 0.0 && precision != 1.0)
-        return fail(OGL_ERR_INVALID, "preconditioner Multigrid: cyclePrecision %g is neither 0 (double) nor 1 (single)",
-                    precision);
-    return check_smoother(prop("smootherSweeps", 2.0), prop("correctionScale", 1.0));
+    OGL_TRY(check_knob(Knob::coarseVisits));
+    OGL_TRY(check_knob(Knob::cyclePrecision));
+    OGL_TRY(check_knob(Knob::smootherSweeps));
+    // (a condition, not a tuning value: with an exact coarse solve the correction step I - scale Pi stops contracting at 2)
+    return check_knob(Knob::correctionScale);
 }
 
 // This solver's side of an apply of the hierarchy (its own or a stored one): coarseVisits, and how often one apply then
@@ -86,15 +66,16 @@ int ogl_solver::check_multigrid_keywords()
 int ogl_solver::prepare_multigrid_apply()
 {
     const MultigridPart &M = precond_data->mg;
-    mg_coarse_visits = (int)prop("coarseVisits", 1.0);
-    props["coarseVisits"] = (double)mg_coarse_visits;
+    mg_coarse_visits = (int)knob<Knob::coarseVisits>();
+    set_knob<Knob::coarseVisits>((double)mg_coarse_visits);
     // smootherSweeps and correctionScale are the applier's too; check_multigrid_keywords has refused the rest, and an
     // apply never runs with a count the ping-pong of the sweeps was not built for
-    OGL_TRY(check_smoother(prop("smootherSweeps", 2.0), prop("correctionScale", 1.0)));
-    mg_sweeps = (int)prop("smootherSweeps", 2.0);
-    mg_scale = prop("correctionScale", 1.0);
-    props["smootherSweeps"] = (double)mg_sweeps;
-    props["correctionScale"] = mg_scale;
+    OGL_TRY(check_knob(Knob::smootherSweeps));
+    OGL_TRY(check_knob(Knob::correctionScale));
+    mg_sweeps = (int)knob<Knob::smootherSweeps>();
+    mg_scale = knob<Knob::correctionScale>();
+    set_knob<Knob::smootherSweeps>((double)mg_sweeps);
+    set_knob<Knob::correctionScale>(mg_scale);
     // (read-only, of the hierarchy in use: the maps kept for keyword aggregateCaching and the refreshes it has left)
     props["mgKeptBytes"] = (double)M.kept_bytes();
     props["mgAggregateCachingLeft"] = (double)(M.kept_for.valid ? M.kept_left : 0);
@@ -111,7 +92,7 @@ int ogl_solver::prepare_multigrid_apply()
                     mg_coarse_visits, M.n_levels, total, MG_MAX_VISITS_PER_APPLY);
     for (int l = 0; l < M.n_levels; ++l) props["mgVisits" + std::to_string(l)] = visits[(size_t)l];
     // cyclePrecision is the applier's too: a stored hierarchy gets its binary32 twin when a solver first asks for it
-    mg_single = prop("cyclePrecision", 0.0) == 1.0;
+    mg_single = knob<Knob::cyclePrecision>() == 1.0;
     if (mg_single) OGL_TRY(prepare_multigrid_single());
     props["mgCyclePrecisionInUse"] = mg_single ? 1.0 : 0.0;
     return OGL_OK;
@@ -335,18 +316,18 @@ int ogl_solver::mg_caller_numbered_level0(PrecondData &P)
 int ogl_solver::generate_multigrid(PrecondData &P)
 {
     MultigridPart &M = P.mg;
-    const int keep = (int)prop("aggregateCaching", 0.0);
+    const int keep = (int)knob<Knob::aggregateCaching>();
     MultigridPart::KeptFor asking;
     asking.valid = true;
     asking.pat_id = pat_id;
     asking.rows = pat.n_rows;
     asking.nnz = pat.local_nnz;
     asking.own = pat.renumbered();
-    asking.hashed = prop("aggregation", 0.0) == 1.0;
-    asking.passes = (int)prop("aggregatePasses", 1.0);
-    asking.max_levels = (int)prop("maxLevels", 9.0);
-    asking.min_coarse = prop("minCoarseRows", 10.0);
-    M.cg_iters = (int)prop("coarseSolverIters", 4.0);
+    asking.hashed = knob<Knob::aggregation>() == 1.0;
+    asking.passes = (int)knob<Knob::aggregatePasses>();
+    asking.max_levels = (int)knob<Knob::maxLevels>();
+    asking.min_coarse = knob<Knob::minCoarseRows>();
+    M.cg_iters = (int)knob<Knob::coarseSolverIters>();
     M.host_reads = 0;
     const bool refresh = keep > 0 && M.kept_left > 0 && M.kept_for == asking;
     if (refresh) {
@@ -375,7 +356,7 @@ int ogl_solver::refresh_multigrid(PrecondData &P)
         launch_gather_coeffs(st, L0.nnz, M.map0.p, csr(false).vals, L0.dbl.vals.p);
     }
     // (property mgKeepStream 1, measurements: the maps loaded past the caches)
-    const bool stream = prop("mgKeepStream", 0.0) != 0.0;
+    const bool stream = knob<Knob::mgKeepStream>() != 0.0;
     for (int l = 0; l < M.n_levels; ++l) {
         MgLevel &L = *M.levels[(size_t)l];
         const MgCsr A = mg_matrix<double>(L);
@@ -729,7 +710,7 @@ void ogl_solver::apply_multigrid(const double *in, double *out, const DevScalars
     const MultigridPart &M = precond_data->mg;
     // the tail: the levels of at most mgTailRows rows (this solver's own property, also on a stored hierarchy); never
     // more than the kernel's level table and reduction tree hold
-    const double tail_rows = std::min(prop("mgTailRows", (double)MG_TAIL_DEFAULT_ROWS), (double)MG_TAIL_MAX_ROWS);
+    const double tail_rows = std::min(knob<Knob::mgTailRows>(), (double)MG_TAIL_MAX_ROWS);
     mg_tail_first = M.n_levels;
     while (mg_tail_first > 0 && M.n_levels - mg_tail_first < MG_TAIL_MAX_LEVELS &&
            (double)M.levels[(size_t)mg_tail_first - 1]->n <= tail_rows)
@@ -738,7 +719,7 @@ void ogl_solver::apply_multigrid(const double *in, double *out, const DevScalars
     //  it is launched, whatever its size)
     if (mg_single && mg_tail_first < 1) mg_tail_first = 1;
     props["mgTailLevels"] = (double)(M.n_levels - mg_tail_first);
-    props["mgTailRows"] = tail_rows;
+    set_knob<Knob::mgTailRows>(tail_rows);
     MgRun run;
     run.st = reg->stream;
     run.gate = gate;

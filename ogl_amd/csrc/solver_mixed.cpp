@@ -27,11 +27,10 @@ int32_t *word_of(MixedScalars *m, size_t offset) { return reinterpret_cast<int32
 // BJ with maxBlockSize 1.  Anything else with mixedPrecision set is refused, none silently.
 int ogl_solver::mixed_requested(bool *on)
 {
-    *on = prop("mixedPrecision", 0.0) != 0.0;
+    *on = knob<Knob::mixedPrecision>() != 0.0;
     if (!*on) return OGL_OK;
-    const double inner_rel_tol = prop("innerRelTol", 1e-4), inner_max_iter = prop("innerMaxIter", 1000.0);
-    if (!(inner_rel_tol > 0.0 && inner_rel_tol < 1.0))
-        return fail(OGL_ERR_INVALID, "innerRelTol %g outside (0, 1)", inner_rel_tol);
+    OGL_TRY(check_knob(Knob::innerRelTol));
+    const double inner_max_iter = knob<Knob::innerMaxIter>();
     if (!(inner_max_iter >= 1.0)) return fail(OGL_ERR_INVALID, "innerMaxIter %g below 1", inner_max_iter);
     const PrecondKind kind = precond_kind_of(cfg);
     const bool precond_ok = cfg.preconditioner == OGL_PRECOND_NONE || kind == PrecondKind::Jacobi;
@@ -158,8 +157,8 @@ int ogl_solver::run_mixed(ogl_perf *perf)
     crit.max_iter = cfg.max_iter;
     crit.frequency = 1;
     crit.export_res = cfg.export_res;
-    const int inner_max_iter = (int)std::min(prop("innerMaxIter", 1000.0), 2147483647.0);
-    OGL_TRY(mixed_storage(crit, prop("innerRelTol", 1e-4), inner_max_iter));
+    const int inner_max_iter = (int)std::min(knob<Knob::innerMaxIter>(), 2147483647.0);
+    OGL_TRY(mixed_storage(crit, knob<Knob::innerRelTol>(), inner_max_iter));
     MixedScalars *m = mixed.scal.p;
     const float *inv_d = nullptr;
     if (precond) {  // inv_d32 = fl32 of the inverse diagonal the double path would use for this solve
@@ -313,11 +312,11 @@ int ogl_solver::run_mixed(ogl_perf *perf)
     perf->t_solve_ms = t_solve;
     perf->spmv_avg_ms = 0;
     perf->spmv_launches = 0;
-    props[is_final ? "prevSolveIters_final" : "prevSolveIters"] = perf->n_iterations;
+    is_final ? set_knob<Knob::prevSolveIters_final>(perf->n_iterations) : set_knob<Knob::prevSolveIters>(perf->n_iterations);
     const double res_norm_time = std::max(1e-3, (double)chk_ms * 1e3);
     perf->t_res_norm_us = res_norm_time;
     perf->n_global_rows = n_global;
-    props["_prev_solve"] = std::floor(t_solve * 1e3 / std::max(perf->n_iterations, 1) / res_norm_time);
+    set_knob<Knob::_prev_solve>(std::floor(t_solve * 1e3 / std::max(perf->n_iterations, 1) / res_norm_time));
     return OGL_OK;
 }
 
@@ -339,7 +338,7 @@ int ogl_solver::spmv_f32(const float *x, float *y)
     OGL_TRY(mixed_spmv(mixed.p.p, mixed.q.p, nullptr, nullptr));
     // property mixedTimedSpmvs > 0 (measurements only): that many inner SpMVs with the pi partials, as a turn runs them,
     // timed with HIP events -> mixedSpmvUs
-    if (const int timed = (int)prop("mixedTimedSpmvs", 0.0); timed > 0) {
+    if (const int timed = (int)knob<Knob::mixedTimedSpmvs>(); timed > 0) {
         EventPair ev;
         OGL_HIP_CHECK(ev_create(&ev[0]));
         OGL_HIP_CHECK(ev_create(&ev[1]));

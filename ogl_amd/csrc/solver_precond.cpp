@@ -34,7 +34,7 @@ int ogl_solver::generate_preconditioner(PrecondData &P)
 {
     // structures of a renumbered device copy (block-Jacobi blocks, ISAI(spd)'s triangle) in the CALLER's numbering:
     // the reference's operator (property precondCallerNumbering 0 = the backend's numbering, for A/B)
-    const bool caller_numbering = prop("precondCallerNumbering", 1.0) != 0.0;
+    const bool caller_numbering = knob<Knob::precondCallerNumbering>() != 0.0;
     if (P.struct_caller_numbering != caller_numbering) P.struct_pat_id = 0;  // (the switch was flipped: rebuild)
     P.struct_caller_numbering = caller_numbering;
     const PrecondKind kind = precond_kind_of(cfg);
@@ -71,7 +71,7 @@ int ogl_solver::generate_jacobi(PrecondData &P)
     // caller's cells and no same-rank interface adds entries: 1/d from there (216^3: 124 -> ~25 us per generation,
     // 562 MB of CSR values not touched); otherwise from the CSR values through the diagonal positions -- same bits
     const bool from_source = source_diag_valid && d_new_id.n == 0 && pat.local_iface_nnz == 0 &&
-                             d_source.n >= (size_t)pat.diag_start() + (size_t)n && prop("jacobiFromSource", 1.0) != 0.0;
+                             d_source.n >= (size_t)pat.diag_start() + (size_t)n && knob<Knob::jacobiFromSource>() != 0.0;
     props["jacobiFromSourceInUse"] = from_source ? 1.0 : 0.0;
     if (from_source)
         launch_jacobi_generate_diag(st, (int32_t)n, d_source.p + pat.diag_start(), P.bj.values.p);
@@ -109,9 +109,9 @@ int ogl_solver::generate_block_jacobi(PrecondData &P, bool through_perm)
     // block rows stored by device row)
     B.through_perm = through_perm;
     B.perm_pat_id = through_perm ? pat_id : 0;
-    B.by_device_row = through_perm && prop("bjStagedApply", 1.0) == 0.0;
+    B.by_device_row = through_perm && knob<Knob::bjStagedApply>() == 0.0;
     const DevBlockJacobi J = B.view(pat.n_rows, k, through_perm ? d_new_id.p : nullptr, through_perm ? d_old_of.p : nullptr);
-    launch_bj_generate(st, csr(), J, prop("bjGroupLanes", 1.0) != 0.0);
+    launch_bj_generate(st, csr(), J, knob<Knob::bjGroupLanes>() != 0.0);
     return OGL_OK;
 }
 
@@ -131,7 +131,7 @@ int ogl_solver::generate_isai(PrecondData &P, bool caller_numbering)
         ogl_label wide = -1;
         OGL_TRY(download_local_pattern(pat));
         // scratch for the dense systems of the huge rows: batches of rows within a budget (property, bytes)
-        const int64_t budget = (int64_t)(prop("isaiScratchBytes", 2147483648.0) / sizeof(double));
+        const int64_t budget = (int64_t)(knob<Knob::isaiScratchBytes>() / sizeof(double));
         if (!build_isai_structure(pat, spd, cfg.sparsity_power, caller_numbering,
                                   IsaiRowClasses{ISAI_THREAD_ROW, MAX_ISAI_ROW, MAX_ISAI_HUGE_ROW}, budget, S, wide))
             return fail(OGL_ERR_UNSUPPORTED,
@@ -149,7 +149,7 @@ int ogl_solver::generate_isai(PrecondData &P, bool caller_numbering)
         props["isaiWideRows"] = (double)S.wide_rows.size();
         props["isaiHugeRows"] = (double)S.huge_rows.size();
         // (property isaiSortRows 0: W / W^T on the compressed layout only where their own row order qualifies, A/B)
-        const bool sort_w = prop("isaiSortRows", 1.0) != 0.0;
+        const bool sort_w = knob<Knob::isaiSortRows>() != 0.0;
         auto compress = [&](SellDev &d, const std::vector<int32_t> &rp, const std::vector<int32_t> &c) -> int {
             OGL_TRY(d.build(N, rp.data(), c.data(), reg->stager, st));
             if (!d.ready && sort_w) OGL_TRY(d.build(N, rp.data(), c.data(), reg->stager, st, true));
@@ -178,7 +178,7 @@ int ogl_solver::generate_isai(PrecondData &P, bool caller_numbering)
         P.set_structure(pat_id, kind, cfg.sparsity_power);
     }
     launch_isai_generate(st, csr(), spd ? 1 : 0, I.w_row_ptrs.p, I.w_cols.p, I.w_vals.p, I.w_max_row, I.wide_rows.p,
-                         I.n_wide_rows, prop("isaiGroupLanes", 1.0) != 0.0);
+                         I.n_wide_rows, knob<Knob::isaiGroupLanes>() != 0.0);
     // the dense systems of the huge rows live in a scratch of up to isaiScratchBytes that only this generation
     // needs: allocated here, released below (a field's own preconditioner plus the registry-wide cached one would
     // otherwise sit on 2 GiB each for the whole run)
@@ -187,7 +187,7 @@ int ogl_solver::generate_isai(PrecondData &P, bool caller_numbering)
         launch_isai_generate_huge(st, csr(), spd ? 1 : 0, I.w_row_ptrs.p, I.w_cols.p, I.w_vals.p, I.huge_rows.p,
                                   I.huge_off.p, I.huge_batches[bt], I.huge_batches[bt + 1] - I.huge_batches[bt],
                                   I.huge_scratch.p);
-    if (I.n_huge_rows > 0 && prop("isaiKeepScratch", 0.0) == 0.0) {
+    if (I.n_huge_rows > 0 && knob<Knob::isaiKeepScratch>() == 0.0) {
         OGL_HIP_CHECK(hipStreamSynchronize(st));
         I.huge_scratch.release();
     }
@@ -207,8 +207,8 @@ int ogl_solver::generate_factor(PrecondData &P)
     const PrecondKind skind = ic ? PrecondKind::Ic : PrecondKind::Ilu;  // (ILU and IRILU share the factor)
     // keywords of the generating solve (validated in init_preconditioner): recorded in the object, which is applied the
     // way it was generated
-    const bool want_isai = prop("triangularSolves", 0.0) == 1.0 && cfg.preconditioner != OGL_PRECOND_IRILU;
-    const int sweeps = (int)prop("factorSweeps", 0.0);
+    const bool want_isai = knob<Knob::triangularSolves>() == 1.0 && cfg.preconditioner != OGL_PRECOND_IRILU;
+    const int sweeps = (int)knob<Knob::factorSweeps>();
     const int power = cfg.sparsity_power;
     const bool have = P.has_structure(pat_id, skind, 0);
     const bool need_w = want_isai && !(F.w_pat_id == pat_id && F.w_power == power && F.w_ic == ic);
@@ -260,7 +260,7 @@ int ogl_solver::generate_factor(PrecondData &P)
             IsaiPart &W = F.w;
             F.w_pat_id = 0;
             const int32_t N = pat.n_rows;
-            const bool sort_w = prop("isaiSortRows", 1.0) != 0.0;
+            const bool sort_w = knob<Knob::isaiSortRows>() != 0.0;
             auto compress = [&](SellDev &d, const std::vector<int32_t> &rp, const std::vector<int32_t> &c) -> int {
                 d.ready = false;
                 if (!cfg.compress_indices) return OGL_OK;
@@ -304,7 +304,7 @@ int ogl_solver::generate_factor(PrecondData &P)
     } else {
         // runs of levels of at most iluThinRows rows each: one single-workgroup launch per run
         std::vector<int32_t> seg;
-        factor_segments(F.fwd_ptr_h, (int32_t)prop("iluThinRows", 256.0), seg);
+        factor_segments(F.fwd_ptr_h, (int32_t)knob<Knob::iluThinRows>(), seg);
         launch_factor_gather(st, F.nnz, F.map_ptr.p, F.map.p, csr().vals, F.vals.p);
         for (size_t g = 0; g + 2 < seg.size(); g += 3)
             launch_factor_levels(st, V, F.fwd_ptr_h.data(), F.fwd_ptr.p, F.fwd_rows.p, seg[g], seg[g + 1], seg[g + 2] != 0);
@@ -340,7 +340,7 @@ void ogl_solver::apply_factor(const double *in, double *out, const DevScalars *g
     if (F.tri_isai) {
         // keyword triangularSolves isai: y = W_L r, z = W_U y through the product kernels and layouts of ISAI's W / W^T
         // (streamed past the caches exactly when the system matrix is); W lives in the caller's numbering
-        const bool stream_w = props.count("spmvStream") && props.at("spmvStream") == 1.0;
+        const bool stream_w = knob<Knob::spmvStream>() == 1.0;
         const IsaiPart &W = F.w;
         const double *r = in;
         double *y = d_fac_tmp[0].p, *z = rn ? d_fac_tmp[1].p : out;
@@ -409,11 +409,9 @@ void ogl_solver::apply_factor(const double *in, double *out, const DevScalars *g
 // other preconditioner ignores them.
 int ogl_solver::check_factor_keywords()
 {
-    const double tri = prop("triangularSolves", 0.0), sw = prop("factorSweeps", 0.0);
-    if (tri != 0.0 && tri != 1.0)
-        return fail(OGL_ERR_INVALID, "triangularSolves %g is not 0 (exact) or 1 (isai)", tri);
-    if (!(sw >= 0.0 && sw <= 10.0) || sw != std::floor(sw))
-        return fail(OGL_ERR_INVALID, "factorSweeps %g is not an integer in [0, 10]", sw);
+    OGL_TRY(check_knob(Knob::triangularSolves));
+    OGL_TRY(check_knob(Knob::factorSweeps));
+    const double tri = knob<Knob::triangularSolves>();
     if (tri == 1.0 && cfg.preconditioner == OGL_PRECOND_IRILU)
         return fail(OGL_ERR_UNSUPPORTED, "preconditioner IRILU with triangularSolves isai: IRILU has its own sweeps for the "
                     "triangular solves (use IC or ILU)");
@@ -479,7 +477,7 @@ void ogl_solver::apply_preconditioner(const double *in, double *out, const DevSc
         const bool general = P.kind == PrecondKind::Gisai;
         double *w_out = general ? out : d_isai_tmp.p;
         // (W / W^T are streamed past the caches exactly when the system matrix is: one working set, one policy)
-        const bool stream_w = props.count("spmvStream") && props.at("spmvStream") == 1.0;
+        const bool stream_w = knob<Knob::spmvStream>() == 1.0;
         if (cfg.compress_indices && I.w_sell.ready)
             launch_spmv_sell(st, I.w_sell.view(n, stream_w), SPMV_PLAIN, in, nullptr, w_out, general ? last : SpmvDots{}, gate);
         else
@@ -496,10 +494,10 @@ void ogl_solver::apply_preconditioner(const double *in, double *out, const DevSc
         //  generated -- are reached through this solver's permutation)
         const bool perm = pat.renumbered() && (P.bj.through_perm || P.caller_order_blocks());
         const DevBlockJacobi J = P.bj.view(n, P.stride, perm ? d_new_id.p : nullptr, perm ? d_old_of.p : nullptr,
-                                           perm ? (int32_t)prop("bjPermXcdGroup", 0.0) : 0);
+                                           perm ? (int32_t)knob<Knob::bjPermXcdGroup>() : 0);
         if (perm && !P.bj.by_device_row) {
             // (property bjFusedPerm 0: the three-launch form with two staging vectors, for A/B)
-            const bool fused_perm = prop("bjFusedPerm", 1.0) != 0.0 && in != out;
+            const bool fused_perm = knob<Knob::bjFusedPerm>() != 0.0 && in != out;
             launch_bj_apply_staged(st, J, in, out, dot_part, gate, fused_perm ? nullptr : d_bj_tmp0.p,
                                    fused_perm ? nullptr : d_bj_tmp1.p);
             return;
@@ -550,7 +548,7 @@ int ogl_solver::prepare_apply()
         }
         fac_isai_scratch = tri_isai;
         if (pat.renumbered()) OGL_TRY(d_fac_tmp[2].alloc(n, st));
-        const int32_t thin = (int32_t)prop("iluThinRows", 256.0);
+        const int32_t thin = (int32_t)knob<Knob::iluThinRows>();
         factor_segments(P.fac.fwd_ptr_h, thin, fac_seg_fwd);
         factor_segments(P.fac.bwd_ptr_h, thin, fac_seg_bwd);
         int launches = 0;
@@ -604,7 +602,7 @@ int ogl_solver::init_preconditioner()
                     MAX_JACOBI_BLOCK);
     if (is_factor(kind)) OGL_TRY(check_factor_keywords());
     const int stride = kind == PrecondKind::BlockJacobi ? cfg.max_block_size : (isai ? cfg.sparsity_power : 0);
-    const int cache = (int)prop("preconditionerCaching", 0);
+    const int cache = (int)knob<Knob::preconditionerCaching>();
     const bool stored =
         reg->has_cached_precond && reg->cached_precond.matches(kind, (size_t)pat.n_rows, stride);
     // (the store is shared by all fields, Preconditioner.H:357: a stored object whose values live in ANOTHER pattern's
@@ -612,17 +610,17 @@ int ogl_solver::init_preconditioner()
     //  PrecondData::foreign_to)
     const bool foreign = stored && reg->cached_precond.foreign_to(pat_id, pat.renumbered());
     // (property precondTimedApplies > 0, measurements only: the generation and that many applies timed with HIP events)
-    const int timed = (int)prop("precondTimedApplies", 0.0);
+    const int timed = (int)knob<Knob::precondTimedApplies>();
     EventPair tev;
     if (timed > 0) {
         OGL_HIP_CHECK(ev_create(&tev[0]));
         OGL_HIP_CHECK(ev_create(&tev[1]));
     }
     if (stored && cache > 0 && !foreign) {
-        props["preconditionerCaching"] = cache - 1;
+        set_knob<Knob::preconditionerCaching>(cache - 1);
         precond_data = &reg->cached_precond;
     } else {
-        props["preconditionerCaching"] = cfg.caching;
+        set_knob<Knob::preconditionerCaching>(cfg.caching);
         PrecondData &P = stored ? own_precond : reg->cached_precond;
         if (timed > 0) OGL_HIP_CHECK(hipEventRecord(tev[0], reg->stream));
         OGL_TRY(generate_preconditioner(P));

@@ -14,9 +14,8 @@ using namespace ogl;
 int ogl_solver::proj_requested(int *K)
 {
     *K = 0;
-    const double v = prop("guessProjection", 0.0);
-    if (!(v >= 0.0 && v <= (double)PROJ_MAX) || v != std::floor(v))
-        return fail(OGL_ERR_INVALID, "guessProjection %g is not an integer in 0 .. %d", v, PROJ_MAX);
+    OGL_TRY(check_knob(Knob::guessProjection));
+    const double v = knob<Knob::guessProjection>();
     const int n_ranks = reg->comm ? reg->comm->n_ranks : 1;
     if (v != 0.0 && n_ranks > 1)
         return fail(OGL_ERR_UNSUPPORTED, "guessProjection %d runs on one rank: this registry has %d ranks", (int)v, n_ranks);
@@ -31,8 +30,8 @@ int ogl_solver::proj_requested(int *K)
 int ogl_solver::proj_credit_requested(int K, bool mixed_on, bool *credit)
 {
     *credit = false;
-    const double v = prop("guessProjectionCredit", 0.0);
-    if (v != 0.0 && v != 1.0) return fail(OGL_ERR_INVALID, "guessProjectionCredit %g is not 0 or 1", v);
+    OGL_TRY(check_knob(Knob::guessProjectionCredit));
+    const double v = knob<Knob::guessProjectionCredit>();
     if (v == 1.0 && K > 0 && mixed_on)
         return fail(OGL_ERR_UNSUPPORTED,
                     "guessProjectionCredit 1 is not built for mixedPrecision: its outer criterion does not take the credit");
@@ -43,11 +42,8 @@ int ogl_solver::proj_credit_requested(int K, bool mixed_on, bool *credit)
 // Property guessProjectionProducts: 0 (separate, the default: k + 1 launches of the in-loop product) | 1 (onePass)
 int ogl_solver::proj_products_requested(bool *one_pass)
 {
-    const double v = prop("guessProjectionProducts", 0.0);
-    *one_pass = v == 1.0;
-    if (v != 0.0 && v != 1.0)
-        return fail(OGL_ERR_INVALID, "guessProjectionProducts %g is not 0 (separate) or 1 (onePass)", v);
-    return OGL_OK;
+    *one_pass = knob<Knob::guessProjectionProducts>() == 1.0;
+    return check_knob(Knob::guessProjectionProducts);
 }
 
 // Called by the solve between the reset of its scalars and its first check: S0 of the pre-step into the criterion's state,
@@ -61,9 +57,9 @@ void ogl_solver::proj_credit(hipStream_t st, ogl::DevScalars *s)
 // coefficients keeps it (W is formed anew in every solve).  With K > 0 the buffers are sized here, once.
 int ogl_solver::proj_sync(int K)
 {
-    if (prop("guessProjectionReset", 0.0) == 1.0) {
+    if (knob<Knob::guessProjectionReset>() == 1.0) {
         proj.clear();
-        props["guessProjectionReset"] = 0.0;
+        set_knob<Knob::guessProjectionReset>(0.0);
     }
     if (K != proj.K || pat_id != proj.pat_id) proj.clear();
     proj.K = K;
@@ -94,7 +90,7 @@ int ogl_solver::proj_pre_step(int K, bool credit, bool one_pass)
     proj.offered = k;
     proj.launches = 0;
     proj.active = true;
-    proj.timed = k >= 1 && prop("guessProjectionTimed", 0.0) != 0.0;
+    proj.timed = k >= 1 && knob<Knob::guessProjectionTimed>() != 0.0;
     auto mark = [&](int i) -> int {
         if (!proj.timed) return OGL_OK;
         if (!proj.ev[i]) OGL_HIP_CHECK(ev_create(&proj.ev[i]));

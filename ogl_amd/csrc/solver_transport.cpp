@@ -339,7 +339,7 @@ template int ogl_solver::halo_end(int, const PeerHalo &, const float *, float *,
 // peer_connect found two ranks on one device
 bool ogl_solver::peer_safe_wait() const
 {
-    return prop("peerSafeWait", reg->peer_shared_device ? 1.0 : 0.0) != 0.0;
+    return knob<Knob::peerSafeWait>(reg->peer_shared_device ? 1.0 : 0.0) != 0.0;
 }
 
 int ogl_registry::allreduce(double *dev, int n)
