@@ -82,7 +82,17 @@ typedef enum {
      * mgAggregatesReused (1: the generation behind the hierarchy in use was such a refresh; 0 otherwise, also where a
      * stored hierarchy was applied as it is), mgAggregateCachingLeft, mgKeptBytes (device bytes of the kept maps) and
      * mgGenerateHostReads (device-to-host reads of the last generation: 0 for a refresh). */
-    OGL_PRECOND_MULTIGRID = 7
+    OGL_PRECOND_MULTIGRID = 7,
+    /* A fixed polynomial in the Jacobi-scaled local matrix (this build's addition):
+     * z = p(D^-1 A) D^-1 r, p the Chebyshev polynomial of degree chebyshevDegree (4; a whole number in [1, 16]) for the
+     * interval [lambda_max / chebyshevEigRatio, lambda_max] (chebyshevEigRatio 30; inside (1, 1e6)).  lambda_max is the
+     * Gershgorin bound max_i sum_j |a_ij| / |a_ii| of the local matrix, computed on the device, unless chebyshevLambdaMax
+     * (0) is > 0 and replaces it; any other value of the three is OGL_ERR_INVALID naming keyword and value.  An apply is
+     * chebyshevDegree + 1 launches on the whole-matrix half storage (chebyshevFused 1), 2 chebyshevDegree + 1 on every other
+     * layout and with chebyshevFused 0; the bits are the same.  A bound that is not finite or not positive (a zero
+     * diagonal) fails the solve with OGL_ERR_INVALID.  Read-only after a solve: chebyshevLambdaMaxInUse,
+     * chebyshevLambdaMinInUse, chebyshevLaunchesPerApply, chebyshevFusedInUse. */
+    OGL_PRECOND_CHEBYSHEV = 8
 } ogl_precond_kind;
 
 typedef enum { OGL_FORMAT_COO = 0, OGL_FORMAT_CSR = 1, OGL_FORMAT_ELL = 2 } ogl_matrix_format;

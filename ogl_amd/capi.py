@@ -19,6 +19,7 @@ SOLVER_CG, SOLVER_BICGSTAB, SOLVER_GMRES = 0, 1, 2
 PRECOND_NONE, PRECOND_BJ, PRECOND_ISAI, PRECOND_GISAI = 0, 1, 2, 3
 PRECOND_IC, PRECOND_ILU, PRECOND_IRILU = 4, 5, 6
 PRECOND_MULTIGRID = 7
+PRECOND_CHEBYSHEV = 8
 # keywords of the Multigrid sub-dictionary (Preconditioner.H:297-317): they travel as properties; cycle as a number
 # (defaults, ranges and one line each: the table in csrc/properties.hpp, which property_table() reads out)
 MG_KEYWORDS = ("maxLevels", "minCoarseRows", "coarseSolverIters", "cycle", "zeroGuess", "aggregation", "aggregatePasses",
@@ -415,6 +416,15 @@ class Solver:
         """The keyword factorSweeps (0 .. 10; default 0) of IC / ILU / IRILU for the next solves: 0 the exact level-scheduled
         factorisation, N >= 1 the factor from N synchronous fixed-point sweeps."""
         self.set_property("factorSweeps", float(N))
+        return self
+
+    def set_chebyshev(self, degree=None, eig_ratio=None, lambda_max=None):
+        """The keywords of preconditioner Chebyshev for the next solves (None: left as it is): chebyshevDegree (1 .. 16;
+        default 4), chebyshevEigRatio (inside (1, 1e6); default 30: the polynomial is built for [lambda_max / ratio,
+        lambda_max]) and chebyshevLambdaMax (> 0 replaces the Gershgorin bound of D^-1 A; default 0: computed)."""
+        for key, v in (("chebyshevDegree", degree), ("chebyshevEigRatio", eig_ratio), ("chebyshevLambdaMax", lambda_max)):
+            if v is not None:
+                self.set_property(key, float(v))
         return self
 
     def set_guess_projection(self, K):

@@ -45,8 +45,8 @@ struct DevScalars {
     unsigned long long halo_wait_ticks, reduce_wait_ticks;
     uint32_t reduce_waits;
     uint32_t launch_seq;  // leader finalisation (LeadBox): tag of the next leader launch's mailbox words
-    // IC / ILU / IRILU: the factor's breakdown word (PrecondData::f_breakdown), copied here after the last kernel of the
-    // solve so that it comes back with the final scalars
+    // IC / ILU / IRILU: the factor's breakdown word (FactorPart::breakdown), Chebyshev: its table's (ChebTable::breakdown),
+    // copied here after the last kernel of the solve so that it comes back with the final scalars
     int32_t factor_breakdown;
     int32_t pad_;
 };
@@ -705,6 +705,31 @@ void launch_proj_products_sym(hipStream_t st, const DevSym &A, const double *x0,
 // keyword guessProjectionCredit: s->init_res = rec[0] (S0) when a column was kept and S0 is finite and > 0, else 0 -- after
 // launch_reset_scalars and before the solve's first check (criterion_verdict, device_common.hpp)
 void launch_proj_credit(hipStream_t st, const double *rec, DevScalars *s);
+// Preconditioner Chebyshev (kernels_cheb.hip): z = p(D^-1 A) D^-1 r with the Chebyshev polynomial of
+// [lambda_max / ratio, lambda_max].  The table lives in the preconditioner object and the apply's kernels read it through
+// the pointer, never from launch arguments: a regeneration changes the numbers under launches that stay what they were.
+constexpr int CHEB_MAX_DEGREE = 16;
+struct ChebTable {
+    double lambda_max, lambda_min;  // lambda_max: first the running maximum of k_cheb_bound (as its bit pattern)
+    double c0;                      // 1 / theta
+    double a[CHEB_MAX_DEGREE], b[CHEB_MAX_DEGREE];  // step k = 1 .. degree: a[k - 1] = rho_k rho_(k-1), b[k - 1] = 2 rho_k / delta
+    int32_t breakdown, pad_;        // 1: lambda_max is not finite or not positive
+};
+// tab->lambda_max = max over the rows of (sum_j |a_ij|, stored order, from 0) / |a_ii| (not finite: +inf); the caller
+// has zeroed it.  diag_pos: position of each row's diagonal entry (-1: none)
+void launch_cheb_bound(hipStream_t st, const DevCsr &A, const int32_t *diag_pos, ChebTable *tab);
+// one thread: the table for `degree` steps from tab->lambda_max (forced > 0: from that instead) and the ratio
+void launch_cheb_coeffs(hipStream_t st, int32_t n_rows, int32_t degree, double ratio, double forced, ChebTable *tab);
+// z1 = (r w) c0
+void launch_cheb_first(hipStream_t st, int32_t n, const double *r, const double *w, const ChebTable *tab, double *z1,
+                       const DevScalars *gate);
+// One step of the recurrence, z_next = (z + a_k (z - z_prev)) + b_k (w t) with t = r - A z: z_io holds z_prev (k == 1:
+// nothing, z_prev = 0) and receives z_next.  dot_part != nullptr: also the per-chunk partials of r . z_next.
+// launch_cheb_step: t comes from a product kernel; launch_cheb_step_sym: formed here on the half storage (the same bits)
+void launch_cheb_step(hipStream_t st, int32_t n, int32_t k, const double *t, const double *w, const ChebTable *tab,
+                      const double *z, double *z_io, const double *r, double *dot_part, const DevScalars *gate);
+void launch_cheb_step_sym(hipStream_t st, const DevSym &A, int32_t k, const double *r, const double *w, const ChebTable *tab,
+                          const double *z, double *z_io, double *dot_part, const DevScalars *gate);
 // The Krylov basis a GKOGMRES solve works on: one of the two is set (launch_key.hpp hashes it)
 struct GmresBasis {
     const double *V = nullptr;  // basisPrecision double

@@ -184,4 +184,26 @@ constexpr int32_t N_KNOBS = (int32_t)(sizeof(KNOBS) / sizeof(KNOBS[0]));
 
 constexpr const KnobEntry &knob_entry(Knob k) { return KNOBS[(int32_t)k]; }
 
+// The inputs of preconditioner Chebyshev: entries of the same type, read
+// and range-checked through the same code (ogl_solver::keyword<>, check_entry), in a list of their own.  OGL_KNOBS above is
+// what ogl_host_property hands out, and tests/test_property_table.py pins it entry for entry to the call sites'
+// defaults it was transcribed from; this list is not part of that record.
+#define OGL_CHEB_KEYWORDS(X) \
+    X(chebyshevDegree, fixed(4.0), whole(1, CHEB_MAX_DEGREE), false, "Chebyshev: degree of the polynomial, products per apply") \
+    X(chebyshevEigRatio, fixed(30.0), open(1.0, 1e6), false, "Chebyshev: lambda_max / lambda_min of the interval the polynomial is built for") \
+    X(chebyshevLambdaMax, fixed(0.0), none(), false, "Chebyshev: > 0 replaces the Gershgorin bound of D^-1 A (0: computed; negative or not finite: refused)") \
+    X(chebyshevFused, fixed(1.0), none(), false, "Chebyshev on the whole-matrix half storage: product and recurrence in one kernel (0: two launches per step)")
+
+enum class ChebKeyword : int32_t {
+#define OGL_KNOB_ID(name, dflt, domain, written_back, text) name,
+    OGL_CHEB_KEYWORDS(OGL_KNOB_ID)
+#undef OGL_KNOB_ID
+};
+constexpr KnobEntry CHEB_KEYWORDS[] = {
+#define OGL_KNOB_ENTRY(name, dflt, domain, written_back, text) {#name, dflt, domain, written_back, text},
+    OGL_CHEB_KEYWORDS(OGL_KNOB_ENTRY)
+#undef OGL_KNOB_ENTRY
+};
+constexpr const KnobEntry &knob_entry(ChebKeyword k) { return CHEB_KEYWORDS[(int32_t)k]; }
+
 }  // namespace ogl

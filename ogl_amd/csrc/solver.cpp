@@ -266,11 +266,13 @@ double ogl_solver::knob_value(Knob k, double dflt) const
 }
 
 // Every range check of a property: the keyword, the offending value, what is allowed.
-int ogl_solver::check_knob(Knob k) const
+int ogl_solver::check_knob(Knob k) const { return check_entry(knob_entry(k)); }
+
+int ogl_solver::check_entry(const KnobEntry &e) const
 {
-    const KnobEntry &e = knob_entry(k);
     const KnobDomain &d = e.domain;
-    const double v = knob_value(k, e.dflt.value);
+    const auto it = props.find(e.name);
+    const double v = it == props.end() ? e.dflt.value : it->second;
     if (d.type == KnobDomain::None) return OGL_OK;
     if (d.type == KnobDomain::Open ? v > d.lo && v < d.hi : v >= d.lo && v <= d.hi && v == std::floor(v)) return OGL_OK;
     char range[64];
@@ -321,6 +323,7 @@ double ogl_solver::turn_extra_bytes() const
     // Multigrid: the coarse matrices (12 bytes per entry, about half the fine level's entries in all) and the fine level's
     // inverse diagonal, aggregates and three vectors
     if (cfg.preconditioner == OGL_PRECOND_MULTIGRID) extra += 6.0 * nnz + 36.0 * N;
+    if (cfg.preconditioner == OGL_PRECOND_CHEBYSHEV) extra += 8.0 * N;  // 1 / d (the second iterate: the temporary below)
     if (cfg.preconditioner != OGL_PRECOND_NONE && !(cfg.preconditioner == OGL_PRECOND_BJ && cfg.max_block_size == 1))
         extra += 16.0 * N;                                                      // materialised z (and the ISAI temporary)
     if (cfg.solver == OGL_SOLVER_BICGSTAB) extra += 32.0 * N;

@@ -84,7 +84,7 @@ struct MgWide {
 
 // The preconditioner kinds.  precond_kind_of is the only place that turns the configuration (the public OGL_PRECOND_*
 // value + maxBlockSize) into one, precond_name the only place that holds the names the error messages use.
-enum class PrecondKind { None, Jacobi, BlockJacobi, Isai, Gisai, Ic, Ilu, Irilu, Multigrid };
+enum class PrecondKind { None, Jacobi, BlockJacobi, Isai, Gisai, Ic, Ilu, Irilu, Multigrid, Chebyshev };
 inline PrecondKind precond_kind_of(const ogl_config &cfg)  // (None also for a value that is not built)
 {
     switch (cfg.preconditioner) {
@@ -95,12 +95,13 @@ inline PrecondKind precond_kind_of(const ogl_config &cfg)  // (None also for a v
     case OGL_PRECOND_ILU: return PrecondKind::Ilu;
     case OGL_PRECOND_IRILU: return PrecondKind::Irilu;
     case OGL_PRECOND_MULTIGRID: return PrecondKind::Multigrid;
+    case OGL_PRECOND_CHEBYSHEV: return PrecondKind::Chebyshev;
     default: return PrecondKind::None;
     }
 }
 inline const char *precond_name(PrecondKind k)
 {
-    static const char *const names[] = {"none", "BJ", "BJ", "ISAI", "GISAI", "IC", "ILU", "IRILU", "Multigrid"};
+    static const char *const names[] = {"none", "BJ", "BJ", "ISAI", "GISAI", "IC", "ILU", "IRILU", "Multigrid", "Chebyshev"};
     return names[(int)k];
 }
 inline bool is_isai(PrecondKind k) { return k == PrecondKind::Isai || k == PrecondKind::Gisai; }
@@ -331,6 +332,20 @@ struct MultigridPart {
     }
 };
 
+// Chebyshev: 1 / diagonal (n_rows + 2, scalar Jacobi's bits), the table of the recurrence with the
+// breakdown word (ChebTable, kernels.hpp), and the degree the table was written for.  w belongs to the generating
+// pattern's device numbering, like scalar Jacobi's inverse diagonal.
+struct ChebPart {
+    DevBuf<double> w;
+    DevBuf<ChebTable> table;
+    int degree = 0;
+    void release()
+    {
+        w.release();
+        table.release();
+    }
+};
+
 // A generated preconditioner ("Cached_preconditinoner" holds one of these, Preconditioner.H:357): what is common to all
 // kinds, and one part per family of kinds.  All parts are present at all times and the parts of the OTHER kinds are
 // NOT released when the object changes kind: the store is registry-wide, so a case with ISAI on p and block Jacobi on
@@ -339,13 +354,15 @@ struct MultigridPart {
 struct PrecondData {
     PrecondKind kind = PrecondKind::None;
     size_t n_rows = 0;
-    int stride = 0;  // block Jacobi: maxBlockSize; ISAI / GISAI: sparsityPower
+    int stride = 0;  // block Jacobi: maxBlockSize; ISAI / GISAI: sparsityPower; Chebyshev: chebyshevDegree
     BlockJacobiPart bj;
     IsaiPart isai;
     FactorPart fac;
     MultigridPart mg;
+    ChebPart cheb;
     void release()
     {
+        cheb.release();
         bj.release();
         isai.release();
         fac.release();
@@ -355,6 +372,7 @@ struct PrecondData {
     bool is_isai() const { return ogl::is_isai(kind); }
     bool factor() const { return is_factor(kind); }
     bool multigrid() const { return kind == PrecondKind::Multigrid; }
+    bool chebyshev() const { return kind == PrecondKind::Chebyshev; }
     uint64_t serial = 0;  // new value with every generation (an applier checks it still holds what it adopted)
     // the pattern-only part (block pointers / W and W^T patterns / the factor's structure / Multigrid's level 0) is kept
     // for as long as it was derived from the same sparsity pattern: only the values are regenerated per solve
@@ -392,7 +410,7 @@ struct PrecondData {
     // May a solver with pattern `id` (renumbered or not) apply this object?  Own pattern: always.  Another pattern:
     //
     //   kind                                         generator renumbered   applier renumbered   ->
-    //   Jacobi, ISAI, GISAI                          yes                    any                  foreign
+    //   Jacobi, ISAI, GISAI, Chebyshev               yes                    any                  foreign
     //                                                no                     yes                  foreign
     //                                                no                     no                   own
     //   block Jacobi, block-major in caller's order  any                    any                  own (through the applier's permutation)
@@ -639,6 +657,9 @@ struct ogl_solver {
     ogl::DevBuf<double> d_gs_part, d_gs_h;
     ogl::DevBuf<double> d_isai_tmp;                     // ISAI(spd): W r before W^T
     ogl::DevBuf<double> d_fac_tmp[3];  // IC / ILU / IRILU: vectors in the caller's order, IRILU's iterates
+    // Chebyshev: [0] the second iterate of the recurrence, [1] t = r - A z of the unfused step (held only while it runs)
+    ogl::DevBuf<double> d_cheb_tmp[2];
+    bool cheb_fused = false;  // this solver's applies run k_cheb_step_sym (prepare_apply: chebyshevFused on SpmvLayout::Sym)
     // Multigrid: generation of the hierarchy (per-round and per-level sizes are the only host round trips) and one V-cycle
     // (keyword aggregateCaching: generate_multigrid is a refresh -- the values under the aggregates P holds, no host round
     //  trip -- where P's record allows it, else the full generation)
@@ -730,13 +751,27 @@ struct ogl_solver {
     // generate_preconditioner dispatches on the kind; each generator: pattern-only part if the object does not hold it
     // for this pattern, then the values (generate_multigrid: above)
     int generate_preconditioner(ogl::PrecondData &P);
+    // PrecondData::stride of a kind under this solver's keywords: what a stored object must match to be adopted
+    int precond_stride(ogl::PrecondKind kind) const
+    {
+        if (kind == ogl::PrecondKind::BlockJacobi) return cfg.max_block_size;
+        if (ogl::is_isai(kind)) return cfg.sparsity_power;
+        return kind == ogl::PrecondKind::Chebyshev ? (int)keyword<ogl::ChebKeyword::chebyshevDegree>() : 0;
+    }
     int generate_jacobi(ogl::PrecondData &P);
+    int generate_inv_diag(ogl::DevBuf<double> &inv_diag);  // 1 / d of the device copy (scalar Jacobi, Chebyshev's w)
+    int generate_chebyshev(ogl::PrecondData &P);
     int generate_block_jacobi(ogl::PrecondData &P, bool through_perm);
     int generate_isai(ogl::PrecondData &P, bool caller_numbering);
     int generate_factor(ogl::PrecondData &P);
     int prepare_apply();  // this solver's scratch and launch schedule for applies of precond_data
     void apply_factor(const double *in, double *out, const ogl::DevScalars *gate, double *dot_part);
+    void apply_chebyshev(const double *in, double *out, const ogl::DevScalars *gate, double *dot_part);
     int check_factor_breakdown(int32_t word);
+    // the preconditioner's breakdown word, where the kind in use has one: the address the final scalars take it from
+    const int32_t *precond_breakdown_word() const;
+    int check_chebyshev_breakdown(int32_t word);  // also reads the bounds in use back for the reports
+    int check_chebyshev_keywords();  // chebyshevDegree, chebyshevEigRatio, chebyshevLambdaMax
     int check_factor_keywords();  // keywords triangularSolves and factorSweeps: validation, and IRILU + isai refused
     // out = M^-1 in for every kind (the Krylov loops fuse scalar Jacobi through `precond` instead); dot_part != nullptr:
     // also the per-chunk partials of sum_i in_i * out_i (CG's rho), out of the same kernel where the kind has one
@@ -832,6 +867,13 @@ struct ogl_solver {
         props[ogl::knob_entry(K).name] = v;
     }
     int check_knob(ogl::Knob k) const;  // the current value against the table's domain: OGL_ERR_INVALID, one phrasing
+    int check_entry(const ogl::KnobEntry &e) const;  // ... of any entry (check_knob; the Chebyshev keywords)
+    template <ogl::ChebKeyword K>
+    double keyword() const  // an input of preconditioner Chebyshev (properties.hpp, OGL_CHEB_KEYWORDS)
+    {
+        const auto it = props.find(ogl::knob_entry(K).name);
+        return it == props.end() ? ogl::knob_entry(K).dflt.value : it->second;
+    }
     // ogl_solver_set_matrix_like: the solver whose device copy of upper / lower this set_matrix may take (only during
     // that call), and what THIS solver's copy was uploaded from (host arrays + sampled checksum) for a later taker
     const ogl_solver *share_from = nullptr;

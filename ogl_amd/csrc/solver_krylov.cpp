@@ -1223,14 +1223,14 @@ int ogl_solver::krylov_finish(KrylovRun &k, ogl_perf *perf)
         k.cur ^= 1;
     }
     DevScalars *fin_s = bicg_fold ? k.slot_s[k.cur] : (fused ? s2 : s);
-    if (precond_data && precond_data->factor())  // (the factor's breakdown word travels with the final scalars)
-        OGL_HIP_CHECK(hipMemcpyAsync(&fin_s->factor_breakdown, precond_data->fac.breakdown.p, sizeof(int32_t),
-                                     hipMemcpyDeviceToDevice, st));
+    if (const int32_t *word = precond_breakdown_word())  // (the preconditioner's breakdown word travels with the final scalars)
+        OGL_HIP_CHECK(hipMemcpyAsync(&fin_s->factor_breakdown, word, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     OGL_HIP_CHECK(hipStreamSynchronize(st));
     OGL_HIP_CHECK(hipGetLastError());
     DevScalars fin;
     OGL_HIP_CHECK(hipMemcpy(&fin, fin_s, sizeof(fin), hipMemcpyDeviceToHost));
     OGL_TRY(check_factor_breakdown(fin.factor_breakdown));  // (IC / ILU / IRILU: a broken-down factor fails the solve)
+    OGL_TRY(check_chebyshev_breakdown(fin.factor_breakdown));  // (Chebyshev: a bound that is not finite and positive)
     if (k.folded() && !fin.stop) return fail(OGL_ERR_STATE, "criterion did not stop within maxIter + frequency");
     if (fin.comm_error && !k.multi && k.lead.box)
         return fail(OGL_ERR_STATE, "leader finalisation timed out: the sums of a turn were not published within "

@@ -1,8 +1,9 @@
 // solver_precond.cpp -- the preconditioners other than Multigrid (solver_mg.cpp), Preconditioner.H:47-258,353-431:
 //   * generate_preconditioner: the dispatch on the kind with the common tail (serial, numbering record), and one
-//     generator per family -- generate_jacobi, generate_block_jacobi, generate_isai, generate_factor -- each laid out as
+//     generator per family -- generate_jacobi, generate_block_jacobi, generate_isai, generate_factor, generate_chebyshev --
+//     each laid out as
 //     "pattern-only part if the object does not hold it for this pattern, then the values"
-//   * apply_preconditioner (every kind) with apply_factor, and check_factor_breakdown
+//   * apply_preconditioner (every kind) with apply_factor and apply_chebyshev, and the breakdown checks
 //   * prepare_apply: the applying solver's scratch vectors and launch schedule
 //   * init_preconditioner: validate -> caching rule -> generate or adopt -> prepare_apply -> timed applies
 //   * precond_current
@@ -49,10 +50,11 @@ int ogl_solver::generate_preconditioner(PrecondData &P)
     // Pgm + Multigrid (Preconditioner.H:259-341) on the local matrix in the caller's numbering; the aggregates depend on
     // the values, so nothing of it is pattern-only (solver_mg.cpp)
     case PrecondKind::Multigrid: OGL_TRY(generate_multigrid(P)); break;
+    case PrecondKind::Chebyshev: OGL_TRY(generate_chebyshev(P)); break;
     case PrecondKind::None: return fail(OGL_ERR_UNSUPPORTED, "preconditioner kind %d is not built", cfg.preconditioner);
     }
     P.kind = kind;
-    P.stride = kind == PrecondKind::BlockJacobi ? cfg.max_block_size : (is_isai(kind) ? cfg.sparsity_power : 0);
+    P.stride = precond_stride(kind);
     P.n_rows = (size_t)pat.n_rows;
     static uint64_t serials = 0;
     P.serial = ++serials;
@@ -62,11 +64,13 @@ int ogl_solver::generate_preconditioner(PrecondData &P)
 }
 
 // scalar Jacobi: 1 / diag
-int ogl_solver::generate_jacobi(PrecondData &P)
+int ogl_solver::generate_jacobi(PrecondData &P) { return generate_inv_diag(P.bj.values); }
+
+int ogl_solver::generate_inv_diag(DevBuf<double> &inv_diag)
 {
     hipStream_t st = reg->stream;
     const size_t n = (size_t)pat.n_rows;
-    OGL_TRY(P.bj.values.alloc(n + 2, st));
+    OGL_TRY(inv_diag.alloc(n + 2, st));
     // the diagonal sits contiguous in the staged source of the last coefficient update when the device rows are the
     // caller's cells and no same-rank interface adds entries: 1/d from there (216^3: 124 -> ~25 us per generation,
     // 562 MB of CSR values not touched); otherwise from the CSR values through the diagonal positions -- same bits
@@ -74,10 +78,62 @@ int ogl_solver::generate_jacobi(PrecondData &P)
                              d_source.n >= (size_t)pat.diag_start() + (size_t)n && knob<Knob::jacobiFromSource>() != 0.0;
     props["jacobiFromSourceInUse"] = from_source ? 1.0 : 0.0;
     if (from_source)
-        launch_jacobi_generate_diag(st, (int32_t)n, d_source.p + pat.diag_start(), P.bj.values.p);
+        launch_jacobi_generate_diag(st, (int32_t)n, d_source.p + pat.diag_start(), inv_diag.p);
     else
-        launch_jacobi_generate_pos(st, csr(), d_diag_pos.p, P.bj.values.p);
+        launch_jacobi_generate_pos(st, csr(), d_diag_pos.p, inv_diag.p);
     return OGL_OK;
+}
+
+// Chebyshev: w = 1 / d as scalar Jacobi forms it, the Gershgorin bound of D^-1 A over the device CSR
+// copy unless chebyshevLambdaMax replaces it, and the table of the recurrence -- three launches, no device-to-host read.
+// The keywords were validated in init_preconditioner (check_chebyshev_keywords).
+int ogl_solver::generate_chebyshev(PrecondData &P)
+{
+    hipStream_t st = reg->stream;
+    ChebPart &C = P.cheb;
+    OGL_TRY(generate_inv_diag(C.w));
+    OGL_TRY(C.table.alloc(1, st));
+    const double forced = keyword<ChebKeyword::chebyshevLambdaMax>();
+    OGL_HIP_CHECK(hipMemsetAsync(C.table.p, 0, sizeof(ChebTable), st));
+    if (!(forced > 0.0)) launch_cheb_bound(st, csr(), d_diag_pos.p, C.table.p);
+    C.degree = (int)keyword<ChebKeyword::chebyshevDegree>();
+    launch_cheb_coeffs(st, pat.n_rows, C.degree, keyword<ChebKeyword::chebyshevEigRatio>(), forced, C.table.p);
+    return OGL_OK;
+}
+
+int ogl_solver::check_chebyshev_keywords()
+{
+    OGL_TRY(check_entry(knob_entry(ChebKeyword::chebyshevDegree)));
+    OGL_TRY(check_entry(knob_entry(ChebKeyword::chebyshevEigRatio)));
+    const double forced = keyword<ChebKeyword::chebyshevLambdaMax>();
+    if (!(forced >= 0.0) || !std::isfinite(forced))
+        return fail(OGL_ERR_INVALID, "chebyshevLambdaMax %g is not 0 (the bound is computed) or a finite number > 0", forced);
+    return OGL_OK;
+}
+
+// z^1 = (r w) c0, then `degree` steps z^(k+1) = (z^k + a_k (z^k - z^(k-1))) + b_k (w (r - A_loc z^k)), z^(k+1) written over
+// z^(k-1): the iterates alternate between `out` and one scratch vector, assigned so that the last one lands in `out`.
+// Fused (this solver's in-loop layout is the whole-matrix half storage): one launch per step; else the residual product
+// of the layout in use, local part only, into a second scratch vector and the elementwise step behind it.
+void ogl_solver::apply_chebyshev(const double *in, double *out, const DevScalars *gate, double *dot_part)
+{
+    hipStream_t st = reg->stream;
+    const ChebPart &C = precond_data->cheb;
+    const int32_t n = pat.n_rows;
+    const int degree = C.degree;
+    double *odd = degree % 2 == 0 ? out : d_cheb_tmp[0].p, *even = degree % 2 == 0 ? d_cheb_tmp[0].p : out;  // z^1, z^3, .. | z^2, ..
+    launch_cheb_first(st, n, in, C.w.p, C.table.p, odd, gate);
+    for (int k = 1; k <= degree; ++k) {
+        const double *z = k % 2 ? odd : even;
+        double *z_io = k % 2 ? even : odd;
+        double *part = k == degree ? dot_part : nullptr;
+        if (cheb_fused) {
+            launch_cheb_step_sym(st, sym(), k, in, C.w.p, C.table.p, z, z_io, part, gate);
+        } else {
+            spmv_on(spmv_layout, SPMV_RESIDUAL, z, in, d_cheb_tmp[1].p, SpmvDots{}, gate);
+            launch_cheb_step(st, n, k, d_cheb_tmp[1].p, C.w.p, C.table.p, z, z_io, in, part, gate);
+        }
+    }
 }
 
 // Jacobi factory with max_block_size = maxBlockSize, skip_sorting (Preconditioner.H:100-104)
@@ -420,6 +476,29 @@ int ogl_solver::check_factor_keywords()
     return OGL_OK;
 }
 
+// where the final scalars take the breakdown word of the preconditioner in use from (nullptr: the kind has none)
+const int32_t *ogl_solver::precond_breakdown_word() const
+{
+    if (!precond_data) return nullptr;
+    if (precond_data->factor()) return precond_data->fac.breakdown.p;
+    if (precond_data->chebyshev()) return &precond_data->cheb.table.p->breakdown;
+    return nullptr;
+}
+
+// Chebyshev: a bound that is not finite or not positive (a zero diagonal) fails the solve; `word` as it came back with the
+// final scalars.  The solve is over: the bounds in use are read back for the reports here, not in the generation.
+int ogl_solver::check_chebyshev_breakdown(int32_t word)
+{
+    if (!precond_data || !precond_data->chebyshev()) return OGL_OK;
+    double bounds[2] = {0.0, 0.0};
+    OGL_HIP_CHECK(hipMemcpy(bounds, precond_data->cheb.table.p, sizeof(bounds), hipMemcpyDeviceToHost));
+    props["chebyshevLambdaMaxInUse"] = bounds[0];
+    props["chebyshevLambdaMinInUse"] = bounds[1];
+    if (word == 0) return OGL_OK;
+    return fail(OGL_ERR_INVALID, "preconditioner Chebyshev: the bound lambda_max = %g of D^-1 A of the local matrix is not "
+                "finite and positive (a zero diagonal entry?)", bounds[0]);
+}
+
 // a zero (ILU) / non-positive (IC) pivot of the factor in use: the solve fails instead of handing out NaN.  `word` = the
 // factor's breakdown word as it came back with the final scalars.  Several ranks: a breakdown on any rank fails every rank
 // (its NaN reaches the others through the all-reduced dots).
@@ -471,6 +550,7 @@ void ogl_solver::apply_preconditioner(const double *in, double *out, const DevSc
     case PrecondKind::Ilu:
     case PrecondKind::Irilu: apply_factor(in, out, gate, dot_part); return;
     case PrecondKind::Multigrid: apply_multigrid(in, out, gate, dot_part); return;
+    case PrecondKind::Chebyshev: apply_chebyshev(in, out, gate, dot_part); return;
     case PrecondKind::Isai:
     case PrecondKind::Gisai: {  // one or two SpMVs
         const IsaiPart &I = P.isai;
@@ -521,6 +601,15 @@ int ogl_solver::prepare_apply()
     // (Multigrid's vectors in the caller's order belong to the hierarchy; coarseVisits and its guard are this solver's)
     case PrecondKind::Multigrid: OGL_TRY(prepare_multigrid_apply()); break;
     case PrecondKind::Jacobi: precond = P.bj.values.p; break;
+    case PrecondKind::Chebyshev:
+        // the second iterate; the unfused step's t = r - A z (released again when this solver's applies run fused)
+        cheb_fused = keyword<ChebKeyword::chebyshevFused>() != 0.0 && spmv_layout == SpmvLayout::Sym;
+        OGL_TRY(d_cheb_tmp[0].alloc(n, st));
+        if (cheb_fused) d_cheb_tmp[1].release();
+        else OGL_TRY(d_cheb_tmp[1].alloc(n, st));
+        props["chebyshevFusedInUse"] = cheb_fused ? 1.0 : 0.0;
+        props["chebyshevLaunchesPerApply"] = (double)(cheb_fused ? P.cheb.degree + 1 : 2 * P.cheb.degree + 1);
+        break;
     case PrecondKind::Isai: OGL_TRY(d_isai_tmp.alloc(n, st)); break;  // W r before W^T
     case PrecondKind::BlockJacobi:
         // the staged apply's two vectors in the caller's order
@@ -601,7 +690,8 @@ int ogl_solver::init_preconditioner()
         return fail(OGL_ERR_INVALID, "BJ maxBlockSize %d outside [1, %d]", cfg.max_block_size,
                     MAX_JACOBI_BLOCK);
     if (is_factor(kind)) OGL_TRY(check_factor_keywords());
-    const int stride = kind == PrecondKind::BlockJacobi ? cfg.max_block_size : (isai ? cfg.sparsity_power : 0);
+    if (kind == PrecondKind::Chebyshev) OGL_TRY(check_chebyshev_keywords());
+    const int stride = precond_stride(kind);
     const int cache = (int)knob<Knob::preconditionerCaching>();
     const bool stored =
         reg->has_cached_precond && reg->cached_precond.matches(kind, (size_t)pat.n_rows, stride);
