@@ -1807,6 +1807,12 @@ bool factor_isai_pattern(const FactorStructure &F, int power, int max_row, std::
         w_row_ptrs[(size_t)i + 1] = (int32_t)w_cols.size();
     }
     transpose_pattern(N, w_row_ptrs, w_cols, t_row_ptrs, t_cols, t_map);
+    // (W_U has the transposed pattern and the same bound: a row coupled to many LATER rows is narrow in W_L and wide here)
+    for (int32_t i = 0; i < N; ++i)
+        if (t_row_ptrs[(size_t)i + 1] - t_row_ptrs[(size_t)i] > max_row) {
+            first_wide_row = i;
+            return false;
+        }
     return true;
 }
 

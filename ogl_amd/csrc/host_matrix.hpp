@@ -292,7 +292,8 @@ void build_factor_gather_lists(const FactorStructure &F, std::vector<int32_t> &g
                                std::vector<int32_t> &gs_b);
 // Keyword triangularSolves isai: the pattern of W_L = the `power`-th power of the factor's lower-triangle pattern, the
 // diagonal included (rows ascending by column, the diagonal last), and its transpose (the pattern of W_U) with
-// t_map = position in W_L.  false (first_wide_row set): a row would get more than max_row entries.
+// t_map = position in W_L.  false (first_wide_row set): a row of W_L or, failing that, of W_U would get more than max_row
+// entries.
 bool factor_isai_pattern(const FactorStructure &F, int power, int max_row, std::vector<int32_t> &w_row_ptrs,
                          std::vector<int32_t> &w_cols, std::vector<int32_t> &t_row_ptrs, std::vector<int32_t> &t_cols,
                          std::vector<int32_t> &t_map, ogl_label &first_wide_row);

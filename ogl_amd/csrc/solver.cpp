@@ -1368,17 +1368,19 @@ int ogl_solver::set_matrix(const ogl_ldu_view &ldu)
         // polyhedral mesh) of a size where the SpMV is not launch-bound: the CSR-stream kernel gets its packed
         // columns, and the candidates are timed once per pattern (compress_indices 2: no timing, the first that is
         // ready of the compressed copy and the packed columns runs)
-        const bool big = pat.n_rows >= SPMV_TUNE_MIN_ROWS;
+        // (property spmvForceLayout 0 | 1 | 2: CSR-stream | compressed | packed columns whatever the timing says -- how
+        //  the parity tests reach a layout on a pattern where another one wins.  A forced layout also counts below the
+        //  tuning size, and 2 builds the packed columns next to a compressed copy of 8-bit codes: how those tests reach
+        //  the packed columns on a system of a few rows)
+        const int forced = (int)knob<Knob::spmvForceLayout>();
+        const bool big = pat.n_rows >= SPMV_TUNE_MIN_ROWS || (forced >= 0 && forced < 3);
         const bool irregular_sell = sell_dev.ready && sell_dev.irregular;
-        if (big && !s21_dev.tried && (irregular_sell || !sell_dev.ready))
+        if (big && !s21_dev.tried && (irregular_sell || !sell_dev.ready || forced == 2))
             OGL_TRY(s21_dev.build(pat.n_rows, pat.local_nnz, d_row_ptrs.p, d_cols.p, st, props));
         if (big && cfg.compress_indices == 1 && !layout_tuned && (irregular_sell || s21_dev.ready)) {
             std::vector<SpmvLayout> cand{SpmvLayout::Csr};
             if (sell_dev.ready) cand.push_back(SpmvLayout::Sell);
             if (s21_dev.ready) cand.push_back(SpmvLayout::Csr21);
-            // (property spmvForceLayout 0 | 1 | 2: CSR-stream | compressed | packed columns whatever the timing says -- how
-            //  the parity tests reach a layout on a pattern where another one wins)
-            const int forced = (int)knob<Knob::spmvForceLayout>();
             const SpmvLayout by_force[3] = {SpmvLayout::Csr, SpmvLayout::Sell, SpmvLayout::Csr21};
             SpmvLayout win;
             OGL_TRY(tune_spmv_layouts(cand, forced >= 0 && forced < 3 ? &by_force[forced] : nullptr, &win));

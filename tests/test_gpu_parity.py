@@ -265,7 +265,7 @@ def test_preconditioner_caching_rules(reg, oracle):
         r.close()
 
 
-# the kinds in the order the walk visits them: (field tag, solver, configuration)
+# the kinds in the order the walk visits them: (field tag, solver, configuration[, properties set on the field])
 KIND_WALK = [
     ("jacobi", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_BJ, max_block_size=1)),
     ("bj4", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_BJ, max_block_size=4)),
@@ -275,6 +275,13 @@ KIND_WALK = [
     ("ilu", capi.SOLVER_BICGSTAB, dict(preconditioner=capi.PRECOND_ILU)),
     ("irilu", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_IRILU)),
     ("mg", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_MULTIGRID)),
+    ("cheb", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_CHEBYSHEV), (("chebyshevDegree", 4.0),)),
+    ("ic_isai", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_IC), (("triangularSolves", 1.0),)),
+    ("ilu_swept", capi.SOLVER_BICGSTAB, dict(preconditioner=capi.PRECOND_ILU), (("factorSweeps", 3.0), ("triangularSolves", 1.0))),
+    # (ILU -> IRILU: the hand-over of a shared swept factor, W released in between)
+    ("irilu_swept", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_IRILU), (("factorSweeps", 3.0),)),
+    ("mg_single", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_MULTIGRID),
+     (("cyclePrecision", float(capi.MG_CYCLE_PRECISION["single"])),)),
     ("jacobi", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_BJ, max_block_size=1)),
     ("bj4", capi.SOLVER_CG, dict(preconditioner=capi.PRECOND_BJ, max_block_size=4)),
 ]
@@ -291,34 +298,39 @@ WALK_CASES = [
 def test_one_store_walked_through_every_kind(name, make, renumber, caching):
     """The preconditioner store is registry-wide (Preconditioner.H:357) and keeps the buffers of every kind it has held
     (PrecondData, solver.hpp): one registry, one field per kind, solved in the order Jacobi -> BJ(4) -> ISAI -> GISAI ->
-    IC -> ILU -> IRILU -> Multigrid -> Jacobi -> BJ(4), so that the store changes kind with every solve.  Every solve's
+    IC -> ILU -> IRILU -> Multigrid -> Chebyshev -> IC with `triangularSolves isai` -> ILU swept, isai -> IRILU swept ->
+    Multigrid in single precision -> Jacobi -> BJ(4), so that the store changes kind with every solve.  Every solve's
     x, residual history and counters are bit-equal to the same solve in a fresh registry that has seen nothing else, and
     a second lap allocates nothing (the ledger's deviceBytesInUse stays where the first lap left it).  (updateInitGuess:
     a field's later solves start from the zero vector handed in, like its first, not from the solution left on the device.)"""
     case = make()
     b = synthetic.apply_case(case, synthetic.x_star(case.global_index, case.global_n))
 
-    def solve_in(r, tag, solver, kw):
+    def solve_in(r, tag, solver, kw, props=()):
         s = r.solver(f"walk_{tag}", cg_cfg(solver=solver, max_iter=6, caching=caching, renumber=renumber,
                                             update_init_guess=1, **kw))
+        for key, value in props:
+            s.set_property(key, value)
         s.set_matrix(case)
         x, perf = s.solve(b, np.zeros_like(b))
         counters = (perf.n_iterations, perf.n_norm_evals, perf.initial_residual, perf.final_residual, perf.norm_factor)
         return s, x, s.history().copy(), counters
 
     fresh = {}
-    for tag, solver, kw in KIND_WALK[:8]:
+    for tag, solver, kw, *props in KIND_WALK:
+        if tag in fresh:  # (every distinct tag once)
+            continue
         r = capi.Registry()
         try:
-            fresh[tag] = solve_in(r, tag, solver, kw)[1:]
+            fresh[tag] = solve_in(r, tag, solver, kw, *props)[1:]
         finally:
             r.close()
     r = capi.Registry()
     try:
         in_use = []
         for lap in range(2):
-            for step, (tag, solver, kw) in enumerate(KIND_WALK):
-                s, x, hist, counters = solve_in(r, tag, solver, kw)
+            for step, (tag, solver, kw, *props) in enumerate(KIND_WALK):
+                s, x, hist, counters = solve_in(r, tag, solver, kw, *props)
                 fx, fhist, fcounters = fresh[tag]
                 np.testing.assert_array_equal(x, fx, err_msg=f"lap {lap} step {step} {tag}")
                 np.testing.assert_array_equal(hist, fhist, err_msg=f"lap {lap} step {step} {tag}")

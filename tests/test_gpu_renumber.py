@@ -11,6 +11,9 @@ import pytest
 
 from ogl_amd import capi, synthetic
 from helpers import blocked, oracle_csr, oracle_matrix, oracle_matrix_renumbered, oracle_precond_renumbered, to_new
+import chebyshev_walk as cw
+import factor_isai_walk as fw
+import precond_cases as pc
 
 pytestmark = pytest.mark.gpu
 
@@ -340,14 +343,18 @@ def test_block_jacobi_through_the_permutation_both_applies(reg, oracle, chunk_ro
 
 @pytest.mark.parametrize("name,kw", [("bj1", dict(preconditioner=capi.PRECOND_BJ)),
                                      ("gisai", dict(preconditioner=capi.PRECOND_GISAI)),
-                                     ("bj3_backend", dict(preconditioner=capi.PRECOND_BJ, max_block_size=3))])
+                                     ("bj3_backend", dict(preconditioner=capi.PRECOND_BJ, max_block_size=3)),
+                                     ("chebyshev", dict(preconditioner=capi.PRECOND_CHEBYSHEV)),
+                                     ("ic_isai", dict(preconditioner=capi.PRECOND_IC))])
 def test_stored_preconditioner_of_another_numbering_is_not_applied(oracle, chunk_rows, name, kw):
     """the preconditioner store is shared by all fields of a registry (Preconditioner.H:357).  A stored
     inverse diagonal, W, or block Jacobi whose VALUES are laid out in the device numbering of the field that generated
     it would be a silently permuted operator for a field whose device copy is numbered differently: such an object is
     regenerated for the solve instead (`PrecondData::foreign_to`), and the second field's history is the oracle's with
     ITS OWN preconditioner.  (Blocks kept block-major in the caller's order stay portable, as in the reference: the
-    applying solver carries the vectors through its permutation.)"""
+    applying solver carries the vectors through its permutation.)  Chebyshev's w and table are regenerated like the
+    inverse diagonal; a factor under `triangularSolves isai` is the portable row of the table -- W lives in the caller's
+    numbering, the second field adopts the stored object and applies the FIRST field's W through its own permutation."""
     a = synthetic.renumber_case(synthetic.poisson_case(14), 700, seed=1)
     b_case = synthetic.renumber_case(synthetic.poisson_case(14), 700, seed=2)            # same sizes, another numbering
     skw = dict(tolerance=1e-11, rel_tol=0.0, max_iter=200)
@@ -358,6 +365,8 @@ def test_stored_preconditioner_of_another_numbering_is_not_applied(oracle, chunk
             s = r.solver(f"store_{name}_{tag}", cfg(caching=3, **kw, **skw))
             if name == "bj3_backend":
                 s.set_property("precondCallerNumbering", 0.0)
+            if name == "ic_isai":
+                s.set_triangular_solves("isai")
             s.set_matrix(case)
             if tag == "B":      # (this field's counter says "use the stored object": Preconditioner.H:384-418)
                 s.set_property("preconditionerCaching", 2.0)
@@ -368,7 +377,20 @@ def test_stored_preconditioner_of_another_numbering_is_not_applied(oracle, chunk
         new_id = s.renumbering()
         assert not np.array_equal(new_id, sols[0][0].renumbering())
         A, (rp, cols, vals) = oracle_matrix_renumbered(oracle, case, new_id)
-        if name == "bj3_backend":
+        if name == "ic_isai":
+            # adopted: the counter went down, and z is the first field's walk on r in the caller's order
+            assert s.get_property("preconditionerCaching") == 1.0
+            assert s.get_property("triangularSolvesInUse") == 1.0
+            first = fw.Walk(oracle, *oracle_csr(oracle, a), "IC", isai=True, power=1, sweeps=0)
+            own = fw.Walk(oracle, *oracle_csr(oracle, case), "IC", isai=True, power=1, sweeps=0)
+            res = np.random.default_rng(3).standard_normal(case.n_cells)
+            assert not np.array_equal(first.apply(res), own.apply(res))                   # really two operators
+            np.testing.assert_array_equal(s.apply_preconditioner(res), first.apply(res))
+            P = pc.callback(first.apply, new_id)
+        elif name == "chebyshev":
+            assert s.get_property("preconditionerCaching") == 3.0                         # generated for this solve
+            P = cw.Walk(oracle, rp, cols, vals).precond()                                 # of its own renumbered system
+        elif name == "bj3_backend":
             P = oracle.Precond(rp, cols, vals, 3)                                         # the backend's own blocks
         elif kw["preconditioner"] == capi.PRECOND_BJ:
             P = oracle_precond_renumbered(oracle, case, rp, cols, vals, new_id, kw.get("max_block_size", 1))
